@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec at 1024^2, FLUX-schnell geometry + canny condition, 4 denoise steps (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--batch B] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
           or plain `python bench.py --gpus N`: with no torchrun environment the script launches its own N ranks (one fresh child
           process per GPU, started BEFORE anything touches the GPU; reference script/infer.sh:49-67 `accelerate launch`)
@@ -687,6 +687,22 @@ def _timed(one_step, steps, warmup, dev, world, timer, ops, power=None, per_pass
     return DU.max_over_ranks(elapsed, dev, world), out, own
 
 
+DUMP_BYTES = 64_000_000    # --dump-outputs: at most this much in all, over every rank's files
+
+
+def dump_output(path: str, t: torch.Tensor, max_elems: int) -> bool:
+    """Write `t` as a float32 .npy at `path`. Above `max_elems` elements, a fixed sample of them is written instead (1-D, at positions drawn from a
+    seeded generator in ascending order, so two runs with the same arguments sample the same elements). Returns whether it sampled."""
+    import numpy as np
+    a = t.detach().float().cpu()
+    sampled = a.numel() > max_elems
+    if sampled:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:max_elems].sort().values
+        a = a.reshape(-1)[idx]
+    np.save(path, a.numpy())
+    return sampled
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -707,7 +723,14 @@ def main():
     ap.add_argument("--small", action="store_true", help="debug: reduced depth (NOT the headline configuration)")
     ap.add_argument("--graph", action="store_true", help="capture one step (the whole denoise loop) in a HIP graph and replay it (SURVEY 8(f) rank 1)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: rehearse the multi-process harness (spawn, rendezvous, barriers, JSON) on the CPU with gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents the last timed step returned as DIR/latents.npy (DIR/latents_rank<r>.npy with --gpus > 1), "
+                         "float32, at most 64 MB in all (a fixed seeded sample of a larger output); inputs are seeded, so equal arguments compare run to run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a GPU run: --dry-run computes nothing")
     if args.pmc_child:                 # one counter pass of same_run_traffic(): the cfg2 workload's launches and nothing else
         args.gpus, args.config, args.batch, args.steps, args.warmup = 1, "cfg2", 4, 1, 1      # warm-up + one step: the parser keeps the second step's launches
         args.no_kernel_timer = args.no_cpu_baseline = args.no_scaling_base = args.no_other_configs = args.no_pmc = True
@@ -769,6 +792,12 @@ def main():
     sampler = _PowerSampler(dev) if rank == 0 else None
     elapsed, out, own_elapsed = _timed(one_step, args.steps, args.warmup, dev, world, timer, ops, power=sampler)
     power = sampler.stop() if sampler is not None else None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        path = os.path.join(args.dump_outputs, "latents.npy" if world == 1 else f"latents_rank{rank}.npy")
+        sampled = dump_output(path, out, DUMP_BYTES // 4 // world - 1024)          # 1024 elements of room per file for the .npy header
+        print(f"[bench] rank {rank}: wrote {path} ({'a fixed sample of ' if sampled else ''}{tuple(out.shape)} latents of the last timed step)",
+              file=sys.stderr, flush=True)
     # one all_gather of every rank's own record, so that a straggler (or a rank on the wrong device) shows in the one JSON line.
     # The measured MFMA-only rate of each rank's chip rides along: boxes differ by 8-12 % (DVFS), and cross-box comparisons need it.
     probe = not (args.no_kernel_timer or args.graph)          # profiling runs (--no-kernel-timer) keep the probe's launches out of the kernel statistics

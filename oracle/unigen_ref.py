@@ -9,7 +9,7 @@ diffusers / peft / ipdb are absent: ordinary ModuleNotFoundError) and `UniGenFlu
 (FluxJointRoPETransformerBlock, FluxSingleRoPETransformerBlock). Its self-contained torch-only definitions ARE run: tests/golden/ref_harness.py
 compiles them from the reference's files at run time (build container only; sha256-pinned sources, a namespace of torch symbols, a builtin
 whitelist, every free name checked), the make_ref_*_golden.py generators write their outputs as tensors, and
-tests/test_ref_leaf_cpu.py::test_committed_reference_fixtures_regenerate_bit_identically re-runs the generators against the committed files.
+tests/golden/check_ref_fixtures.py re-runs the generators against the committed files.
 Pinned rows of this file (22 reference definitions):
   leaves (tests/test_ref_leaf_cpu.py, ref_leaf.safetensors)
     modulated_flatten_literal / modulated_linear  <- modulated_flatten          src/UniGenUtils.py:204-228

@@ -17,7 +17,7 @@ TINY = dict(num_layers=2, num_single_layers=4, attention_head_dim=128, num_atten
 CONTROL = dict(use_rope=True, use_shared_expert=True, use_single_trans_blocks=True, single_control_dev=2)
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol(tmp_path):
     from unigen_amd import build, lib
     build.build()
     hdr = open(os.path.join(ROOT, "include", "unigen_hip.h")).read()
@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
     assert cdll.ug_version() >= 100
     # the ctypes mirror of ug_gemm_desc has the C layout (checked against a compile of the header)
     src = '#include "unigen_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%zu %zu %zu %zu", sizeof(ug_gemm_desc), offsetof(ug_gemm_desc, alpha), offsetof(ug_gemm_desc, M), offsetof(ug_gemm_desc, lora_r));return 0;}'
-    exe = os.path.join("/tmp", "ug_layout_check")
+    exe = str(tmp_path / "ug_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     sizes = list(map(int, subprocess.run([exe], capture_output=True, check=True).stdout.split()))
     D = lib.GemmDesc
@@ -770,6 +770,21 @@ def test_bench_refuses_more_ranks_than_gpus():
     # a torchrun-style environment whose world size disagrees with --gpus is an error too
     r = _run_bench(["--gpus", "2", "--dry-run"], env_extra=dict(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+    r = _run_bench(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_dump_output_is_float32_capped_and_reproducible(tmp_path):
+    """--dump-outputs writes float32 .npy files; an output above the element cap becomes a seeded sample that is the same on every run."""
+    import numpy as np
+    import bench
+    t = torch.randn(3, 5, 7, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    assert not bench.dump_output(str(tmp_path / "full.npy"), t, 1000)
+    full = np.load(tmp_path / "full.npy")
+    assert full.dtype == np.float32 and full.shape == (3, 5, 7) and np.array_equal(full, t.float().numpy())
+    assert bench.dump_output(str(tmp_path / "s1.npy"), t, 50) and bench.dump_output(str(tmp_path / "s2.npy"), t, 50)
+    s1, s2 = np.load(tmp_path / "s1.npy"), np.load(tmp_path / "s2.npy")
+    assert s1.dtype == np.float32 and s1.shape == (50,) and np.array_equal(s1, s2) and np.isin(s1, full).all()
 
 
 def test_consis_module_parameters_follow_the_reference():

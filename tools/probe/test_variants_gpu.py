@@ -17,7 +17,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-os.environ.setdefault("UG_LIB_PATH", os.path.join(ROOT, "tools", "probe", "libunigen_hip_probe.so"))
+# UG_LIB_PATH comes from the command line above: set here, it would move every other test collected in the same session onto the probe library
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
