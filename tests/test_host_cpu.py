@@ -80,6 +80,12 @@ def test_error_codes_without_gpu_compute():
     assert cdll.ug_adaln_modulate_bwd(16, 64, 16, 64, 16, 64, 4, 16, 64, None, 8, 64, 1e-6, None) == lib.UG_ERR_BAD_SHAPE                 # no partials buffer
     assert cdll.ug_adaln_modulate_bwd(16, 8192, 16, 8192, 16, 8192, 4, 16, 8192, 16, 8, 8192, 1e-6, None) == lib.UG_ERR_BAD_ALIGN and b"4096" in cdll.ug_last_error()
     assert cdll.ug_qk_rmsnorm_rope_bwd(16, 1024, 16, 1024, 16, 1024, 16, 16, None, None, 4, 4, 0, 1, 1024, 1e-6, None) == lib.UG_ERR_UNSUPPORTED   # head width > 256
+    assert cdll.ug_moe_gate_bwd(16, 16, 16, 16, 64, 16, 4, 64, 17, 16, 64, 16, None) == lib.UG_ERR_BAD_SHAPE and b"E <= 16" in cdll.ug_last_error()  # 17 experts
+    assert cdll.ug_moe_gate_bwd(16, 16, 16, 16, 64, 16, 4, 60, 16, 16, 64, 16, None) == lib.UG_ERR_BAD_ALIGN                # D % 8
+    assert cdll.ug_moe_gate_bwd_f32(16, 16, 16, 16, 64, 16, 4, 60, 2, 16, 64, 16, None) == lib.UG_ERR_BAD_ALIGN
+    assert cdll.ug_rowdot(16, 191, 16, 192, 16, 4, 3, 64, None) == lib.UG_ERR_BAD_SHAPE                                      # lda < groups * cols
+    assert cdll.ug_rowdot_f32(16, 192, 16, 191, 16, 4, 3, 64, None) == lib.UG_ERR_BAD_SHAPE                                  # ldb < groups * cols
+    assert cdll.ug_adaln_modulate_bwd(16, 4104, 16, 4104, 16, 4104, 4, 16, 4104, 16, 8, 4104, 1e-6, None) == lib.UG_ERR_BAD_ALIGN and b"4096" in cdll.ug_last_error()
 
 
 def test_no_cpu_fallback():
