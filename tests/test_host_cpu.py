@@ -88,6 +88,51 @@ def test_error_codes_without_gpu_compute():
     assert cdll.ug_adaln_modulate_bwd(16, 4104, 16, 4104, 16, 4104, 4, 16, 4104, 16, 8, 4104, 1e-6, None) == lib.UG_ERR_BAD_ALIGN and b"4096" in cdll.ug_last_error()
 
 
+def test_forward_projection_abi_rejections():
+    """The fused q/k epilogue, the LoRA segment and the stand-alone q/k pass refuse what they do not implement, before any launch (fake,
+    aligned pointers: every descriptor below differs from a valid one in exactly the field under test)."""
+    from unigen_amd import lib
+    cdll = lib.load()
+    P = 4096
+
+    def qkv(**kw):
+        d = lib.GemmDesc()
+        d.A, d.W, d.C, d.lda, d.ldw, d.ldc, d.M, d.N, d.K = P, P, P, 64, 64, 768, 256, 768, 64
+        d.epilogue, d.qk_wq, d.qk_wk, d.rope_cs, d.qk_until_n, d.qk_dh, d.qk_eps = lib.EPI_QKV_ROPE, P, P, P, 512, 128, 1e-6
+        for k, v in kw.items():
+            setattr(d, k, v)
+        rc = cdll.ug_gemm_bf16(ctypes.byref(d), None)
+        return rc, cdll.ug_last_error()
+
+    lora = dict(lora_T=P, ldt=64, lora_B=P, ldb=64, lora_r=64)
+    rc, msg = qkv(**lora)
+    assert rc == lib.UG_ERR_UNSUPPORTED and b"LoRA" in msg
+    rc, msg = qkv(groups=2)
+    assert rc == lib.UG_ERR_UNSUPPORTED and b"grouped" in msg
+    for rpb in (1, 128, 255):                                               # positions would wrap more than once per 16-row group
+        assert qkv(rope_rpb=rpb)[0] == lib.UG_ERR_BAD_SHAPE
+    rc, msg = qkv(c_rpb=448, c_bstride=512)                                 # the C row map would split a 256-row tile
+    assert rc == lib.UG_ERR_UNSUPPORTED and b"multiple of 256" in msg
+    assert qkv(gelu_from_n=256)[0] == lib.UG_ERR_BAD_SHAPE                  # GELU inside the q | k columns
+    assert qkv(c_shift_from_n=256, c_shift=8, ldc=776)[0] == lib.UG_ERR_BAD_SHAPE
+    assert qkv(qk_dh=96)[0] == lib.UG_ERR_UNSUPPORTED
+    assert qkv(rope_cs=None)[0] == lib.UG_ERR_BAD_ALIGN                     # the table may only be omitted at head width 64
+    # the LoRA segment of the plain epilogues
+    rc, msg = qkv(epilogue=lib.EPI_BIAS, **dict(lora, lora_r=96))
+    assert rc == lib.UG_ERR_UNSUPPORTED and b"lora_r" in msg
+    rc, msg = qkv(epilogue=lib.EPI_BIAS, groups=2, **lora)
+    assert rc == lib.UG_ERR_UNSUPPORTED and b"not grouped" in msg
+    assert qkv(epilogue=lib.EPI_BIAS, **dict(lora, ldt=60))[0] == lib.UG_ERR_BAD_ALIGN
+    # ug_qk_rmsnorm_rope(buf, ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh, wq_a, wk_a, wq_b, wk_b, split,
+    #                    cos, sin, eps, stream)
+    qk = lambda dh=128, wq_b=P, wk_b=P, cos=P, sin=P, q_off=0: cdll.ug_qk_rmsnorm_rope(P, 768, 1, 16, 16, 0, q_off, 256, 2, dh, None, None, wq_b, wk_b,
+                                                                                       0, cos, sin, 1e-6, None)
+    assert qk(dh=96) == lib.UG_ERR_UNSUPPORTED
+    assert qk(sin=None) == lib.UG_ERR_BAD_SHAPE and qk(cos=None) == lib.UG_ERR_BAD_SHAPE
+    assert qk(wk_b=None) == lib.UG_ERR_BAD_SHAPE and b"pairs" in cdll.ug_last_error()
+    assert qk(wq_b=None) == lib.UG_ERR_BAD_SHAPE
+
+
 def test_no_cpu_fallback():
     from unigen_amd import lib, ops
     a = torch.zeros(8, 64, dtype=torch.bfloat16)

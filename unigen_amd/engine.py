@@ -530,7 +530,7 @@ class HipModule(nn.Module):
         # live LoRA adapters of to_q / to_k / to_v: T = ns A_cat^T in one GEMM, then the K-segment of this launch (the q/k RMSNorm + RoPE then
         # runs as its own kernel: UG_EPI_QKV_ROPE is not LoRA-extended)
         lt, lb = self._lora_operands([a + ".to_q", a + ".to_k", a + ".to_v"], ns, B * Ls, "s")
-        fused = (lt is None and wq is not None and (cs is not None or (cos is None and dh == 64)) and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, ns.dtype))
+        fused = (lt is None and wq is not None and (cs is not None or (cos is None and dh == 64)) and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, ns.dtype, c_rpb=Ls, rope_rpb=Ls))
         ops.gemm(ns, w_qkv, b_qkv, qkv2[Lc:], M=B * Ls, ldc=3 * D, c_map=RowMap(Ls, Lj),
                  qk_rope=ops.QkRope(wq, wk, cs, Ls, Lc, 2 * D, dh=dh) if fused else None, lora_t=lt, lora_b=lb)
         # context stream
@@ -587,7 +587,7 @@ class HipModule(nn.Module):
             w2, b2 = self._attn_qkv(a2)
             w2q, w2k = opt(a2 + ".norm_q.weight"), opt(a2 + ".norm_k.weight")
             lt, lb = self._lora_operands([a2 + ".to_q", a2 + ".to_k", a2 + ".to_v"], n2, B * Ls, "s")
-            fused2 = lt is None and w2q is not None and dh == 64 and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, n2.dtype)     # attn2 has no RoPE
+            fused2 = lt is None and w2q is not None and dh == 64 and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, n2.dtype, c_rpb=0, rope_rpb=Ls)     # attn2 has no RoPE
             ops.gemm(n2, w2, b2, q2, M=B * Ls, qk_rope=ops.QkRope(w2q, w2k, None, Ls, 0, 2 * D, dh=dh) if fused2 else None, lora_t=lt, lora_b=lb)
             if w2q is not None and not fused2:
                 ops.qk_rmsnorm_rope(q2, batches=B, rows_per_batch=Ls, ld=3 * D, q_off=0, k_off=D, heads=H, dh=dh, wq_b=w2q, wk_b=w2k, split=0)

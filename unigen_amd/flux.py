@@ -303,7 +303,7 @@ class UniGenFlux(HipModule):
             # q / k RMSNorm + RoPE ride in the same launch's epilogue when the shapes allow (whole 256^2 tiles)
             # live LoRA adapters of the four projections: ONE T = n A_cat^T for all of them, then the K-segment of this launch (engine._lora_operands)
             lt, lb = self._lora_operands([a + ".to_q", a + ".to_k", a + ".to_v", p + ".proj_mlp"], n, B * Lj, "j")
-            fused = lt is None and cs is not None and ops.qk_rope_fusable(B * Lj, 7 * D, 2 * D, dh, n.dtype)
+            fused = lt is None and cs is not None and ops.qk_rope_fusable(B * Lj, 7 * D, 2 * D, dh, n.dtype, c_rpb=0, rope_rpb=Lj)
             ops.gemm(n, w7, b7, sb, M=B * Lj, ldc=8 * D, epilogue=L.EPI_BIAS_GELU, gelu_from_n=3 * D, c_shift_from_n=3 * D, c_shift=D,
                      qk_rope=ops.QkRope(wq, wk, cs, Lj, 0, 2 * D, dh=dh) if fused else None, lora_t=lt, lora_b=lb)
         else:

@@ -121,13 +121,17 @@ class QkRope:
         self.wq, self.wk, self.cs, self.rpb, self.pos0, self.until_n, self.eps, self.dh = wq, wk, cs, rows_per_batch, pos0, until_n, eps, dh
 
 
-def qk_rope_fusable(M: int, N: int, until_n: int, dh: int, dtype: torch.dtype) -> bool:
-    """Whether ug_gemm_bf16 can take q/k RMSNorm + RoPE in its epilogue for this projection: bf16, heads of 128, whole 256^2 tiles, and
-    at least one full round of them (below that the dispatcher prefers the 128^2 kernel, which has no such epilogue).
+def qk_rope_fusable(M: int, N: int, until_n: int, dh: int, dtype: torch.dtype, *, c_rpb: int = 0, rope_rpb: int = 0) -> bool:
+    """Whether ug_gemm_bf16 can take q/k RMSNorm + RoPE in its epilogue for this projection: bf16, heads of 64 or 128, whole 256^2 tiles, and
+    at least one full round of them (below that the dispatcher prefers the 128^2 kernel, which has no such epilogue). c_rpb / rope_rpb are the
+    rows per batch of the launch's C row map and of its positions (0, the default: identity map, position = row): the epilogue needs the
+    former a multiple of 256 (one scalar row map per tile) and the latter 0 or >= 256 (at most one position wrap per 16-row group) -
+    launch_qkrope refuses anything else.
     UG_GEMM_FUSE_QKROPE=0 keeps the stand-alone ug_qk_rmsnorm_rope pass (A/B measurements)."""
     if os.environ.get("UG_GEMM_FUSE_QKROPE", "1") == "0":
         return False
-    return (dtype == torch.bfloat16 and dh in (64, 128) and M % 256 == 0 and N % 256 == 0 and until_n % 256 == 0 and (M // 256) * (N // 256) >= 256)
+    return (dtype == torch.bfloat16 and dh in (64, 128) and M % 256 == 0 and N % 256 == 0 and until_n % 256 == 0 and (M // 256) * (N // 256) >= 256
+            and c_rpb % 256 == 0 and (rope_rpb == 0 or rope_rpb >= 256))
 
 
 _gemm_ws: dict = {}
