@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec at 1024^2, FLUX-schnell geometry + canny condition, 4 denoise steps (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--batch B] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--batch B] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
           or plain `python bench.py --gpus N`: with no torchrun environment the script launches its own N ranks (one fresh child
           process per GPU, started BEFORE anything touches the GPU; reference script/infer.sh:49-67 `accelerate launch`)
@@ -13,9 +13,13 @@ excluded. Multi-GPU is batch-parallel: every rank holds a weight r
 are the barriers around the timed region and one MAX all-reduce of the elapsed time (weak scaling).
 
 The JSON line carries `roofline` (dominant kernel = the bf16 MFMA GEMM: algorithmic FLOPs per launch / HIP-event duration of
-the launches inside the timed region, against the 2.5 PFLOP/s datasheet peak and against the MFMA-only rate measured on this chip) and
+the launches inside the timed region, against the 2.5 PFLOP/s datasheet peak) and `power` (hwmon, inside the timed region).
+
+A plain run does nothing beyond set-up, warm-up, the timed steps, --dump-outputs and the JSON line. `--full` adds everything that takes
+work of its own after the timed region: the bare-MFMA probe (`roofline.peak_measured`, `e2e_frac_of_measured`), `scaling_base`,
 `cpu_baseline` (the oracle = CPU restatement of the reference, timed on this box's host cores on ONE full-depth forward of the same
-workload at B = 1 with the GPU run's own weights; an image = 4 such forwards).
+workload at B = 1 with the GPU run's own weights; an image = 4 such forwards), `parity` against the golden fixture, `small_m`,
+`other_configs` and the rocprofv3 counter passes behind `roofline.traffic`. The timed steps and `ms_per_step` are the same either way.
 """
 from __future__ import annotations
 
@@ -556,7 +560,8 @@ def _roofline_blocks(s, elapsed, pk16, pk32, attn_kernel, traffic_file=None, liv
     out["roofline"] = dict(bound="mfma", kernel="gemm256_kernel / gemm128_kernel (ug_gemm_bf16)", achieved=ach, peak=MFMA_BF16_PEAK_TFLOPS, unit="TFLOP/s",
                            frac=ach / MFMA_BF16_PEAK_TFLOPS, peak_measured=pk16 or None, frac_of_measured=meas(ach, pk16),
                            peak_measured_note=("ug_probe_mfma_bf16: bare v_mfma_f32_16x16x32_bf16 loop (the GEMM's shape), register operands with random values, "
-                                               f"one wave per SIMD on every CU, HIP events; the 32x32x16 shape (attention) measures {pk32:.0f}"),
+                                               f"one wave per SIMD on every CU, HIP events; the 32x32x16 shape (attention) measures {pk32:.0f}") if pk16
+                           else "not measured in this run (bench.py --full runs the probe)",
                            traffic=traffic, traffic_note=traffic_note, traffic_source=traffic_src, pmc_gemm256=pmc or None, launches=gm["launches"],
                            avg_launch_us=1000.0 * gm["ms"] / gm["launches"], avg_launch_gflop=gm["flops"] / gm["launches"] / 1e9,
                            share_of_step_time=gm["ms"] * 1e-3 / elapsed)
@@ -703,7 +708,29 @@ def dump_output(path: str, t: torch.Tensor, max_elems: int) -> bool:
     return sampled
 
 
-def main():
+def extra_blocks(args, world: int, config: str) -> set:
+    """The measurements a run makes after its timed steps, beside the headline figure: none without --full. With it, what the run's shape
+    allows and no --no-* option leaves out: `probe` (bare-MFMA rate), `scaling_base`, `cpu_baseline` (+ `parity`), `small_m`, `other_configs`,
+    `pmc` (the rocprofv3 counter passes)."""
+    if not args.full:
+        return set()
+    timed_kernels = not (args.no_kernel_timer or args.graph)
+    cfg2 = world == 1 and config == "cfg2" and args.batch == 4 and not (args.small or args.graph)
+    out = set()
+    if timed_kernels:
+        out.add("probe")
+    if cfg2 and not args.no_scaling_base:
+        out.add("scaling_base")
+    if world == 1 and not args.no_cpu_baseline:
+        out.add("cpu_baseline")
+    if cfg2 and timed_kernels and not args.no_other_configs:
+        out |= {"small_m", "other_configs"}
+    if cfg2 and timed_kernels and not (args.no_pmc or _under_profiler()):
+        out.add("pmc")
+    return out
+
+
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -712,13 +739,16 @@ def main():
                     help="BASELINE.json configs: cfg2 = UniGenFlux canny B=4 (the metric's configuration, default at N = 1); cfg4 = the same model at B=8 per "
                          "GPU (global 64 on 8 GPUs; default at N > 1); cfg3 = MultiCondtionUniGenFlux depth+canny+openpose B=8; cfg5 = UniGenSD3 depth B=8 (CFG, 28 steps)")
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU per step; default 4 for cfg2, 8 for cfg3 / cfg4 / cfg5 (reference infer.py:173 shards samples by rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure: the MFMA probe, scaling_base, cpu_baseline and parity, "
+                         "small_m, other_configs and the rocprofv3 counter passes (each can be left out with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full, N = 1: skip cpu_baseline and parity")
     ap.add_argument("--cpu-baseline", choices=["auto", "full", "slice", "cfg1"], default="auto",
-                    help="full = one full-depth 1024^2 oracle forward x 4 (needs ~90 GB host RAM); cfg1 = BASELINE configs[0] end to end (512^2, B = 1, 4 steps) on CPU and GPU")
+                    help="with --full: full = one full-depth 1024^2 oracle forward x 4 (needs ~90 GB host RAM); cfg1 = BASELINE configs[0] end to end (512^2, B = 1, 4 steps) on CPU and GPU")
     ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-scaling-base", action="store_true", help="N = 1, cfg2 only: skip the extra B = 8 measurement (cfg4's per-GPU shape, the like-for-like base of the 1 -> 8 curve)")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1, cfg2 only: skip the cfg3 / cfg5 blocks (other_configs: 1 warm-up + 3 passes each at B = 8) and the batch-1 blocks (small_m)")
-    ap.add_argument("--no-pmc", action="store_true", help="N = 1, cfg2 only: skip the two rocprofv3 --pmc child passes that measure roofline.traffic in this run (then read from profiles/)")
+    ap.add_argument("--no-scaling-base", action="store_true", help="with --full, N = 1, cfg2 only: skip the extra B = 8 measurement (cfg4's per-GPU shape, the like-for-like base of the 1 -> 8 curve)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, N = 1, cfg2 only: skip the cfg3 / cfg5 blocks (other_configs: 1 warm-up + 3 passes each at B = 8) and the batch-1 blocks (small_m)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full, N = 1, cfg2 only: skip the rocprofv3 --pmc child passes that measure roofline.traffic in this run (then read from profiles/)")
     ap.add_argument("--pmc-child", action="store_true", help="internal: the workload of one counter pass (cfg2, B = 4, one step, nothing else)")
     ap.add_argument("--small", action="store_true", help="debug: reduced depth (NOT the headline configuration)")
     ap.add_argument("--graph", action="store_true", help="capture one step (the whole denoise loop) in a HIP graph and replay it (SURVEY 8(f) rank 1)")
@@ -726,6 +756,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the latents the last timed step returned as DIR/latents.npy (DIR/latents_rank<r>.npy with --gpus > 1), "
                          "float32, at most 64 MB in all (a fixed seeded sample of a larger output); inputs are seeded, so equal arguments compare run to run")
+    return ap
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -769,6 +804,7 @@ def main():
     if args.batch <= 0:
         args.batch = 4 if config == "cfg2" else 8
     B = args.batch
+    extra = extra_blocks(args, world, config)
     if config == "cfg5":
         model, one_step, info = _sd3_workload(B, rank, dev, args.small)
     else:
@@ -799,8 +835,9 @@ def main():
         print(f"[bench] rank {rank}: wrote {path} ({'a fixed sample of ' if sampled else ''}{tuple(out.shape)} latents of the last timed step)",
               file=sys.stderr, flush=True)
     # one all_gather of every rank's own record, so that a straggler (or a rank on the wrong device) shows in the one JSON line.
-    # The measured MFMA-only rate of each rank's chip rides along: boxes differ by 8-12 % (DVFS), and cross-box comparisons need it.
-    probe = not (args.no_kernel_timer or args.graph)          # profiling runs (--no-kernel-timer) keep the probe's launches out of the kernel statistics
+    # With --full the measured MFMA-only rate of each rank's chip rides along: boxes differ by 8-12 % (DVFS), and cross-box comparisons need it.
+    # The probe is a run of its own; profiling runs (--no-kernel-timer) keep its launches out of the kernel statistics.
+    probe = "probe" in extra
     pk16 = ops.probe_mfma_peak(dev, shape=1) if probe else 0.0
     pk32 = ops.probe_mfma_peak(dev, shape=0) if probe else 0.0
     per_rank = [dict(rank=i, images=int(r[0]), seconds=r[1], images_per_s=r[0] / r[1], device_index=int(r[2]), mfma_probe_16x16x32_tflops=r[3],
@@ -808,7 +845,7 @@ def main():
                 for i, r in enumerate(DU.all_gather_floats([B * args.steps, own_elapsed, local_rank, pk16, pk32], dev, world))]
 
     scaling_base = None
-    if world == 1 and config == "cfg2" and B == 4 and not args.no_scaling_base and not args.small and not args.graph:
+    if "scaling_base" in extra:
         # cfg4's per-GPU share (B = 8) on ONE GPU: the like-for-like base of the 1 -> 8 scaling curve (N > 1 lines run B = 8 per GPU);
         # measured after the timed region, same model
         del one_step
@@ -854,7 +891,7 @@ def main():
             if os.path.exists(tf) and not args.small and config == "cfg2" and B == 4:      # PMC passes of this same command (see the file's `source`, tools/pmc_summary.py)
                 traffic_file = tf
             line.update(_roofline_blocks(s, elapsed, pk16, pk32, info["attn_kernel"], traffic_file))
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in extra:
             if config in ("cfg3", "cfg5"):
                 line["cpu_baseline"] = cpu_baseline_other(model, config)
             else:
@@ -864,7 +901,7 @@ def main():
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
             if config != "cfg5":
                 line["parity"] = fixture_parity(dev)
-        if world == 1 and config == "cfg2" and B == 4 and not (args.small or args.graph or args.no_other_configs or args.no_kernel_timer):
+        if "small_m" in extra:
             # the batch-1 regime on the same model (same weights, nothing rebuilt): a few seconds
             small = {}
             for nm in ("b1_1024", "cfg1_gpu"):
@@ -873,7 +910,7 @@ def main():
                 except Exception as e:
                     small[nm] = dict(error=f"{type(e).__name__}: {e}")
             line["small_m"] = small
-        if world == 1 and config == "cfg2" and B == 4 and not (args.small or args.graph or args.no_other_configs or args.no_kernel_timer):
+        if "other_configs" in extra:
             # BASELINE configs[2] and [4] inside the driver's own record: one warm-up + one pass each at their stated B = 8,
             # after everything of the headline block is final - the cfg2 numbers above are untouched by this
             import gc
@@ -888,7 +925,7 @@ def main():
                 except Exception as e:                      # the headline line must survive: the failure is recorded, never hidden
                     others[oc] = dict(error=f"{type(e).__name__}: {e}")
             line["other_configs"] = others
-        if world == 1 and config == "cfg2" and B == 4 and s and not (args.small or args.graph or args.no_pmc or _under_profiler()):
+        if "pmc" in extra and s:
             # roofline.traffic from THIS run's own counter passes (two rocprofv3 children, after every timed region); on any failure the recorded profile stays
             import gc
             model = one_step = step8 = out = None       # the parent's 37 GB of weights go before the children build their own copy

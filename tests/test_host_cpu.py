@@ -838,6 +838,34 @@ def test_bench_dump_output_is_float32_capped_and_reproducible(tmp_path):
     assert s1.dtype == np.float32 and s1.shape == (50,) and np.array_equal(s1, s2) and np.isin(s1, full).all()
 
 
+def test_bench_measures_beyond_the_headline_only_with_full(monkeypatch):
+    """A plain run makes no measurement after its timed steps; --full makes every one the run's shape allows, and each --no-* option
+    leaves its own out."""
+    import bench
+    monkeypatch.setattr(bench, "_under_profiler", lambda: False)
+
+    def extra(argv, world=1):
+        args = bench.parser().parse_args(argv)
+        config = args.config or ("cfg2" if world == 1 else "cfg4")
+        args.batch = args.batch or (4 if config == "cfg2" else 8)
+        return bench.extra_blocks(args, world, config)
+
+    everything = {"probe", "scaling_base", "cpu_baseline", "small_m", "other_configs", "pmc"}
+    for argv in ([], ["--steps", "5", "--warmup", "2"], ["--config", "cfg3"], ["--graph"], ["--dump-outputs", "d"]):
+        assert extra(argv) == set(), argv
+    assert extra([], world=2) == set()
+    assert extra(["--full"]) == everything
+    assert extra(["--full", "--no-cpu-baseline", "--no-other-configs", "--no-scaling-base"]) == {"probe", "pmc"}
+    assert extra(["--full", "--no-pmc"]) == everything - {"pmc"}
+    assert extra(["--full", "--no-kernel-timer"]) == {"scaling_base", "cpu_baseline"}
+    assert extra(["--full", "--graph"]) == {"cpu_baseline"}
+    assert extra(["--full", "--batch", "8"]) == extra(["--full", "--small"]) == {"probe", "cpu_baseline"}
+    assert extra(["--full", "--config", "cfg5"]) == {"probe", "cpu_baseline"}
+    assert extra(["--full"], world=2) == {"probe"}
+    monkeypatch.setattr(bench, "_under_profiler", lambda: True)          # under a profiler the counter passes stay out
+    assert extra(["--full"]) == everything - {"pmc"}
+
+
 def test_consis_module_parameters_follow_the_reference():
     """use_consis_module (src/UniGenTransformer.py:893-923): two joint blocks `consis_module.{0,1}` under the reference's key names, trainable,
     default-initialised; the oracle's state shapes agree; with the flag off (every shipped configuration) nothing is registered."""
