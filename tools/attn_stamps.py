@@ -18,7 +18,7 @@ if "--build" in sys.argv:
     Bd.build()                                                      # the product objects the stamp library links against
     out = os.path.join(ROOT, "tools", "probe", "bin"); os.makedirs(out, exist_ok=True)
     obj = os.path.join(out, "attention_stamps.o")
-    extra = [a_ for a_ in sys.argv if a_.startswith("-D")]          # e.g. -DUG_ATTN_AIS_64=1: the stamps of a variant
+    extra = [a_ for a_ in sys.argv if a_.startswith("-D")]          # e.g. -DUG_ATTN_AIS_64=1 with tools/probe/patches/attn_r06_variants.diff applied: the stamps of a variant
     tag = os.environ.get("UG_STAMPS_TAG", "")
     subprocess.run([Bd.HIPCC, "-DUG_ATTN_STAMPS", *extra, *Bd.FLAGS, *Bd.EXTRA["attention.hip"], "-c", os.path.join(Bd.CSRC, "attention.hip"), "-o", obj], check=True)
     objs = [obj if s_ == "attention.hip" else os.path.join(Bd.CSRC, s_.replace(".hip", ".o")) for s_ in Bd.SOURCES]

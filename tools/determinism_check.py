@@ -22,7 +22,7 @@ for (M, N, K, epi) in [(16384, 9216, 3072, L.EPI_BIAS), (18432, 3072, 15360, L.E
         if ref is None: ref = out
         elif not torch.equal(ref, out): bad += 1; print("GEMM mismatch", M, N, K, epi, it, (ref.float() - out.float()).abs().max().item())
     print("gemm", M, N, K, epi, "ok" if bad == 0 else "MISMATCH", flush=True)
-# Round 6: the split-K slabs travel at system scope without fences (UG_GEMM_SLAB_SC). A slice's partial sums read too early - or a stale line of the slab area from
+# Round 6: the split-K slabs travel at system scope without fences (the fenced form: tools/probe/patches/gemm_r06_variants.diff). A slice's partial sums read too early - or a stale line of the slab area from
 # an earlier launch - would show as a run-to-run difference: 200 repeats of the sliced small-M launches, with ANOTHER sliced launch on other data in between (it
 # rewrites the same slab area and tickets), every output compared bit for bit with the first one.
 shapes = [(512, 3072, 12288), (1024, 3072, 12288), (1536, 3072, 15360)]

@@ -61,7 +61,7 @@ if os.environ.get("UG_AB_SHAPES") == "smallm":   # round 6: the launches whose t
         ("cfg2 single out 18432 x 3072 x 15360 res_gate", 18432, D, 5 * D, L.EPI_RES_GATE),
         ("cfg2 text ff down 2048 x 3072 x 12288 res_gate", 2048, D, 4 * D, L.EPI_RES_GATE),
     ]
-if os.environ.get("UG_AB_SHAPES") == "w128":     # round 6: launches the dispatcher gives to the 128^2 kernel (4-wave against 8-wave workgroups, -DUG_GEMM128_W8=1|2)
+if os.environ.get("UG_AB_SHAPES") == "w128":     # round 6: launches the dispatcher gives to the 128^2 kernel (4-wave against 8-wave workgroups: -DUG_GEMM128_W8=0|1 with tools/probe/patches/gemm_r06_variants.diff applied)
     B = 1
     SHAPES = [
         ("512^2 attn out 1024 x 3072 x 3072 res_gate", 1024, D, D, L.EPI_RES_GATE),

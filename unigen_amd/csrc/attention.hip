@@ -92,22 +92,13 @@ __device__ __forceinline__ float ug_max_halves(float x) {
 // the VALU, together (the lock-step loop, STAGGER = false, kept for A/B: both phases then serialise and a tile costs the sum).
 // Two barriers per tile; every thread fetches its share of K(t+2), V(t+1) at the start of an even segment and publishes it to LDS at
 // the end of the following odd one, into buffers nobody reads in those two segments.
-template <int DH, int NW, bool STAGGER, int PRIO = 1, bool WIDE = false, bool DMA = false, int KV = 64, int OCC = 2, int LSUM = 0, int AIS = 0, bool BUFD = false>   // head dim 128 | 64; waves per workgroup: 8 (256 query rows, 1 / CU) or 4 (128 rows, 2 / CU)
+template <int DH, int NW, bool STAGGER, int PRIO = 1, bool WIDE = false, bool DMA = false, int KV = 64, int OCC = 2, bool LSUM = false, bool BUFD = false>   // head dim 128 | 64; waves per workgroup: 8 (256 query rows, 1 / CU) or 4 (128 rows, 2 / CU)
 // BUFD (round 6; head width 64 / OCC 4 only): the whole-tile LDS-DMAs in BUFFER form. The stamps put group B's softmax segment 770 cycles above group A's
-// (2263 vs 1497), all of it the 4 DMA issues per wave and tile; AIS = 1 showed the cost follows the issuer (A's X 1063 -> 1937), i.e. it is the issue
-// sequence itself: per tile ~20 VALU instructions of lane-offset re-derivation (kept out of registers in round 3), a 64-bit VALU pointer bump,
-// two v_readfirstlane + s_nop 4 per operand, on a SIMD whose VALU the four waves' softmax already saturates. Here the per-lane byte offset is ONE
-// VGPR held through the loop (run 1's is that ^ 16: needs K and V to share a row stride that is a multiple of 16 elements - the dispatcher checks),
-// the (batch, head) base is an SGPR resource, the tile / run offset an SGPR: per tile 4 x (s_mov m0 + buffer_load ... lds), one v_xor, scalar adds.
-// AIS (round 6, DMA stagger only): WHO issues the LDS-DMAs of K(t+2) / V(t+1), and where. The per-segment stamps (tools/attn_stamps.py, profiles/r06b_*)
-// show the loop's period is the SUM of the two groups' softmax segments - the matrix segment X is the shorter one of every pair (dh 64: Y 1497 /
-// X 1063 cycles for group A, Y 2264 / X 1115 for group B) - and that group B's Y is 770 cycles longer than A's only because it opens with the
-// tile's 4 DMA issues per wave (~140 cycles each + their address arithmetic), while group A then sits 1300 cycles at the barrier behind its X.
-//   0: group B at the start of its softmax segment Y(t) (rounds 2-5);
-//   1: group A at the END of its matrix segment X(t) - the same global segment 2t+2, so every buffer-reuse and landing deadline is unchanged
-//      (K(t)'s and V(t-1)'s last readers finished in segment 2t+1; the data is waited for at the end of A's next softmax segment, 2t+3, and first
-//      read in 2t+4) - i.e. inside the time A would spend waiting for B's softmax anyway;
-//   2: split: group A issues K(t+2) at the end of X(t), group B V(t+1) at the start of Y(t) (each waits for its own).
+// (2263 vs 1497), all of it the 4 DMA issues per wave and tile, i.e. the issue sequence itself: per tile ~20 VALU instructions of lane-offset re-derivation
+// (kept out of registers in round 3), a 64-bit VALU pointer bump, two v_readfirstlane + s_nop 4 per operand, on a SIMD whose VALU the four waves'
+// softmax already saturates. Here the per-lane byte offset is ONE VGPR held through the loop (run 1's is that ^ 16: needs K and V to share a row stride
+// that is a multiple of 16 elements - the dispatcher checks), the (batch, head) base is an SGPR resource, the tile / run offset an SGPR: per tile
+// 4 x (s_mov m0 + buffer_load ... lds), one v_xor, scalar adds.
 // LSUM (round 6, stagger only): the softmax row sums leave the VALU. With the scores' scale / exp2 / max / pack the running sum `l += p` is one of ~5
 // VALU instructions per score and the softmax segment Y is what the barriers wait for (tools/attn_stamps.py); here each lane's probabilities are
 // summed on the matrix pipe instead, inside X, from the SAME packed bf16 fragments P.V consumes: v_mfma_f32_4x4x4_16b_bf16 (16 blocks of 4x4x4) with
@@ -115,13 +106,17 @@ template <int DH, int NW, bool STAGGER, int PRIO = 1, bool WIDE = false, bool DM
 // accumulated over the tile's 8 half-fragments: 8 two-pass MFMAs per tile and wave (+12.5 % matrix-pipe cycles) for 32 v_add_f32 (-20 % of the
 // softmax segment's issue cycles). The denominator is then the sum of the ROUNDED probabilities - the ones the numerator multiplies - not of their
 // fp32 originals (relative difference <= 2^-9 / sqrt(keys), below the output's own bf16 rounding).
+// (Round 6 also measured and dropped: five other assignments of the LDS-DMA issue to the wave groups, a 16-wave workgroup, the buffer form at head
+// width 128 and a second row-sum chain - stamps in profiles/r06b_*, rates in profiles/r06_attn_variants.log, code in
+// tools/probe/patches/attn_r06_variants.diff.)
 // KV: keys per tile. 64 everywhere in rounds 1-2; round 3 adds KV = 128 for head dim 64 (UniGenSD3): a 128-key tile of 128-byte rows is the
 // same 16 KiB image, the same register budget (S^T 64 + P 32 + O 32 + Q 16 against 32 + 16 + 64 + 32 at dh 128 / 64 keys) and the same 32
 // MFMAs per matrix segment as the dh 128 kernel, so the per-segment costs (two barriers, the max exchange, the lazy-rescale test, fences,
 // the first-read latency) are paid once per 128 keys instead of once per 64 (at dh 64 the kernel ran at 55-60 %
 // of its VALU-issue bound).
 // PRIO (stagger only): 0 = no priority games; 1 = s_setprio 1 around the matrix stream of every X segment; 2 = ONE static s_setprio 1 for
-// the younger wave group (waves 4-7) before the loop (cdna guide T5, static form). WIDE: 16-byte epilogue stores (T21).
+// the younger wave group (waves 4-7) before the loop (cdna guide T5, static form); 3 = s_setprio 1 around every softmax segment Y. WIDE: 16-byte
+// epilogue stores (T21).
 // DMA (stagger only): K / V tiles go HBM -> LDS with global_load_lds_dwordx4 (no staging registers, no ds_write): the swizzled image is
 // produced on the SOURCE side (lane l of an instruction lands at byte 16 l of a 1 KiB run = 4 rows at dh 128, so it fetches chunk
 // (l % 16) ^ f(row) of its row), and group B (waves 4-7) issues all of it at the start of its softmax segment, two segments ahead of use.
@@ -257,8 +252,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
         for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
     static_assert(!LSUM || STAGGER, "the matrix-pipe row sum lives in the stagger loop's X segment");
-    f32x4 lacc = {0.f, 0.f, 0.f, 0.f}, lacc2 = {0.f, 0.f, 0.f, 0.f};   // LSUM: register 0 of each = half of this lane's running row sum (rows 1-3 of its 4x4 block: unused
-                                                                       // copies); LSUM = 2: two chains, so that no MFMA of a k-step waits for the one issued just before it (4 more registers)
+    f32x4 lacc = {0.f, 0.f, 0.f, 0.f};                 // LSUM: register 0 = half of this lane's running row sum (rows 1-3 of its 4x4 block: unused copies)
     bf16x4 ones4 = {(short)0x3f80, (short)0x3f80, (short)0x3f80, (short)0x3f80};
     if constexpr (LSUM) asm volatile("" : "+v"(ones4));        // one VGPR pair for the loop, not re-materialised per use
 
@@ -344,7 +338,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
         const float m_new = up ? tmax : m_run;
         if (!__all(!up)) {
             const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            if constexpr (LSUM) { lacc[0] *= alpha; lacc2[0] *= alpha; } else l_run *= alpha;
+            if constexpr (LSUM) lacc[0] *= alpha; else l_run *= alpha;
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -411,11 +405,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
     // matrix pipe in this segment (its SIMD partner is in the VALU-only Y), so an exposed ds_read latency is an idle pipe. hipcc's
     // own order (sched_group_barrier hints included) ran the segment at 70-90 cycles per MFMA.
     auto qx_frag = [&](int s) __attribute__((always_inline)) -> bf16x8 { if constexpr (QLDS) return *(const bf16x8*)(smem + q_lds + 16 * ((2 * s) ^ qx)); else return qf[s]; };
-    auto do_X = [&](int t, auto cur_c, bool have_qk, auto&& hook, auto kofs_c) __attribute__((always_inline)) {
+    auto do_X = [&](int t, auto cur_c, bool have_qk) __attribute__((always_inline)) {
         constexpr int CUR = decltype(cur_c)::value;
-        constexpr int KOFS = decltype(kofs_c)::value;       // >= 0 (AIS 5): byte offset of the ring slot that holds K(t+1), a compile-time constant like CUR
         const unsigned char* Vbuf = smem + CUR * 2 * TILE + TILE;
-        const unsigned char* Kbuf = KOFS >= 0 ? smem + KOFS : smem + (CUR ^ 1) * 2 * TILE;
+        const unsigned char* Kbuf = smem + (CUR ^ 1) * 2 * TILE;
         bf16x8 vf[NKS][NDB];
         auto rdv = [&](int ks) __attribute__((always_inline)) {
 #pragma unroll
@@ -438,10 +431,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
             if constexpr (LSUM) {        // this lane's 8 probabilities of the k-step, summed on the matrix pipe (see the template's header)
                 const bf16x8 pw = pf[ks >> 1][ks & 1];
                 lacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones4, __builtin_shufflevector(pw, pw, 0, 1, 2, 3), lacc, 0, 0, 0);
-                if constexpr (LSUM == 2) lacc2 = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones4, __builtin_shufflevector(pw, pw, 4, 5, 6, 7), lacc2, 0, 0, 0);
-                else lacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones4, __builtin_shufflevector(pw, pw, 4, 5, 6, 7), lacc, 0, 0, 0);
+                lacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones4, __builtin_shufflevector(pw, pw, 4, 5, 6, 7), lacc, 0, 0, 0);
             }
-            hook(ks);                                                              // AIS 3: one LDS-DMA piece behind this k-step's MFMAs (no-op otherwise)
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 2 < NKS) rdv(ks + 2);
             else if (have_qk) {                                                    // the first 2 QPRE k-steps of the second half
@@ -492,7 +483,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
             if (t + 1 < ntiles) tile(t + 1, std::integral_constant<int, 1>{});
         }
     } else {
-        static_assert(!STAGGER || NW == 8 || (NW == 16 && DMA), "the stagger pairs the waves of one SIMD: w, w + 4 (and w + 8, w + 12 in the 16-wave form)");
+        static_assert(!STAGGER || NW == 8, "the stagger pairs the waves of one SIMD: w, w + 4");
         // X / Y stagger. A wave alternates a MATRIX-only segment X(t) = P.V of tile t followed by S^T = K.Q^T of tile t+1, and a
         // VALU-only segment Y(t+1) = online softmax of tile t+1. Waves 0-3 (group A) and 4-7 (group B) - the two waves of every
         // SIMD - run one segment apart, so in every segment a SIMD has one wave feeding the matrix pipe and one feeding the VALU
@@ -564,39 +555,28 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
             dko[u] = (unsigned)(row * (int)k_rs + ch * 8) * 2u;        // bytes
             dvo[u] = (unsigned)(row * (int)v_rs + ch * 8) * 2u;
         }
-        constexpr bool BUFD64 = BUFD && OCC == 4 && DH == 64;      // the one-live-VGPR form; any other BUFD kernel keeps its per-run lane offsets (dko / dvo) and only moves
-                                                                 // the tile part of the address from a 64-bit VALU pointer + v_readfirstlane pair into the scalar offset
-        static_assert(!BUFD || DMA, "BUFD is a form of the LDS-DMA staging");
-        static_assert(!BUFD64 || NIW == 2 || NIW == 1, "the head-width-64 form derives run 1 from run 0");
+        static_assert(!BUFD || (DMA && DH == 64 && OCC == 4), "BUFD is the head-width-64, two-workgroups-per-CU form of the LDS-DMA staging");
+        static_assert(!BUFD || NIW == 2, "the buffer form derives run 1 from run 0");
         unsigned bvo = 0;                              // BUFD: lane offset of run 0 inside a wave's pair of 1 KiB runs (rows lane / 8, swizzled chunk)
         u32x4 rsK = {0u, 0u, 0u, 0u}, rsV = {0u, 0u, 0u, 0u};
         if constexpr (BUFD) {
-            if constexpr (BUFD64) {
-                const int sw = (((lane >> 4) & 1) << 2) | ((lane >> 4) & 2);
-                bvo = (unsigned)((lane >> 3) * (int)k_rs) * 2u + (unsigned)(((lane & 7) ^ sw) << 4);
-                if constexpr (NIW == 1) bvo ^= (unsigned)(wb & 1) << 4;           // one run per wave: the run's parity (row bit 3) is the swizzle's chunk bit 0
-                asm volatile("" : "+v"(bvo));
-            }
+            const int sw = (((lane >> 4) & 1) << 2) | ((lane >> 4) & 2);
+            bvo = (unsigned)((lane >> 3) * (int)k_rs) * 2u + (unsigned)(((lane & 7) ^ sw) << 4);
+            asm volatile("" : "+v"(bvo));
             const unsigned long long ka = (unsigned long long)uniform_ptr(Kb), va = (unsigned long long)uniform_ptr(Vb);
             rsK = (u32x4){(unsigned)ka, (unsigned)(ka >> 32), 0xffffffffu, 0x00020000u};
             rsV = (u32x4){(unsigned)va, (unsigned)(va >> 32), 0xffffffffu, 0x00020000u};
         }
         auto dma_tile = [&](const bf16_t* base, int64_t rs, const unsigned (&off)[NIW], int tile, unsigned dst, auto is_k) {
             if (tile * KVB + KVB <= Lkv) {             // whole tile: wave-uniform base (SGPR pair) + per-lane 32-bit byte offset
-                if constexpr (BUFD && !BUFD64) {
-                    const unsigned so = (unsigned)(tile * KVB * (int)rs) * 2u;                             // scalar: the tile part; the run rows are in the lane offsets
-#pragma unroll
-                    for (int u = 0; u < NIW; ++u) {
-                        if constexpr (decltype(is_k)::value) bufds16(rsK, off[u], so, dst + u * 1024); else bufds16(rsV, off[u], so, dst + u * 1024);
-                    }
-                } else if constexpr (BUFD) {
+                if constexpr (BUFD) {
                     const unsigned so = (unsigned)((tile * KVB + wb * NIW * RPI) * (int)rs) * 2u;          // scalar: tile and run-pair part of the byte offset
                     if constexpr (decltype(is_k)::value) {
                         bufds16(rsK, bvo, so, dst);
-                        if constexpr (NIW == 2) bufds16(rsK, bvo ^ 16u, so + (unsigned)(RPI * (int)rs) * 2u, dst + 1024);
+                        bufds16(rsK, bvo ^ 16u, so + (unsigned)(RPI * (int)rs) * 2u, dst + 1024);
                     } else {
                         bufds16(rsV, bvo, so, dst);
-                        if constexpr (NIW == 2) bufds16(rsV, bvo ^ 16u, so + (unsigned)(RPI * (int)rs) * 2u, dst + 1024);
+                        bufds16(rsV, bvo ^ 16u, so + (unsigned)(RPI * (int)rs) * 2u, dst + 1024);
                     }
                 } else if constexpr (OCC == 4 && DH == 64 && NIW == 2) {
                     // Lane offsets re-derived at the issue (not kept live through the loop: registers are what this form is short of), cheaply:
@@ -637,39 +617,14 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
                 }
             }
         };
-        // AIS 5: K tiles live in a ring of THREE slots - the two K halves of the double buffer and the (unused: Q stays in registers) Q image area behind it
-        auto kslot = [&](int s3) __attribute__((always_inline)) -> int { return s3 < 2 ? s3 * 2 * TILE : 4 * TILE; };
-        static_assert(AIS != 5 || (DMA && !QLDS && !BUFD64), "AIS 5 keeps its third K slot where the Q image would be");
         auto dma_fetch = [&](int kt, int vt) __attribute__((always_inline)) {         // tiles past the end are simply not fetched
             const unsigned l0 = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + wb * NIW * 1024;
-            if (kt < ntiles) dma_tile(Kb, k_rs, dko, kt, l0 + (AIS == 5 ? kslot(kt % 3) : (kt & 1) * 2 * TILE), std::true_type{});
+            if (kt < ntiles) dma_tile(Kb, k_rs, dko, kt, l0 + (kt & 1) * 2 * TILE, std::true_type{});
             if (vt < ntiles) dma_tile(Vb, v_rs, dvo, vt, l0 + (vt & 1) * 2 * TILE + TILE, std::false_type{});
-        };
-        static_assert(AIS == 0 || DMA, "AIS re-assigns the LDS-DMA issue");
-        static_assert((AIS != 3 && AIS != 4) || (BUFD64 && NKS == 4 && NIW == 2), "AIS 3 / 4 spread the buffer-form pieces over the P.V k-steps");
-        auto dma_piece = [&](int kt, int vt, int j) __attribute__((always_inline)) {
-            if constexpr (BUFD64) {
-                const unsigned l0 = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + wb * NIW * 1024;
-                const int tile = j < 2 ? kt : vt;
-                if (tile >= ntiles) return;
-                const unsigned dst = l0 + (tile & 1) * 2 * TILE + (j < 2 ? 0 : TILE);
-                if (tile * KVB + KVB <= Lkv) {
-                    const unsigned so = (unsigned)((tile * KVB + wb * NIW * RPI) * (int)k_rs) * 2u;
-                    if (j == 0) bufds16(rsK, bvo, so, dst);
-                    else if (j == 1) bufds16(rsK, bvo ^ 16u, so + (unsigned)(RPI * (int)k_rs) * 2u, dst + 1024);
-                    else if (j == 2) bufds16(rsV, bvo, so, dst);
-                    else bufds16(rsV, bvo ^ 16u, so + (unsigned)(RPI * (int)k_rs) * 2u, dst + 1024);
-                } else if (j == 0) dma_tile(Kb, k_rs, dko, tile, dst, std::true_type{});
-                else if (j == 2) dma_tile(Vb, v_rs, dvo, tile, dst, std::false_type{});
-            }
         };
         auto dma_wait = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
         if constexpr (PRIO == 2) { if (!groupA) __builtin_amdgcn_s_setprio(1); }
-        if constexpr (DMA && (AIS == 1 || AIS == 3)) {         // group A is the issuer throughout
-            if (groupA) { dma_fetch(0, ntiles); dma_wait(); }      // K(0) only
-            seg_barrier();
-            if (groupA) dma_fetch(1, 0);                           // waited for at the end of A's Y(0)
-        } else if constexpr (DMA) {
+        if constexpr (DMA) {
             if (!groupA) { dma_fetch(0, ntiles); dma_wait(); }     // K(0) only
             seg_barrier();
             if (!groupA) dma_fetch(1, 0);
@@ -682,16 +637,12 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
         if (!groupA) seg_barrier();                    // B idles through segment 0
         UG_ASTAMP(1);
         do_QK(0, std::integral_constant<int, 0>{});    // A: segment 0 | B: segment 1
-        if (!groupA) { if constexpr (DMA && AIS != 1 && AIS != 3) dma_wait(); else if constexpr (!DMA) publish(1, 0); }    // end of segment 1 (B)
+        if (!groupA) { if constexpr (DMA) dma_wait(); else publish(1, 0); }    // end of segment 1 (B)
         seg_barrier();
         // one tile = Y(t) | X(t); buffer parity is a compile-time constant (two tiles per trip)
-        auto tile = [&](int t, auto cur_c, auto k3_c) __attribute__((always_inline)) {
-            constexpr int K3 = decltype(k3_c)::value;            // t % 3 (AIS 5: the K ring slot of tile t; the loop is unrolled over 6 tiles so that it is a constant)
+        auto tile = [&](int t, auto cur_c) __attribute__((always_inline)) {
             // Y(t): A in odd segment 2t+1 (publishes K(t+1), V(t) at its end) | B in even segment 2t+2 (fetches K(t+2), V(t+1) at its start)
-            if (!groupA) { if constexpr (DMA && AIS == 0) dma_fetch(t + 2, t + 1); else if constexpr (DMA && (AIS == 2 || AIS == 4 || AIS == 5)) dma_fetch(ntiles, t + 1); else if constexpr (!DMA) fetch(t + 2, t + 1); }
-            // AIS 5: group A issues K(t+2) at the START of its softmax segment (2t+1) into ring slot (t+2) % 3, whose last readers (QK(t-1): segments 2t-2, 2t-1) are
-            // done - with two slots it would be the buffer group B's X(t-1) reads K(t) from right now; group B keeps V(t+1) (start of ITS softmax segment, 2t+2)
-            if constexpr (DMA && AIS == 5) { if (groupA) dma_fetch(t + 2, ntiles); }
+            if (!groupA) { if constexpr (DMA) dma_fetch(t + 2, t + 1); else fetch(t + 2, t + 1); }
             if constexpr (PRIO == 3) __builtin_amdgcn_s_setprio(1);                  // the softmax segment outranks the partner's matrix stream at issue
             do_SM();
             // P^T is "used" here: hipcc otherwise sinks the (pure) scale / exp2 / pack chain across the barrier to its first use, the
@@ -703,57 +654,28 @@ __global__ __launch_bounds__(64 * NW, OCC) void flash_attn_kernel(
             // group A publishes K(t+1), V(t) and at once re-fills the staging registers with K(t+2), V(t+1): its VALU segment has slack
             // (the partner's matrix segment is longer), whereas a fetch at the head of its own X(t) delayed the first MFMA
             if constexpr (!DMA) { if (groupA) { publish(t + 1, t); fetch(t + 2, t + 1); } }
-            if constexpr (DMA && AIS == 5) {
-                // K(t+1) (issued one tile ago) must have landed before X(t); K(t+2), issued at the top of this segment, may stay in flight: NIW pieces
-                if (groupA) { if (t + 2 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory"); else dma_wait(); }
-            } else if constexpr (DMA && AIS != 0) { if (groupA) dma_wait(); }      // A's DMAs of the end of X(t-1): K(t+1) (and V(t), AIS 1), first read in X(t)
             UG_SEG(0);
             seg_barrier();
             UG_SEG(1);
             // X(t) = P.V(t) then K.Q^T(t+1): A in even segment 2t+2 | B in odd segment 2t+3 (publish). (Measured and dropped: group B
             // reading its first V^T fragments ahead of the barrier, inside its softmax segment: -4 %, -10 % with two k-steps.)
-            if constexpr (DMA && AIS == 5) {
-                constexpr int KN = (K3 + 1) % 3;
-                do_X(t, cur_c, t + 1 < ntiles, [](int) {}, std::integral_constant<int, (KN < 2 ? KN * 2 * TILE : 4 * TILE)>{});
-            } else if constexpr (DMA && AIS == 4) {
-                // split: group A issues the two K(t+2) pieces behind the first two P.V k-steps of its matrix segment, group B the V(t+1) tile at the start of its softmax segment
-                do_X(t, cur_c, t + 1 < ntiles, [&](int ks) __attribute__((always_inline)) { if (groupA && ks < 2) dma_piece(t + 2, ntiles, ks); }, std::integral_constant<int, -1>{});
-            } else if constexpr (DMA && AIS == 3) {
-                // group A: the four pieces of K(t+2) / V(t+1), one behind the MFMAs of each P.V k-step of ITS matrix segment (buffer form: two scalar
-                // instructions + the DMA each); a ragged or missing tile takes the whole-tile path behind step 0 (K) / step 2 (V)
-                do_X(t, cur_c, t + 1 < ntiles, [&](int ks) __attribute__((always_inline)) { if (groupA) dma_piece(t + 2, t + 1, ks); }, std::integral_constant<int, -1>{});
-            } else {
-                do_X(t, cur_c, t + 1 < ntiles, [](int) {}, std::integral_constant<int, -1>{});
-            }
-            if (!groupA) { if constexpr (DMA && AIS != 1 && AIS != 3) dma_wait(); else if constexpr (!DMA) publish(t + 2, t + 1); }
-            if constexpr (DMA && AIS == 1) { if (groupA) dma_fetch(t + 2, t + 1); }
-            if constexpr (DMA && AIS == 2) { if (groupA) dma_fetch(t + 2, ntiles); }
+            do_X(t, cur_c, t + 1 < ntiles);
+            if (!groupA) { if constexpr (DMA) dma_wait(); else publish(t + 2, t + 1); }
             UG_SEG(2);
             seg_barrier();
             UG_SEG(3);
         };
         UG_SEG0();
-        if constexpr (AIS == 5) {
-            for (int t = 0; t < ntiles; t += 6) {                  // buffer parity AND K ring slot as compile-time constants: period 6
-                tile(t, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                if (t + 1 < ntiles) tile(t + 1, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-                if (t + 2 < ntiles) tile(t + 2, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-                if (t + 3 < ntiles) tile(t + 3, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-                if (t + 4 < ntiles) tile(t + 4, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-                if (t + 5 < ntiles) tile(t + 5, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
-            }
-        } else {
-            for (int t = 0; t < ntiles; t += 2) {
-                tile(t, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                if (t + 1 < ntiles) tile(t + 1, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-            }
+        for (int t = 0; t < ntiles; t += 2) {
+            tile(t, std::integral_constant<int, 0>{});
+            if (t + 1 < ntiles) tile(t + 1, std::integral_constant<int, 1>{});
         }
         UG_ASTAMP(2);
         if (groupA) seg_barrier();                     // A's trailing (empty) segment pairs with B's last one
     }
 
     // ---- epilogue: O[q][d] = O^T / l ----
-    if constexpr (LSUM) l_run = lacc[0] + lacc2[0];
+    if constexpr (LSUM) l_run = lacc[0];
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     // training: log2 sum_k 2^(c s) of the row for the backward kernels (m_run is the row's reference point, shared by both lane halves)
 #ifndef UG_ATTN_STAMPS
@@ -2221,78 +2143,34 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
                q_batch_stride % 8 == 0 && k_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && o_batch_stride % 4 == 0 &&
                ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 8),
                UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd: strides must be multiples of 8 elements and bases 16-byte aligned");
+#define UG_ATTN_LAUNCH_KV(KVV, OCCV, LS, BUF, DHV, NWV, STG, ...)                                                                                  \
+    hipLaunchKernelGGL((flash_attn_kernel<DHV, NWV, STG, __VA_ARGS__, KVV, OCCV, LS, BUF>), dim3((unsigned)nwg), dim3(64 * NWV), 2 * 2 * KVV * 2 * DHV + (STG ? 32 * NWV * 2 * DHV : 0), (hipStream_t)stream, \
+                       (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v, \
+                       v_row_stride, v_batch_stride, (bf16_t*)o, o_row_stride, o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, c, lse_out, lse_ld)
 #ifndef UG_PROBE_BUILD
     // PRODUCT BUILD: one kernel per head width - the X|Y stagger with LDS-DMA staging and 16-byte stores; at head width 128 with s_setprio around the
-    // softmax segment (PRIO 3), at head width 64 the <= 128-register form so that two workgroups share a CU (KV 64, OCC 4). Every other form that was
-    // built and measured (lock-step loop, 4-wave workgroups, one wave per SIMD, register staging, 128-key tiles, priority variants) is compiled only
-    // into the probe library (python -m unigen_amd.build --probe; tools/probe/README.md), where UG_ATTN_* select it.
+    // softmax segment (PRIO 3), at head width 64 the <= 128-register form so that two workgroups share a CU (KV 64, OCC 4), its row sums on the matrix
+    // pipe (LSUM) and, where the strides allow it, its DMAs in buffer form (BUFD). Every other form that was built and measured (lock-step loop, 4-wave
+    // workgroups, one wave per SIMD, register staging, 128-key tiles, priority variants) is compiled only into the probe library (python -m
+    // unigen_amd.build --probe; tools/probe/README.md), where UG_ATTN_* select it; the round-6 variants are tools/probe/patches/attn_r06_variants.diff.
     constexpr int nw = 8;
     const int qrows = 32 * nw;
     const int nQ = (int)((Lq + qrows - 1) / qrows);
     const int64_t nwg = (int64_t)nQ * heads * batches;
     UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: grid too large");
     const float c = softmax_scale * 1.4426950408889634f;
-#define UG_ATTN_LAUNCH_KV(KVV, OCCV, DHV, NWV, STG, ...)                                                                                  \
-    hipLaunchKernelGGL((flash_attn_kernel<DHV, NWV, STG, __VA_ARGS__, KVV, OCCV>), dim3((unsigned)nwg), dim3(64 * NWV), 2 * 2 * KVV * 2 * DHV + (STG ? 32 * NWV * 2 * DHV : 0), (hipStream_t)stream, \
-                       (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v, \
-                       v_row_stride, v_batch_stride, (bf16_t*)o, o_row_stride, o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, c, lse_out, lse_ld)
     // (Round 4: the same stagger on v_mfma_f32_16x16x32_bf16 - flash_attn_m16_kernel, probe library, UG_ATTN_M16=1 - measured +3.5...+4.2 % in a
     // sustained interleaved A/B at 4608^2 / 4096 x 4608 / 8192 x 8704 and -5.6 % INSIDE the cfg2 forward (1113 vs 1177 TFLOP/s, same box, same
     // library, profiles/r04h_attn_m16_in_app.log): its advantage is the higher clock the chip reaches for that shape after ~10 ms of back-to-back
     // launches; a 0.9 ms launch between GEMMs never gets there, and at equal clock its 64 MFMA issues per tile cost the partner wave's softmax more
     // issue slots than 32 do. Not shipped.)
-    // UG_ATTN_LSUM_128 / UG_ATTN_LSUM_64 (build-time, 0 | 1 | 2): the row sums on the matrix pipe (template parameter LSUM: 1 = one accumulation chain, 2 = two), per head width
-#ifndef UG_ATTN_LSUM_128
-#define UG_ATTN_LSUM_128 0
-#endif
-#ifndef UG_ATTN_LSUM_64
-#define UG_ATTN_LSUM_64 1      // round 6: +1.5...+2.6 % on the cfg5 shapes by itself, +3.9...+6.3 % together with BUFD (profiles/r06_attn_variants.log); head width 128: -4 % (X is its longer segment)
-#endif
-#ifndef UG_ATTN_AIS_128
-#define UG_ATTN_AIS_128 0
-#endif
-#ifndef UG_ATTN_AIS_64
-#define UG_ATTN_AIS_64 0
-#endif
-#ifndef UG_ATTN_PRIO_64
-#define UG_ATTN_PRIO_64 0      // 1: s_setprio around the matrix stream, 3: around the softmax segment (the head-width-128 default)
-#endif
-#ifndef UG_ATTN_BUFD_64
-#define UG_ATTN_BUFD_64 1      // round 6: +2.3...+4.6 %, bit-identical (profiles/r06_attn_variants.log)
-#endif
-#define UG_ATTN_LAUNCH_LS(KVV, OCCV, LS, AISV, BUFV, DHV, NWV, STG, ...)                                                                                  \
-    hipLaunchKernelGGL((flash_attn_kernel<DHV, NWV, STG, __VA_ARGS__, KVV, OCCV, LS, AISV, BUFV>), dim3((unsigned)nwg), dim3(64 * NWV), 2 * 2 * KVV * 2 * DHV + (STG ? 32 * NWV * 2 * DHV : 0), (hipStream_t)stream, \
-                       (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v, \
-                       v_row_stride, v_batch_stride, (bf16_t*)o, o_row_stride, o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, c, lse_out, lse_ld)
-#ifndef UG_ATTN_NW16_64
-#define UG_ATTN_NW16_64 0
-#endif
+    // Round 6 (profiles/r06_attn_variants.log): BUFD +2.3...+4.6 %, bit-identical; LSUM +1.5...+2.6 % on the cfg5 shapes by itself, +3.9...+6.3 %
+    // together with BUFD; at head width 128 LSUM lost 4 % (X is its longer segment).
     // the buffer-form DMAs (BUFD) need one row stride for K and V, a multiple of 16 elements, and byte offsets of a (batch, head)'s keys below 2^31
-    const bool bufd_ok = UG_ATTN_BUFD_64 != 0 && k_row_stride == v_row_stride && k_row_stride % 16 == 0 && Lkv * k_row_stride * 2 < (1ll << 31);
-#ifndef UG_ATTN_BUFD_128
-#define UG_ATTN_BUFD_128 0
-#endif
-    const bool bufd128_ok = UG_ATTN_BUFD_128 != 0 && Lkv * k_row_stride * 2 < (1ll << 31) && Lkv * v_row_stride * 2 < (1ll << 31);
-    // (AIS 5 at head width 128 needs the launch's Q-image area as its third K slot: it is part of the stagger kernels' LDS request either way)
-    if (dh == 128 && bufd128_ok) UG_ATTN_LAUNCH_LS(64, 2, UG_ATTN_LSUM_128, UG_ATTN_AIS_128, true, 128, 8, true, 3, true, true);
-    else if (dh == 128) UG_ATTN_LAUNCH_LS(64, 2, UG_ATTN_LSUM_128, UG_ATTN_AIS_128, false, 128, 8, true, 3, true, true);
-#if UG_ATTN_NW16_64       // measured and not shipped (round 6): -0.8...+1.8 % - shorter segments, but every barrier now waits for the slowest of 16 waves
-    else if (bufd_ok) {
-        // ONE 16-wave workgroup per CU (512 query rows) instead of two 8-wave ones: the same four waves per SIMD, but one K / V stream for all of them
-        // (half the L2 -> LDS traffic and half the DMA instructions per query); 96 KiB of LDS (K | V double buffer 32 + the Q image 64)
-        const int nQ16 = (int)((Lq + 511) / 512);
-        const int64_t nwg16 = (int64_t)nQ16 * heads * batches;
-        static bool attr16 = false;
-        if (!attr16) { (void)hipFuncSetAttribute((const void*)flash_attn_kernel<64, 16, true, 0, true, true, 64, 4, UG_ATTN_LSUM_64, (UG_ATTN_AIS_64 == 3 ? 0 : UG_ATTN_AIS_64), true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * 2 * 64 + 32 * 16 * 2 * 64); attr16 = true; }
-        hipLaunchKernelGGL((flash_attn_kernel<64, 16, true, 0, true, true, 64, 4, UG_ATTN_LSUM_64, (UG_ATTN_AIS_64 == 3 ? 0 : UG_ATTN_AIS_64), true>), dim3((unsigned)nwg16), dim3(1024), 2 * 2 * 64 * 2 * 64 + 32 * 16 * 2 * 64, (hipStream_t)stream,
-                           (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v,
-                           v_row_stride, v_batch_stride, (bf16_t*)o, o_row_stride, o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ16, c, lse_out, lse_ld);
-    }
-#endif
-    else if (bufd_ok) UG_ATTN_LAUNCH_LS(64, 4, UG_ATTN_LSUM_64, UG_ATTN_AIS_64, true, 64, 8, true, UG_ATTN_PRIO_64, true, true);
-    else UG_ATTN_LAUNCH_LS(64, 4, UG_ATTN_LSUM_64, (UG_ATTN_AIS_64 == 3 ? 1 : UG_ATTN_AIS_64 == 4 ? 2 : UG_ATTN_AIS_64), false, 64, 8, true, 0, true, true);
-#undef UG_ATTN_LAUNCH_LS
-#undef UG_ATTN_LAUNCH_KV
+    const bool bufd_ok = k_row_stride == v_row_stride && k_row_stride % 16 == 0 && Lkv * k_row_stride * 2 < (1ll << 31);
+    if (dh == 128) UG_ATTN_LAUNCH_KV(64, 2, false, false, 128, 8, true, 3, true, true);
+    else if (bufd_ok) UG_ATTN_LAUNCH_KV(64, 4, true, true, 64, 8, true, 0, true, true);
+    else UG_ATTN_LAUNCH_KV(64, 4, true, false, 64, 8, true, 0, true, true);
 #else
     static int nw = -1;
     if (nw < 0) { const char* e = getenv("UG_ATTN_WAVES"); nw = (e && atoi(e) == 4) ? 4 : 8; }   // 8 measured faster (841 vs 800 TFLOP/s at L = 4608)
@@ -2301,10 +2179,6 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
     const int64_t nwg = (int64_t)nQ * heads * batches;
     UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: grid too large");
     const float c = softmax_scale * 1.4426950408889634f;
-#define UG_ATTN_LAUNCH_KV(KVV, OCCV, DHV, NWV, STG, ...)                                                                                  \
-    hipLaunchKernelGGL((flash_attn_kernel<DHV, NWV, STG, __VA_ARGS__, KVV, OCCV>), dim3((unsigned)nwg), dim3(64 * NWV), 2 * 2 * KVV * 2 * DHV + (STG ? 32 * NWV * 2 * DHV : 0), (hipStream_t)stream, \
-                       (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v, \
-                       v_row_stride, v_batch_stride, (bf16_t*)o, o_row_stride, o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, c, lse_out, lse_ld)
 #define UG_ATTN_LAUNCH(DHV, NWV, STG, ...)                                                                                           \
     hipLaunchKernelGGL((flash_attn_kernel<DHV, NWV, STG, ##__VA_ARGS__>), dim3((unsigned)nwg), dim3(64 * NWV), 2 * 2 * KVB * 2 * DHV + (STG ? 32 * NWV * 2 * DHV : 0), (hipStream_t)stream, \
                        (const bf16_t*)q, q_row_stride, q_batch_stride, (const bf16_t*)k, k_row_stride, k_batch_stride, (const bf16_t*)v, \
@@ -2377,16 +2251,16 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
     else if (nw == 8 && stg && dma && kv64 == 128) {
         static bool attr = false;
         if (!attr) { (void)hipFuncSetAttribute((const void*)flash_attn_kernel<64, 8, true, 0, true, true, 128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 128 * 2 * 64 + 32 * 8 * 2 * 64); attr = true; }
-        UG_ATTN_LAUNCH_KV(128, 2, 64, 8, true, 0, true, true);
+        UG_ATTN_LAUNCH_KV(128, 2, false, false, 64, 8, true, 0, true, true);
     }
     else if (nw == 8 && stg && dma && kv64 == 464) {        // UG_ATTN_KV64=464: 64-key tiles, <= 128 registers, two workgroups per CU
-        UG_ATTN_LAUNCH_KV(64, 4, 64, 8, true, 0, true, true);
+        UG_ATTN_LAUNCH_KV(64, 4, false, false, 64, 8, true, 0, true, true);
     }
     else           { if (nw == 4) UG_ATTN_LAUNCH(64, 4, false); else if (stg) UG_ATTN_STG(64); else UG_ATTN_LAUNCH(64, 8, false); }
-#undef UG_ATTN_LAUNCH_KV
 #undef UG_ATTN_STG
 #undef UG_ATTN_LAUNCH
 #endif   // UG_PROBE_BUILD
+#undef UG_ATTN_LAUNCH_KV
     UG_CHECK_LAUNCH("ug_flash_attn_fwd");
     return UG_OK;
 }

@@ -6,7 +6,7 @@
 // FluxTransformerBlock / FluxSingleTransformerBlock invoked at src/UniGenTransformer.py:1129,1151,1097,1102,1104 and
 // the expert linears :957-959) together with the elementwise ops the reference runs as separate kernels after it.
 //
-// Kernel: 128x128x64 tile, 256 threads = 4 waves (2x2), each wave a 64x64 sub-tile as 4x4 v_mfma_f32_16x16x32_bf16
+// Kernel: 128x128x64 tile, 512 threads = 8 waves (4x2), each wave a 32x64 sub-tile as 2x4 v_mfma_f32_16x16x32_bf16
 // accumulators. Operands are staged HBM -> LDS with global_load_lds_dwordx4 (no VGPR round trip) into two LDS
 // buffers; the LDS image is lane-linear, so the bank-conflict XOR swizzle is applied to the per-lane SOURCE address
 // and to the ds_read address (cdna guide rule 21). The MFMA is issued with W as the "A" operand so each lane ends
@@ -17,12 +17,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef UG_GEMM_SLAB_SC
-#define UG_GEMM_SLAB_SC 1
-#endif
-#ifndef UG_GEMM128_W8
-#define UG_GEMM128_W8 2      // round 6: 8-wave workgroups everywhere the 128^2 kernel runs: +3...+7 % on its launches, bit-identical (profiles/r06aa_gemm128_w8_ab.log)
-#endif
 #ifndef UG_GEMM_SPLITK_MIN_KT_DEFAULT
 #define UG_GEMM_SPLITK_MIN_KT_DEFAULT 96
 #endif
@@ -33,14 +27,15 @@ constexpr int TILE_BYTES = BM * BK * 2;        // 16 KiB per operand tile
 constexpr int BUF_BYTES = 2 * TILE_BYTES;      // A + W
 constexpr int LDS_BYTES = 2 * BUF_BYTES;       // double buffered: 64 KiB -> 2 workgroups / CU
 
-// NWV (round 6): waves per workgroup. 4 = rounds 1-5: a wave owns 64 x 64 of the tile and issues 8 LDS-DMAs per 32 MFMAs - alone on a CU (launches of at most
-// one tile per CU: the batch-1 text / 512^2 projections) that issue sequence, not its latency, paces the K loop (0.94 us per K-tile = 28 % of the CU's MFMA
-// rate; a four-stage prefetch changed nothing, profiles/r06q_gemm128_four_stage_ab.log). 8 = a wave owns 32 x 64 (16 MFMAs, 4 DMAs, 12 fragment reads per
-// K-tile): two waves per SIMD from ONE workgroup cover each other's issue stalls. Same MFMA shape, same K order per output element: bit-identical.
-template <int EPI, int NWV = 4>
-__global__ __launch_bounds__(64 * NWV, 2) void gemm128_kernel(const ug_gemm_desc p) {
-    constexpr int MI = 16 / NWV;                       // 16-row m-subtiles per wave: 4 (64 rows) or 2 (32 rows)
-    constexpr int SR = 16 / NWV;                       // 8-row staging groups per wave and operand: 4 (32 rows) or 2 (16 rows)
+// Round 6: 8 waves, each owning 32 x 64 of the tile (16 MFMAs, 4 DMAs, 12 fragment reads per K-tile), so that two waves per SIMD from ONE workgroup cover
+// each other's issue stalls. With 4 waves (rounds 1-5: 64 x 64 per wave, 8 LDS-DMAs per 32 MFMAs) alone on a CU - launches of at most one tile per CU, the
+// batch-1 text / 512^2 projections - that issue sequence, not its latency, paced the K loop (0.94 us per K-tile = 28 % of the CU's MFMA rate; a four-stage
+// prefetch changed nothing, profiles/r06q_gemm128_four_stage_ab.log). Same MFMA shape, same K order per output element: bit-identical; +3...+7 % on the
+// kernel's launches (profiles/r06aa_gemm128_w8_ab.log; the 4-wave form is tools/probe/patches/gemm_r06_variants.diff).
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void gemm128_kernel(const ug_gemm_desc p) {
+    constexpr int MI = 2;                              // 16-row m-subtiles per wave (32 rows)
+    constexpr int SR = 2;                              // 8-row staging groups per wave and operand (16 rows)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -195,8 +190,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
     //
     // TAIL: tiles [0, full_tiles) fill whole rounds of the grid. When the remaining R tiles would occupy <= half the CUs they
     // are each cut into `nslices` K-slices that run concurrently in the last round: a slice stores its fp32 accumulators as a
-    // slab, publishes it (agent-scope release + ticket), and the LAST arriver of a tile re-reads every slab in slice order
-    // (agent-scope acquire; fixed order -> bitwise reproducible) and runs the epilogue. Nobody waits on anybody: no spin.
+    // slab (system-scope stores), takes a ticket, and the LAST arriver of a tile re-reads every slab in slice order (system-scope
+    // loads; fixed order -> bitwise reproducible) and runs the epilogue. Nobody waits on anybody: no spin.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -649,11 +644,14 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
         if (rem >= 0) {
             // ---- split-K tail: slab out, ticket, last arriver reduces (cdna guide section 5, "in-launch split-K reduction") ----
             float* my = slabs + ((size_t)rem * nslices + slice) * 65536;
-            // UG_GEMM_SLAB_SC (round 6): the slabs travel at SYSTEM scope - `sc0 sc1` stores write through this XCD's L2, `sc0 sc1` loads never hit a
-            // stale line of the reader's - instead of plain accesses bracketed by agent-scope fences. On this chip an agent release is `buffer_wbl2 sc1`
-            // (write back EVERY dirty line of the XCD's L2: by every slice workgroup) and an acquire `buffer_inv sc1` (drop the L2's contents: under the
-            // other workgroups' operand panels); with them the slab round trip measured ~46 us + 6 us per slice (profiles/r06j_shape_rates_cfg1_after_dispatch.log).
-#if UG_GEMM_SLAB_SC
+            // Round 6: the slabs travel at SYSTEM scope - `sc0 sc1` stores write through this XCD's L2, `sc0 sc1` loads never hit a stale line of the
+            // reader's - instead of plain accesses bracketed by agent-scope fences. On this chip an agent release is `buffer_wbl2 sc1` (write back EVERY
+            // dirty line of the XCD's L2: by every slice workgroup) and an acquire `buffer_inv sc1` (drop the L2's contents: under the other workgroups'
+            // operand panels); with them the slab round trip measured ~46 us + 6 us per slice (profiles/r06j_shape_rates_cfg1_after_dispatch.log; the
+            // fenced form is tools/probe/patches/gemm_r06_variants.diff). hipcc pads nothing inside an asm statement: a store of more than 8 bytes needs
+            // two wait states before a VALU may overwrite its data VGPRs (gfx940+), and without the `s_nop 1` the compiler reused the data registers of
+            // the second-to-last slab store as an address one instruction later - a slab element could then hold address bits, and the split-K
+            // launches were not bitwise repeatable under load.
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -662,39 +660,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
                     for (int a = 0; a < 4; ++a)
 #pragma unroll
                         for (int b = 0; b < 2; ++b)
-                            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(my + ((((i * 2 + j) * 4 + a) * 2 + b) * 512 + tid_e) * 4), "v"(acc[i][j][a][b]) : "memory");
-#else
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-                            *(f32x4*)(my + ((((i * 2 + j) * 4 + a) * 2 + b) * 512 + tid_e) * 4) = acc[i][j][a][b];
-#endif
+                            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(my + ((((i * 2 + j) * 4 + a) * 2 + b) * 512 + tid_e) * 4), "v"(acc[i][j][a][b]) : "memory");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave: its slab part has reached memory
             __syncthreads();
             unsigned* flag = (unsigned*)(smem + LDS256_BYTES);
-            if (tid_e == 0) {
-#if !UG_GEMM_SLAB_SC
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // keep: hipcc may drop the fence's own wait
-#endif
-                *flag = __hip_atomic_fetch_add(tickets + rem, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid_e == 0) *flag = __hip_atomic_fetch_add(tickets + rem, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             const bool last = *flag == (unsigned)(nslices - 1);
             __syncthreads();                                              // flag is re-used by a later item
             if (!last) continue;
-            if (tid_e == 0) {
-#if !UG_GEMM_SLAB_SC
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                __hip_atomic_store(tickets + rem, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all arrivals are in: ready for the next launch
-            }
+            if (tid_e == 0) __hip_atomic_store(tickets + rem, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all arrivals are in: ready for the next launch
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -706,7 +681,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
                         for (int b = 0; b < 2; ++b) acc[i][j][a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
             for (int sl = 0; sl < nslices; ++sl) {
                 const float* sp = slabs + ((size_t)rem * nslices + sl) * 65536;
-#if UG_GEMM_SLAB_SC
                 // system-scope loads, 8 in flight per lane (the accumulators leave no room for a whole slab's 32), same slice and element order as before
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -724,17 +698,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
 #pragma unroll
                             for (int b = 0; b < 2; ++b) acc[i][j][a][b] += t[a][b];
                     }
-#else
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b)
-                                acc[i][j][a][b] += *(const f32x4*)(sp + ((((i * 2 + j) * 4 + a) * 2 + b) * 512 + tid_e) * 4);
-#endif
             }
         }
         if constexpr (EPI == UG_EPI_QKV_ROPE) {
@@ -1020,6 +983,33 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
 // UG_GEMM_FORCE_TILE=128|256 pins the kernel choice (tests / A-B timing); default: 256^2 tiles when they fill the chip.
 int forced_tile() { return ug_env_int("UG_GEMM_FORCE_TILE", 0); }
 
+// CUs of the current device (256 on MI355X): the grid of the persistent 256^2 kernel
+int chip_cus() {
+    static int ncu = 0;
+    if (ncu == 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
+        if (ncu <= 0) ncu = 256;
+    }
+    return ncu;
+}
+
+// Split-K tail of a 256^2 launch of `tiles` tiles on `ncu` CUs (see the kernel header): the remainder tiles, padded to a multiple of 8 (rem8), are
+// each cut into `nsl` K-slices when they fill at most half the CUs, the K loop is long and the caller's workspace holds the slabs; nsl = 1: no split.
+// Measured (MI355X, with the fenced slabs of rounds 1-5): the slab round trip cost ~35 us, so the split only pays when a tile's K loop is long
+// (K = 15360 single-block proj_out: +3.5 %; K = 3072 shapes: -2...-3 %) -> require >= 96 K-tiles.
+struct SplitK { int rem8, nsl; };
+SplitK splitk_plan(const ug_gemm_desc& d, int64_t tiles, int ncu) {
+    const int rem = (int)(tiles % ncu), nkt = (int)(d.K / BK);
+    if (!UG_TUNE("UG_GEMM_SPLITK_TAIL", 1) || d.lora_r > 0 || rem == 0 || rem * 2 > ncu || !d.workspace || !ug_aligned(d.workspace, 16) ||
+        nkt < UG_TUNE("UG_GEMM_SPLITK_MIN_KT", UG_GEMM_SPLITK_MIN_KT_DEFAULT))
+        return {0, 1};
+    const int rem8 = (rem + 7) / 8 * 8;
+    int cand = ncu / rem8; if (cand > 8) cand = 8; if (cand > nkt / 4) cand = nkt / 4;
+    if (cand < 2 || (size_t)d.workspace_bytes < 4096 + (size_t)rem8 * cand * 65536 * sizeof(float)) return {0, 1};
+    return {rem8, cand};
+}
+
 template <int EPI>
 int launch(const ug_gemm_desc& d, hipStream_t s) {
     const int groups = d.groups > 0 ? d.groups : 1;
@@ -1036,19 +1026,15 @@ int launch(const ug_gemm_desc& d, hipStream_t s) {
     // 512^2 forms of ff.net.2 (K = 12288) and of the single blocks' proj_out (K = 15360): 24-72 tiles of 256^2 - lost the fill comparison above to the
     // 128^2 kernel, which then ran one round of whole K loops (512 x 3072 x 12288: 187 us = 207 TFLOP/s, profiles/r06i_shape_rates_cfg1.log) although
     // the 256^2 kernel would cut exactly these launches into K-slices that fill the chip (its split-K tail). Priced in microseconds with the measured
-    // unit costs - a 256^2 K-tile 1.53 us, a 128^2 K-tile 0.97 us with one workgroup on the CU / 1.27 us with two, the slab round trip 22 + 2.5 us per slice (46 + 6 before the slabs went to system scope, below):
-    if (!big && !lora && EPI != UG_EPI_F32 && d.M >= 192 && d.N >= 192 && d.workspace && ug_aligned(d.workspace, 16) && UG_TUNE("UG_GEMM_SPLITK_TAIL", 1) &&
-        UG_TUNE("UG_GEMM_SPLITK_SMALLM", 1)) {
-        const int G = 256, nkt = (int)(d.K / BK);
-        const int rem = (int)(t256 % G);
-        if (t256 < G && rem * 2 <= G && nkt >= UG_TUNE("UG_GEMM_SPLITK_MIN_KT", UG_GEMM_SPLITK_MIN_KT_DEFAULT)) {
-            const int rem8 = (rem + 7) / 8 * 8;
-            int cand = G / rem8; if (cand > 8) cand = 8; if (cand > nkt / 4) cand = nkt / 4;
-            if (cand >= 2 && (size_t)d.workspace_bytes >= 4096 + (size_t)rem8 * cand * 65536 * sizeof(float)) {
-                const double t_split = 1.53 * nkt / cand + (UG_GEMM_SLAB_SC ? 22.0 + 2.5 * cand : 46.0 + 6.0 * cand);     // slab round trip as measured with / without the system-scope slabs
-                const double t_128 = (double)((t128 + 511) / 512) * nkt * (t128 <= G ? 0.97 : 1.27);
-                if (t_split < 0.9 * t_128) big = true;
-            }
+    // unit costs - a 256^2 K-tile 1.53 us, a 128^2 K-tile 0.97 us with one workgroup on the CU / 1.27 us with two, the slab round trip 22 + 2.5 us per slice:
+    const int ncu = chip_cus();
+    if (!big && !lora && EPI != UG_EPI_F32 && d.M >= 192 && d.N >= 192 && t256 < ncu && UG_TUNE("UG_GEMM_SPLITK_SMALLM", 1)) {
+        const SplitK sk = splitk_plan(d, t256, ncu);
+        if (sk.nsl > 1) {
+            const int nkt = (int)(d.K / BK);
+            const double t_split = 1.53 * nkt / sk.nsl + 22.0 + 2.5 * sk.nsl;     // (46 + 6 us per slice with the fenced slabs before round 6)
+            const double t_128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * nkt * (t128 <= ncu ? 0.97 : 1.27);
+            if (t_split < 0.9 * t_128) big = true;
         }
     }
     const int f = forced_tile();
@@ -1065,19 +1051,12 @@ int launch(const ug_gemm_desc& d, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)gemm128_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)gemm128_kernel<EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256_BYTES + 16 + UG_STAMP_LDS);
         if (EPI != UG_EPI_F32)
             (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, EPI != UG_EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256_BYTES + 16 + UG_STAMP_LDS);
         attr_set = true;
     }
     if (big) {
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0; hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-            if (ncu <= 0) ncu = 256;
-        }
         const int total = (int)t256;
         dim3 grid((unsigned)(total < ncu ? total : ncu), 1, 1);
         // 16-byte epilogue accesses need 8-column granularity everywhere the epilogue touches
@@ -1099,21 +1078,12 @@ int launch(const ug_gemm_desc& d, hipStream_t s) {
         // 8 (rounds 1-2) 1.991-2.004 / 1322-1330, 6: 2.006, 3 / 5 / 2: 2.002-2.004, 16: 1.965, 32: 1.905 (profiles/r02c_group_m.log)
         const int gm = ((UG_TUNE("UG_GEMM_GROUP_M", 4) & 0xff) << 8) | ((UG_TUNE("UG_GEMM_WALK", 0) & 3) << 16);
         float* slabs = nullptr; unsigned* tickets = nullptr;
-        const int G = ncu, rem = total % G;            // total < ncu: every tile is a remainder tile
-        const int nkt = (int)(d.K / BK);
-        const int split_on = UG_TUNE("UG_GEMM_SPLITK_TAIL", 1);
-        // Measured (MI355X): the slab round trip + fences cost ~35 us, so the split only pays when a tile's K loop is long
-        // (K = 15360 single-block proj_out: +3.5 %; K = 3072 shapes: -2...-3 %) -> require >= 96 K-tiles.
-        if (split_on && !lora && rem > 0 && rem * 2 <= G && d.workspace && nkt >= UG_TUNE("UG_GEMM_SPLITK_MIN_KT", UG_GEMM_SPLITK_MIN_KT_DEFAULT)) {
-            const int rem8 = (rem + 7) / 8 * 8;
-            int cand = G / rem8; if (cand > 8) cand = 8; if (cand > nkt / 4) cand = nkt / 4;
-            const size_t need = 4096 + (size_t)rem8 * cand * 65536 * sizeof(float);
-            if (cand >= 2 && (size_t)d.workspace_bytes >= need && ug_aligned(d.workspace, 16)) {
-                nsl = cand; full = total - rem;
-                if (total < ncu) grid.x = (unsigned)(rem8 * cand);      // one workgroup per K-slice (incl. the 8-alignment padding)
-                tickets = (unsigned*)d.workspace;
-                slabs = (float*)((char*)d.workspace + 4096);
-            }
+        const SplitK sk = splitk_plan(d, total, ncu);
+        if (sk.nsl > 1) {
+            nsl = sk.nsl; full = total - total % ncu;
+            if (total < ncu) grid.x = (unsigned)(sk.rem8 * sk.nsl);     // one workgroup per K-slice (incl. the 8-alignment padding)
+            tickets = (unsigned*)d.workspace;
+            slabs = (float*)((char*)d.workspace + 4096);
         }
         if (lora) {     // (EPI_F32 never gets here with LoRA; its second instantiation is the plain kernel again)
             hipLaunchKernelGGL((gemm256_kernel<EPI, EPI != UG_EPI_F32>), grid, dim3(512), LDS256_BYTES + 16 + UG_STAMP_LDS, s, d, (int)(t256 / groups), total, wide16 | gm, full, nsl, slabs, tickets, UgConvGeom{});
@@ -1126,11 +1096,7 @@ int launch(const ug_gemm_desc& d, hipStream_t s) {
     } else {
         const int nM = (int)((d.M + BM - 1) / BM), nN = (int)((d.N + BN - 1) / BN);
         dim3 grid((unsigned)(nM * nN), 1, (unsigned)groups);
-        // UG_GEMM128_W8 (build-time): 0 = the 4-wave workgroup everywhere, 1 = the 8-wave form for launches of at most one tile per CU, 2 = everywhere
-        if (UG_GEMM128_W8 == 2 || (UG_GEMM128_W8 == 1 && (int64_t)nM * nN * groups <= 256))
-            hipLaunchKernelGGL((gemm128_kernel<EPI, 8>), grid, dim3(512), LDS_BYTES, s, d);
-        else
-            hipLaunchKernelGGL(gemm128_kernel<EPI>, grid, dim3(256), LDS_BYTES, s, d);
+        hipLaunchKernelGGL(gemm128_kernel<EPI>, grid, dim3(512), LDS_BYTES, s, d);
     }
     UG_CHECK_LAUNCH("ug_gemm_bf16");
     return UG_OK;
@@ -1156,12 +1122,7 @@ int launch_qkrope(const ug_gemm_desc& d, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)gemm256_kernel<UG_EPI_QKV_ROPE, false, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_set = true;
     }
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
+    const int ncu = chip_cus();
     const int total = (int)((d.M / 256) * (d.N / 256));
     {   // this epilogue only exists in the 256^2 kernel: its buffer-form A offsets need a monotonic row map and < 2^31 bytes per tile (see launch())
         const int64_t a_jumps = d.a_rpb > 0 ? (255 + d.a_rpb - 1) / d.a_rpb : 0;
@@ -1198,12 +1159,7 @@ int launch_qkrope(const ug_gemm_desc& d, hipStream_t s) {
 // ug_conv2d_nhwc on the 256^2 kernel (see UgConvGeom): whole 256^2 tiles, bias or residual epilogue, no split-K tail (no workspace at this boundary).
 int ug_gemm_launch_conv256(const ug_gemm_desc& d, const UgConvGeom& cv, hipStream_t s) {
     if (d.M % 256 || d.N % 256 || d.K % BK || cv.ktp < 2 || (cv.ktp & (cv.ktp - 1)) || d.K / BK < 3) return UG_ERR_UNSUPPORTED;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
+    const int ncu = chip_cus();
     constexpr int LDS = LDS256_BYTES + 16 + UG_STAMP_LDS;
     static bool attr_set = false;
     if (!attr_set) {
