@@ -445,6 +445,60 @@ int ug_attn_dscore_f32(const void* P, int64_t ld_p, const float* dP, int64_t ld_
                        int64_t cols, float scale, ug_stream_t stream);
 int ug_rowdot_f32(const void* a, int64_t lda, const void* b, int64_t ldb, float* out, int64_t rows, int64_t groups, int64_t cols, ug_stream_t stream);
 
+/* ---- optimizer step of the training loop (csrc/optim.hip): accelerator.clip_grad_norm_(transformer.parameters(), max_grad_norm)
+ * (train.py:658) and torch.optim.AdamW.step() (train.py:660) over every trainable tensor in one launch each. The work list is a DEVICE table
+ * of ug_optim_tensor descriptors and a DEVICE list of int32 (tensor index, chunk index) pairs, chunk c of tensor t covering elements
+ * [c * UG_OPTIM_CHUNK, min((c + 1) * UG_OPTIM_CHUNK, numel)); every element of every tensor in exactly one pair. Any element alignment is
+ * accepted (16-byte vector accesses on the aligned body of a chunk, scalar head and tail). No atomics: results are bitwise reproducible. ---- */
+enum { UG_DT_BF16 = 0, UG_DT_F32 = 1 };
+#define UG_OPTIM_CHUNK 65536
+#define UG_ADAMW_MAX_GROUPS 32
+
+typedef struct ug_optim_tensor {
+    void* param;           /* bf16 or fp32 (param_dtype); unused by ug_grad_sumsq / ug_grad_scale */
+    void* grad;            /* bf16 or fp32 (grad_dtype); written only by ug_grad_scale */
+    float* master;         /* fp32 master weights of a bf16 param; NULL for an fp32 param (updated in place) */
+    float* exp_avg;        /* fp32 first / second moments */
+    float* exp_avg_sq;
+    int64_t numel;
+    int32_t param_dtype;   /* UG_DT_* */
+    int32_t grad_dtype;
+    int32_t group;         /* index into the ug_adamw_group array of ug_adamw_step */
+    int32_t _pad;
+} ug_optim_tensor;
+
+/* hyperparameters of one param group at this step, each computed by the caller in fp64 (as torch's Python does) and rounded to fp32 once */
+typedef struct ug_adamw_group {
+    float decay;             /* 1 - lr * weight_decay */
+    float lerp_w;            /* 1 - beta1 */
+    float beta2;
+    float one_minus_beta2;   /* 1 - beta2 */
+    float eps;
+    float step_size;         /* lr / (1 - beta1^step) */
+    float inv_bc2_sqrt;      /* 1 / fp32(sqrt(1 - beta2^step)) in fp32: torch divides a tensor by a Python scalar as a product with its reciprocal */
+    float _pad;
+} ug_adamw_group;
+
+/* host-side check of a HOST copy of the table before it is uploaded: numel >= 0, known dtypes, non-null grads; with n_groups > 0 (an AdamW table)
+ * also group < n_groups, non-null param / moments, a master exactly for bf16 params. n_groups == 0: a gradient-only table. */
+int ug_optim_check_table(const ug_optim_tensor* table_host, int32_t n_tensors, int32_t n_groups);
+/* bytes of the fp64 per-chunk partials of ug_grad_sumsq */
+int64_t ug_grad_sumsq_workspace_bytes(int64_t n_chunks);
+/* total_norm = ||all grads||_2 (fp32 per lane and wave, fp64 across the chunk and in the fixed-order sum of the chunks, a second one-block launch);
+ * norm_coef[0] = total_norm, norm_coef[1] = min(1, max_norm / (total_norm + 1e-6)) with torch's arithmetic (torch/nn/utils/clip_grad.py:
+ * inf -> 0, NaN propagates). Both fp32 in device memory. */
+int ug_grad_sumsq(const ug_optim_tensor* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, float max_norm, float* norm_coef,
+                  void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+/* grad = grad * (*coef) in place, rounded once to the grad's dtype (torch._foreach_mul_ of clip_grad_norm_ with the 0-dim fp32 clip_coef) */
+int ug_grad_scale(const ug_optim_tensor* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, const float* coef, ug_stream_t stream);
+/* torch.optim.AdamW (decoupled weight decay; torch.optim.adam._single_tensor_adam's order of operations) on every chunk, fp32 arithmetic:
+ *   g = grad * (coef ? *coef : 1); p = p * decay; m = lerp(m, g, lerp_w); v = v * beta2 + one_minus_beta2 * g * g;
+ *   p = p - step_size * (m / (sqrt(v) * inv_bc2_sqrt + eps))      (IEEE sqrt and division)
+ * p is the master (bf16 param: the param is then written as RNE(p)) or the fp32 param itself. Grads are only read. groups_host: n_groups <=
+ * UG_ADAMW_MAX_GROUPS entries, passed by value with the launch. */
+int ug_adamw_step(const ug_optim_tensor* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, const ug_adamw_group* groups_host,
+                  int32_t n_groups, const float* coef, ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

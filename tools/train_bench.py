@@ -1,6 +1,7 @@
 """One training step (forward + backward of the control modules, reference train.py:622-662) at the FLUX-schnell geometry + canny control,
 random weights and inputs: seconds per step, samples/s, peak memory. Not the headline metric (BASELINE.json measures inference); the
-SURVEY 8(f) rank-4 row. usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38]"""
+SURVEY 8(f) rank-4 row. --optim adds the optimizer step of train.py:658-660 (unigen_amd.optim.AdamW(max_grad_norm=1.0): clipping fused, fp32 masters)
+to each timed step. usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +17,7 @@ ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--sd3", action="store_true", help="UniGenSD3 (SD3.5-medium geometry, depth control, transformer-block experts) instead of UniGenFlux")
 ap.add_argument("--no-gradnorm", action="store_true", help="skip the per-step gradient-norm diagnostic (hundreds of small torch kernels: keep it out of rocprofv3 kernel statistics)")
 ap.add_argument("--shapes", action="store_true", help="per-shape table of the last step's GEMM / attention launches (grouped by FLOPs per launch)")
+ap.add_argument("--optim", action="store_true", help="time unigen_amd.optim.AdamW(lr=1e-4, weight_decay=1e-2, max_grad_norm=1.0).step() after each backward")
 a = ap.parse_args()
 dev, BF = torch.device("cuda:0"), torch.bfloat16
 B = a.batch
@@ -59,7 +61,11 @@ else:
 n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
 n_all = sum(p.numel() for p in model.parameters())
 from unigen_amd import ops
-times = []
+opt = None
+if a.optim:
+    from unigen_amd.optim import AdamW
+    opt = AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0)
+times, opt_times = [], []
 timer = None
 for step in range(a.steps + 1):
     if step == a.steps:            # HIP events around every GEMM / attention launch of the last step (not part of the timed minimum)
@@ -76,12 +82,21 @@ for step in range(a.steps + 1):
     torch.cuda.synchronize(); t2 = time.time()
     if step and timer is None:
         times.append((t1 - t0, t2 - t1))
+    if opt is not None:
+        opt.step()
+        torch.cuda.synchronize(); t3 = time.time()
+        if step and timer is None:
+            opt_times.append(t3 - t2)
     gn = float("nan") if a.no_gradnorm else float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in model.parameters() if p.grad is not None)))
     print(f"step {step}: loss {float(loss):.5f} grad-norm {gn:.4e} forward {t1 - t0:.3f}s backward {t2 - t1:.3f}s", flush=True)
 ops.set_timer(None)
 rates = {k: dict(launches=v["launches"], ms=round(v["ms"], 1), tflops=round(v["flops"] / v["ms"] / 1e9, 1)) for k, v in timer.summary().items()}
 fw, bw = min(x[0] for x in times), min(x[1] for x in times)
-print("TRAIN_BENCH", json.dumps(dict(model="UniGenSD3" if a.sd3 else "UniGenFlux", batch=B, size=a.size, layers=[model.config.num_layers, getattr(model.config, "num_single_layers", 0)], checkpointing=bool(a.ckpt),
+extra = {}
+if opt is not None:
+    op = min(opt_times)
+    extra = dict(optimizer_s=round(op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5))
+print("TRAIN_BENCH", json.dumps(dict(**extra, model="UniGenSD3" if a.sd3 else "UniGenFlux", batch=B, size=a.size, layers=[model.config.num_layers, getattr(model.config, "num_single_layers", 0)], checkpointing=bool(a.ckpt),
       params_total=n_all, params_trainable=n_train, forward_s=round(fw, 3), backward_s=round(bw, 3), samples_per_s=round(B / (fw + bw), 3),
       peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1), kernel_rates=rates)))
 

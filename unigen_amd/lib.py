@@ -50,6 +50,24 @@ class ConvDesc(C.Structure):
                 ("Cout", i64), ("KH", i32), ("KW", i32), ("stride", i32), ("pad_t", i32), ("pad_l", i32), ("up", i32), ("zero_page", vp), ("zero_page_bytes", i64)]
 
 
+UG_DT_BF16, UG_DT_F32 = 0, 1
+UG_OPTIM_CHUNK, UG_ADAMW_MAX_GROUPS = 65536, 32
+
+
+class OptimTensor(C.Structure):
+    """Mirror of struct ug_optim_tensor (include/unigen_hip.h)."""
+
+    _fields_ = [("param", vp), ("grad", vp), ("master", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", i64),
+                ("param_dtype", i32), ("grad_dtype", i32), ("group", i32), ("_pad", i32)]
+
+
+class AdamwGroup(C.Structure):
+    """Mirror of struct ug_adamw_group (include/unigen_hip.h)."""
+
+    _fields_ = [("decay", f32), ("lerp_w", f32), ("beta2", f32), ("one_minus_beta2", f32), ("eps", f32), ("step_size", f32), ("inv_bc2_sqrt", f32),
+                ("_pad", f32)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/unigen_hip.h
 SIGNATURES = {
     "ug_version": (i32, []),
@@ -107,6 +125,14 @@ SIGNATURES.update({
     "ug_flash_attn_bwd_workspace_bytes": (i64, [i64, i32, i64]),
     "ug_flash_attn_bwd": (i32, [vp, i64, i64] * 8 + [i64, i32, i64, i64, i32, f32, vp, vp, i64, vp]),
     "ug_flash_attn_fwd_lse": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp, i64, vp]),
+})
+# optimizer step (csrc/optim.hip); the table / chunk list are device pointers, ug_optim_check_table and ug_adamw_step's groups read host memory
+SIGNATURES.update({
+    "ug_optim_check_table": (i32, [vp, i32, i32]),
+    "ug_grad_sumsq_workspace_bytes": (i64, [i64]),
+    "ug_grad_sumsq": (i32, [vp, i32, vp, i64, f32, vp, vp, i64, vp]),
+    "ug_grad_scale": (i32, [vp, i32, vp, i64, vp, vp]),
+    "ug_adamw_step": (i32, [vp, i32, vp, i64, vp, i32, vp, vp]),
 })
 _F32_TWINS = {"ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",
               "ug_adaln_modulate_bwd_f32": "ug_adaln_modulate_bwd", "ug_qk_rmsnorm_rope_bwd_f32": "ug_qk_rmsnorm_rope_bwd",
