@@ -428,6 +428,21 @@ int ug_flash_attn_bwd(const void* q, int64_t q_row_stride, int64_t q_batch_strid
                       int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale,
                       const float* lse_in /* [batches][heads][Lq rounded up to 64], or NULL: recomputed */, void* workspace, int64_t workspace_bytes,
                       ug_stream_t stream);
+/* ---- Backward of the LoRA adapters (csrc/lora_bwd.hip; reference: torch autograd through the PEFT LoraLayer of train.py's
+ * `transformer_lora_parameters`). With y = x W^T + b + (x A_cat^T) B_bd^T and T = x A_cat^T, the adapter gradients are products with one skinny
+ * side R (the padded rank) that contract over the M rows: dA_cat = dT^T X, dB_bd^T = T^T dY.
+ * C[r][j] = alpha * sum_m P[m][r] * Q[m][j]: P [M, R] and Q [M, J] row-major (leading dimensions ldp, ldq: multiples of 8, bases 16-byte aligned),
+ * fp32 accumulation, alpha applied in fp32 before the one rounding; C [R, J] with leading dimension ldc. R = 64, 128, 192 or 256; J a multiple of 64;
+ * any M > 0 (the last partial block of rows is zero-filled on chip). The rows are split across workgroups; the splits' fp32 partial results go
+ * through the caller-owned workspace and are added in a fixed order (no atomics: results are bit-identical run to run).
+ * dB_bd itself is the transpose of the result for P = T, Q = dY: callers view it. ---- */
+int ug_lora_wgrad_bf16(const void* P, int64_t ldp, const void* Q, int64_t ldq, void* C, int64_t ldc, int64_t M, int64_t R, int64_t J, float alpha,
+                       void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+int ug_lora_wgrad_f32(const void* P, int64_t ldp, const void* Q, int64_t ldq, void* C, int64_t ldc, int64_t M, int64_t R, int64_t J, float alpha,
+                      void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+/* bytes of the fp32 scratch of ug_lora_wgrad_* for this shape (splits x R x J floats; 16-byte aligned). An upper bound for both twins: the bf16
+ * entry point stores straight from the tile when the shape makes one split and then ignores the workspace. */
+int64_t ug_lora_wgrad_workspace_bytes(int64_t M, int64_t R, int64_t J);
 int ug_transpose_f32(const void* src, int64_t ld_src, int64_t src_bstride, void* dst, int64_t ld_dst, int64_t dst_bstride, int64_t batch, int64_t rows,
                      int64_t cols, int64_t rows_pad, ug_stream_t stream);
 int ug_colsum_f32(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows, int64_t cols, int64_t rows_per_group,

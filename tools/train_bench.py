@@ -1,7 +1,9 @@
 """One training step (forward + backward of the control modules, reference train.py:622-662) at the FLUX-schnell geometry + canny control,
 random weights and inputs: seconds per step, samples/s, peak memory. Not the headline metric (BASELINE.json measures inference); the
 SURVEY 8(f) rank-4 row. --optim adds the optimizer step of train.py:658-660 (unigen_amd.optim.AdamW(max_grad_norm=1.0): clipping fused, fp32 masters)
-to each timed step. usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim]"""
+to each timed step. --lora R trains rank-R LoRA adapters on the attention projections of the control branch instead, everything else frozen
+(HipModule.set_lora_trainable; UniGenFlux only), and also times the same differentiable forward with the adapters switched off.
+usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim] [--lora R]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,7 +20,10 @@ ap.add_argument("--sd3", action="store_true", help="UniGenSD3 (SD3.5-medium geom
 ap.add_argument("--no-gradnorm", action="store_true", help="skip the per-step gradient-norm diagnostic (hundreds of small torch kernels: keep it out of rocprofv3 kernel statistics)")
 ap.add_argument("--shapes", action="store_true", help="per-shape table of the last step's GEMM / attention launches (grouped by FLOPs per launch)")
 ap.add_argument("--optim", action="store_true", help="time unigen_amd.optim.AdamW(lr=1e-4, weight_decay=1e-2, max_grad_norm=1.0).step() after each backward")
+ap.add_argument("--lora", type=int, default=0, metavar="R", help="train rank-R adapters on the control branch's attention projections, base and control modules frozen")
 a = ap.parse_args()
+if a.lora and a.sd3:
+    ap.error("--lora is implemented for UniGenFlux only")
 dev, BF = torch.device("cuda:0"), torch.bfloat16
 B = a.batch
 g = torch.Generator(device=dev).manual_seed(5)
@@ -46,7 +51,11 @@ else:
         use_rope=True, use_shared_expert=True, use_consis_module=False, use_single_trans_blocks=True, single_control_dev=2,
         single_block_control_method="overall_add", top_num=1, expert_num_each_condition=3))
     model.init_synthetic_(seed=0, std=0.02)
-    model.init_trainable_param()
+    if a.lora:
+        model.add_lora(["attn.to_q", "attn.to_k", "attn.to_v", "attn.to_out.0"], "canny", a.lora, 2.0 * a.lora, prefix="control_", init_lora_weights=False)
+        model.set_lora_trainable()
+    else:
+        model.init_trainable_param()
     if a.ckpt:
         model.enable_gradient_checkpointing()
     grid, T = a.size // 16, 512
@@ -67,6 +76,18 @@ if a.optim:
     opt = AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0)
 times, opt_times = [], []
 timer = None
+if a.lora:                         # the same differentiable forward with every adapter switched off (no adapter launch): what the adapters add to it
+    from unigen_amd.lora import enable_lora
+    fw_off = []
+    with enable_lora(list(model.modules()), []):
+        for _ in range(3):
+            torch.cuda.synchronize(); t0 = time.time()
+            o_ = fwd()
+            torch.cuda.synchronize(); fw_off.append(time.time() - t0)
+            del o_
+    for m_ in model._lora_sites.values():
+        m_.unscale_layer(None)         # enable_lora's exit multiplies by alpha / r again (the reference's behaviour): back to alpha / r
+    torch.cuda.reset_peak_memory_stats()
 for step in range(a.steps + 1):
     if step == a.steps:            # HIP events around every GEMM / attention launch of the last step (not part of the timed minimum)
         timer = ops.KernelTimer(kinds=("gemm", "attn", "attn_bwd")); ops.set_timer(timer)
@@ -96,6 +117,8 @@ extra = {}
 if opt is not None:
     op = min(opt_times)
     extra = dict(optimizer_s=round(op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5))
+if a.lora:
+    extra.update(lora_rank=a.lora, lora_sites=len(model._lora_sites), forward_adapters_off_s=round(min(fw_off[1:]), 3), backward_over_forward=round(bw / fw, 2))
 print("TRAIN_BENCH", json.dumps(dict(**extra, model="UniGenSD3" if a.sd3 else "UniGenFlux", batch=B, size=a.size, layers=[model.config.num_layers, getattr(model.config, "num_single_layers", 0)], checkpointing=bool(a.ckpt),
       params_total=n_all, params_trainable=n_train, forward_s=round(fw, 3), backward_s=round(bw, 3), samples_per_s=round(B / (fw + bw), 3),
       peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1), kernel_rates=rates)))

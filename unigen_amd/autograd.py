@@ -264,6 +264,111 @@ def linear_n(x: torch.Tensor, ws, bs):
     return [o.unflatten(0, lead) if len(lead) != 1 else o for o in outs]
 
 
+class LoRALinearN(torch.autograd.Function):
+    """LinearN (n >= 1 projections of the same rows x) with live LoRA adapters:  y_i = x w_i^T + b_i + T B_bd[rows of i]^T,  T = bf16(x A_cat^T).
+    `a_cat` [Rp, K] / `b_bd` [sum N_i, Rp] are the fused operands of lora.fuse_adapters_autograd (differentiable: torch.autograd carries their
+    gradients on to every adapter's own lora_A / lora_B). The forward is the inference engine's (engine._lora_operands + the K-segment launch): the
+    same two launches, the same rounding points. `has` [n]: whether projection i carries a live adapter (its rows of b_bd are non-zero).
+    Backward: dT = sum_i dy_i B_bd[rows of i] (the projections' rank columns are disjoint, so accumulating through the GEMM's residual epilogue adds
+    exact zeros); dx = sum_i dy_i w_i + dT A_cat, the adapter term as the K-segment of the first launch; dA_cat = dT^T x and dB_bd[rows of i] =
+    (T^T dy_i)^T through ug_lora_wgrad - no transposed copy of x or dy unless a base weight itself is trainable."""
+
+    @staticmethod
+    def forward(ctx, x, n, has, a_cat, b_bd, *wb):
+        ws, bs = wb[:n], wb[n:]
+        M, K = x.shape
+        Ns = [w.shape[0] for w in ws]
+        t = torch.empty(M, a_cat.shape[0], device=x.device, dtype=x.dtype)
+        ops.gemm(x, a_cat, None, t, M=M)
+        out = torch.empty(M, sum(Ns), device=x.device, dtype=x.dtype)
+        has_b = all(b is not None for b in bs)
+        if _adjacent(list(ws)) and (has_b and _adjacent([b.view(-1, 1) for b in bs]) or all(b is None for b in bs)):
+            wp = torch.as_strided(ws[0], (sum(Ns), K), (K, 1))
+            bp = torch.as_strided(bs[0], (sum(Ns),), (1,)) if has_b else None
+            ops.gemm(x, wp, bp, out, M=M, lora_t=t, lora_b=b_bd)
+        else:
+            c0 = 0
+            for w, b, N, h in zip(ws, bs, Ns, has):
+                ops.gemm(x, w, b, out[:, c0:], M=M, lora_t=t if h else None, lora_b=b_bd[c0:c0 + N] if h else None)
+                c0 += N
+        ctx.save_for_backward(x, t, a_cat, b_bd, *ws)
+        ctx.n, ctx.Ns, ctx.has, ctx.has_b = n, Ns, tuple(has), [b is not None for b in bs]
+        outs, c0 = [], 0
+        for N in Ns:
+            outs.append(out[:, c0:c0 + N]); c0 += N
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        saved = ctx.saved_tensors            # ONE access (block checkpointing, see LinearN.backward)
+        x, t, a_cat, b_bd, ws = saved[0], saved[1], saved[2], saved[3], saved[4:]
+        n, M, K, Rp = ctx.n, x.shape[0], x.shape[1], a_cat.shape[0]
+        need_x, need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        dys = [None if dy is None else dy.contiguous() for dy in dys]
+        row0 = [sum(ctx.Ns[:i]) for i in range(n)]
+        for dy, w in zip(dys, ws):
+            if dy is not None and w.shape[0] % 64 != 0:
+                raise L.UniGenHipError(f"LoRALinearN backward: out_features={w.shape[0]} must be a multiple of 64")
+        d_t = None
+        if need_x or need_a:
+            for i, dy in enumerate(dys):
+                if dy is None or not ctx.has[i]:
+                    continue
+                bt = ops.transpose(b_bd[row0[i]:row0[i] + ctx.Ns[i]].detach())                     # [Rp, N_i]
+                if d_t is None:
+                    d_t = torch.empty(M, Rp, device=x.device, dtype=x.dtype)
+                    ops.gemm(dy, bt, None, d_t, M=M)
+                else:
+                    ops.gemm(dy, bt, None, d_t, M=M, epilogue=L.EPI_RES_SCALE, residual=d_t, alpha=1.0)
+        dx = da = db = None
+        dws, dbs = [None] * n, [None] * n
+        Mp = _pad64(M)
+        for i, (dy, w) in enumerate(zip(dys, ws)):
+            if dy is None:
+                continue
+            N = w.shape[0]
+            if need_x:
+                if dx is None:                                    # dy_i w_i + dT A_cat in one accumulator (lora_b [K, Rp] = A_cat^T)
+                    dx = torch.empty(M, K, device=x.device, dtype=x.dtype)
+                    ops.gemm(dy, _w_transposed(w), None, dx, M=M, lora_t=d_t, lora_b=ops.transpose(a_cat.detach()) if d_t is not None else None)
+                else:
+                    ops.gemm(dy, _w_transposed(w), None, dx, M=M, epilogue=L.EPI_RES_SCALE, residual=dx, alpha=1.0)
+            if ctx.needs_input_grad[5 + i]:                       # a trainable base weight: the transposed-copy route of Linear._grads
+                dw = torch.empty(N, K, device=x.device, dtype=x.dtype)
+                ops.gemm(ops.transpose(dy, Mp), _x_transposed(x, Mp), None, dw, M=N)
+                dws[i] = dw
+            if ctx.has_b[i] and ctx.needs_input_grad[5 + n + i]:
+                dbs[i] = ops.colsum(dy).view(N)
+        if need_a and d_t is not None:
+            da = ops.lora_wgrad(d_t, x)
+        if need_b and any(dy is not None and h for dy, h in zip(dys, ctx.has)):
+            full = all(dy is not None and h for dy, h in zip(dys, ctx.has))
+            dbt = (torch.empty if full else torch.zeros)(Rp, sum(ctx.Ns), device=x.device, dtype=x.dtype)
+            for i, dy in enumerate(dys):
+                if dy is not None and ctx.has[i]:
+                    ops.lora_wgrad(t, dy, dbt[:, row0[i]:row0[i] + ctx.Ns[i]])
+            db = dbt.t()                                          # produced as [Rp, N] (ug_lora_wgrad's orientation), viewed as [N, Rp]
+        return (dx, None, None, da, db, *dws, *dbs)
+
+
+def lora_linear_n(x: torch.Tensor, ws, bs, a_cat: torch.Tensor, b_bd: torch.Tensor, has):
+    """linear_n with the fused adapter operands of the launch (lora.fuse_adapters_autograd)."""
+    lead = x.shape[:-1]
+    outs = LoRALinearN.apply(x.reshape(-1, x.shape[-1]).contiguous(), len(ws), tuple(has), a_cat, b_bd, *ws, *bs)
+    return [o.unflatten(0, lead) if len(lead) != 1 else o for o in outs]
+
+
+def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], a_cat: torch.Tensor, b_bd: torch.Tensor) -> torch.Tensor:
+    lead = x.shape[:-1]
+    return LoRALinearN.apply(x.reshape(-1, x.shape[-1]).contiguous(), 1, (True,), a_cat, b_bd, w, b)[0].view(*lead, w.shape[0])
+
+
+def lora_linear_cat2(a: torch.Tensor, m: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], a_cat: torch.Tensor, b_bd: torch.Tensor) -> torch.Tensor:
+    """linear_cat2 with adapters on the projection: the GEMM's one K-segment is taken by the adapters (as in the inference engine, whose
+    [attention | mlp] operand is one buffer), so the concatenation is materialised; same bits as linear_cat2 + the adapter term."""
+    return lora_linear(torch.cat([a, m], dim=-1), w, b, a_cat, b_bd)
+
+
 class MoeGate(torch.autograd.Function):
     """gates = softmax(F.linear((x + c).float(), wg.float())) [S, E] fp32 and the arg-max expert per token: ug_moe_gate_top1 forward,
     ug_moe_gate_bwd backward (deepspeed TopKGate, src/UniGenUtils.py:99). top_k = 2 (top2gating): ug_moe_gate_top2, idx [2, S] with the second

@@ -271,6 +271,66 @@ class HipModule(nn.Module):
                                 m.set_scale(a, 1.0)
         return cm()
 
+    def set_lora_trainable(self, adapters: Optional[Sequence[str]] = None, freeze_rest: bool = True) -> Sequence[str]:
+        """Make the `lora_A` / `lora_B` weights of the named adapters (None: every adapter) trainable - the reference's `transformer_lora_parameters`
+        (train.py:349). With `freeze_rest` every other parameter is frozen (the base, the control modules, the adapters not named); those adapters
+        still take part in the forward while live. The differentiable forward (unigen_amd/training.py) then runs the LoRA-carrying linears of
+        unigen_amd/autograd.py. Returns the names of the trainable parameters."""
+        known = {a for m in self._lora_sites.values() for a in m.lora_A}
+        want = known if adapters is None else set(adapters)
+        if not want or want - known:
+            raise ValueError(f"set_lora_trainable: unknown adapters {sorted(want - known)} (attached: {sorted(known)})" if want else
+                             "set_lora_trainable: no adapter is attached (add_lora)")
+        if freeze_rest:
+            self.requires_grad_(False)
+        for m in self._lora_sites.values():
+            for a in want & set(m.lora_A):
+                m.lora_A[a].weight.requires_grad_(True)
+                m.lora_B[a].weight.requires_grad_(True)
+        return [n for n, p_ in self.named_parameters() if p_.requires_grad]
+
+    def lora_state_dict(self, adapter: str) -> Dict[str, torch.Tensor]:
+        """What PEFT's `get_peft_model_state_dict(model, adapter_name=adapter)` returns and the reference's save hook writes (src/hook.py:29-46):
+        `<proj>.lora_A.weight` / `<proj>.lora_B.weight` - the adapter name dropped - for every projection that carries the adapter."""
+        sd = {}
+        for name, m in self._lora_sites.items():
+            if adapter in m.lora_A:
+                sd[f"{name}.lora_A.weight"] = m.lora_A[adapter].weight.detach().clone()
+                sd[f"{name}.lora_B.weight"] = m.lora_B[adapter].weight.detach().clone()
+        if not sd:
+            raise KeyError(f"lora_state_dict: no projection carries an adapter named {adapter!r}")
+        return sd
+
+    def load_lora_state_dict(self, state_dict: Dict[str, torch.Tensor], adapter: str) -> Sequence[str]:
+        """Load the weights of `adapter` (already attached with add_lora: rank and alpha are not part of a state dict). Accepted key forms:
+        `<proj>.lora_A.weight` (lora_state_dict / PEFT), the same under a `transformer.` prefix (what `FluxPipeline.lora_state_dict` hands to the
+        reference's load hook, src/hook.py:49-70) and the in-model `<proj>.lora_A.<adapter>.weight` (the base weights of a PEFT-wrapped
+        checkpoint sit under `<proj>.base_layer.`: INTEGRATION.md). Every projection that carries the adapter must be covered, every key must be used. Returns the loaded keys."""
+        want = {f"{n}.lora_{s}": getattr(m, f"lora_{s}")[adapter].weight for n, m in self._lora_sites.items() if adapter in m.lora_A for s in "AB"}
+        if not want:
+            raise KeyError(f"load_lora_state_dict: no projection carries an adapter named {adapter!r}")
+        used = []
+        with torch.no_grad():
+            for key, val in state_dict.items():
+                k = key[len("transformer."):] if key.startswith("transformer.") else key
+                if not k.endswith(".weight"):
+                    raise KeyError(f"load_lora_state_dict: unexpected key {key!r}")
+                k = k[:-len(".weight")]
+                if k.endswith("." + adapter):
+                    k = k[:-len(adapter) - 1]
+                dst = want.get(k)
+                if dst is None or k in used:
+                    raise KeyError(f"load_lora_state_dict: {key!r} does not name a lora_A / lora_B weight of adapter {adapter!r}")
+                if tuple(val.shape) != tuple(dst.shape):
+                    raise ValueError(f"load_lora_state_dict: {key!r} is {tuple(val.shape)}, the adapter's weight is {tuple(dst.shape)}")
+                dst.copy_(val.to(dst.device, dst.dtype))
+                used.append(k)
+        if set(used) != set(want):
+            raise KeyError(f"load_lora_state_dict: missing {sorted(set(want) - set(used))[:4]} ...")
+        return used
+
+    # No longer called by the forwards - the differentiable forward carries live adapters (training._lora) - but kept as it was: its behaviour is
+    # pinned by the host tests.
     def _refuse_lora_in_training(self):
         if self._lora_sites and any(m.live_adapters() for m in self._lora_sites.values()):
             raise NotImplementedError("the differentiable forward (unigen_amd/training.py) does not carry LoRA adapters: run under torch.no_grad(), "
@@ -289,7 +349,8 @@ class HipModule(nn.Module):
         if not self._lora_live(prefixes):
             return None, None
         sites = [self._lora_sites.get(p) for p in prefixes]
-        state = tuple((p, tuple((n, s.scaling[n], s.lora_A[n].weight._version, s.lora_B[n].weight._version, s.lora_A[n].weight.data_ptr())
+        state = tuple((p, tuple((n, s.scaling[n], s.lora_A[n].weight._version, s.lora_B[n].weight._version, s.lora_A[n].weight.data_ptr(),
+                                 s.lora_B[n].weight.data_ptr())
                                 for n in s.live_adapters())) for p, s in zip(prefixes, sites) if s is not None)
         key = (tuple(prefixes), self.dtype)
         hit = self._lora_fused.get(key)

@@ -425,8 +425,8 @@ class UniGenFlux(HipModule):
         train.py:622-662 after `init_trainable_param()` - the differentiable forward of unigen_amd/training.py. Same arguments, same 3-tuple."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from . import training
-            self._refuse_lora_in_training()
-            return training.flux_forward(self, *args, **kwargs)
+            with self._lora_scaled(kwargs.get("joint_attention_kwargs")):
+                return training.flux_forward(self, *args, **kwargs)
         with torch.no_grad(), self._lora_scaled(kwargs.get("joint_attention_kwargs")):
             return self._forward_inference(*args, **kwargs)
 

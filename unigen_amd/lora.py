@@ -111,6 +111,36 @@ def fuse_adapters(layers: List[Optional["LoRALayer"]], widths: List[int], dtype,
     return A, Bm
 
 
+def fuse_adapters_autograd(layers: List[Optional["LoRALayer"]], widths: List[int], dtype, device):
+    """fuse_adapters for the differentiable forward (unigen_amd/training.py): the same A_cat / B_bd values, built from the adapters' Parameters with
+    differentiable torch ops (cat, pad, `(B.float() * s).to(dtype)`), so torch.autograd hands the gradients of the fused operands to every adapter's
+    own `lora_A.<name>.weight` / `lora_B.<name>.weight` - the scaling included, the zero blocks and the padded rank columns receiving nothing; the
+    rounding of s * B to `dtype` is the identity in the backward. Not cached: the result belongs to one forward's tape.
+    Returns (A_cat, B_bd, has) - has[i]: projection i carries a live adapter - or None when nothing is live."""
+    pad = torch.nn.functional.pad
+    a_rows, b_cols, spans, R = [], [], [], 0
+    for lay in layers:
+        live = lay.live_adapters() if lay is not None else []
+        c0 = R
+        for a in live:
+            a_rows.append(lay.lora_A[a].weight)
+            b_cols.append((lay.lora_B[a].weight.float() * lay.scaling[a]).to(dtype))
+            R += lay.r[a]
+        spans.append((c0, R, len(live)))
+    if not a_rows:
+        return None
+    Rp = (R + _RANK_PAD - 1) // _RANK_PAD * _RANK_PAD
+    A = pad(torch.cat(a_rows, 0), (0, 0, 0, Rp - R))
+    rows, k = [], 0
+    for (c0, c1, cnt), N in zip(spans, widths):
+        if cnt == 0:
+            rows.append(torch.zeros(N, Rp, device=device, dtype=dtype))
+        else:
+            rows.append(pad(torch.cat(b_cols[k:k + cnt], 1), (c0, Rp - c1)))
+            k += cnt
+    return A, torch.cat(rows, 0), tuple(cnt > 0 for _, _, cnt in spans)
+
+
 class LoRALinear(nn.Module, LoRALayer):
     """nn.Linear-shaped layer (weight [N, K], bias [N]) with named LoRA adapters, stand-alone (outside a transformer)."""
 

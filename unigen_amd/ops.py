@@ -650,6 +650,26 @@ def colsum(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, rows_per_group:
     return out
 
 
+def lora_wgrad(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = None, *, alpha: float = 1.0) -> torch.Tensor:
+    """p [M, R]^T q [M, J] -> [R, J] (ug_lora_wgrad_bf16 / _f32): the adapter gradients dA_cat = dT^T X and dB_bd^T = T^T dY straight from the row-major
+    operands (any row stride that is a multiple of 8). R = 64 ... 256 in steps of 64, J a multiple of 64, any M. `out`: a [R, J] tensor or column
+    block (its row stride is the leading dimension)."""
+    dt = _act(p, "p")
+    _chk(p, "p", dt); _chk(q, "q", dt)
+    (M, R), J = p.shape, q.shape[1]
+    if q.shape[0] != M or p.dim() != 2 or q.dim() != 2:
+        raise ValueError(f"lora_wgrad: p {tuple(p.shape)} and q {tuple(q.shape)} must share their rows")
+    if out is None:
+        out = torch.empty(R, J, device=p.device, dtype=dt)
+    _chk(out, "out", dt)
+    if tuple(out.shape) != (R, J):
+        raise ValueError(f"lora_wgrad: out must be [{R}, {J}], got {tuple(out.shape)}")
+    ws = torch.empty(int(L.load().ug_lora_wgrad_workspace_bytes(M, R, J)), device=p.device, dtype=torch.uint8)
+    L.check(_fn("ug_lora_wgrad_bf16", dt)(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0), M, R, J, alpha,
+                                          ws.data_ptr(), ws.numel(), _stream()), "ug_lora_wgrad_bf16")
+    return out
+
+
 def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
     dt = _act(x, "x")
     x = x.contiguous()

@@ -25,16 +25,35 @@ def _p(model, name: str) -> Optional[torch.Tensor]:
     return model.get_parameter(name) if name in model._pnames() else None
 
 
+def _lora(model, prefixes):
+    """The fused operands (A_cat, B_bd, has) of the live LoRA adapters of ONE launch over `prefixes` (lora.fuse_adapters_autograd), None when no
+    adapter is live - the launch is then the adapter-free one, as in engine._lora_operands. `enable_lora(...)` and a scaling of 0 act here as they do
+    on inference: such an adapter is not live, takes no launch and gets no gradient."""
+    if not model._lora_live(prefixes):
+        return None
+    from .lora import fuse_adapters_autograd
+    return fuse_adapters_autograd([model._lora_sites.get(p) for p in prefixes], [model.get_parameter(p + ".weight").shape[0] for p in prefixes],
+                                  model.dtype, model.device)
+
+
 def _lin(model, prefix: str, x: torch.Tensor) -> torch.Tensor:
+    lo = _lora(model, [prefix])
+    if lo is not None:
+        return A.lora_linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"), lo[0], lo[1])
     return A.linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"))
 
 
 def _lin_n(model, x: torch.Tensor, prefixes):
-    return A.linear_n(x, [_p(model, p + ".weight") for p in prefixes], [_p(model, p + ".bias") for p in prefixes])
+    ws, bs = [_p(model, p + ".weight") for p in prefixes], [_p(model, p + ".bias") for p in prefixes]
+    lo = _lora(model, prefixes)
+    if lo is not None:
+        return A.lora_linear_n(x, ws, bs, *lo)
+    return A.linear_n(x, ws, bs)
 
 
 def _zero_res(model, prefix: str, x, z, scale: float):
-    """x + Linear(z) * conditioning_scale (src/UniGenTransformer.py:1104 + :1141 / :1166-1172): one GEMM with the residual epilogue."""
+    """x + Linear(z) * conditioning_scale (src/UniGenTransformer.py:1104 + :1141 / :1166-1172): one GEMM with the residual epilogue.
+    (The zero-res projections are not among HipModule.LORA_CAPABLE - add_lora refuses them - so this funnel has no adapter form.)"""
     return A.linear_res_scale(x, z, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"), scale)
 
 
@@ -90,10 +109,25 @@ def _attention(model, prefix: str, x, enc, rope, text_first: bool, mlp_prefix: O
 
 
 def _ckpt(model, fn, *tensors):
-    """Block-level activation checkpointing when `enable_gradient_checkpointing()` was called (train.py:317), as diffusers does per block."""
+    """Block-level activation checkpointing when `enable_gradient_checkpointing()` was called (train.py:317), as diffusers does per block.
+    The recomputation runs inside backward(), possibly after an `enable_lora(...)` context or the forward's `joint_attention_kwargs` scale has been
+    undone: the adapters' switch state of the forward is put back around it, so that the block is recomputed with the operands it ran with."""
     if getattr(model, "_grad_checkpoint", False):
         from torch.utils.checkpoint import checkpoint
-        return checkpoint(fn, *tensors, use_reentrant=False)
+        if not model._lora_sites:
+            return checkpoint(fn, *tensors, use_reentrant=False)
+        snap = [(m, dict(m.scaling), list(m.active_adapters)) for m in model._lora_sites.values()]
+
+        def run(*ts):
+            now = [(m, m.scaling, m.active_adapters) for m, _, _ in snap]
+            for m, sc, act in snap:
+                m.scaling, m.active_adapters = dict(sc), list(act)
+            try:
+                return fn(*ts)
+            finally:
+                for m, sc, act in now:
+                    m.scaling, m.active_adapters = sc, act
+        return checkpoint(run, *tensors, use_reentrant=False)
     return fn(*tensors)
 
 
@@ -125,7 +159,10 @@ def _single_block_body(model, prefix: str, h, temb, rope):
     a, _ = _attention(model, prefix + ".attn", n, None, rope, True, mlp_prefix=prefix + ".proj_mlp")
     mlp = A.GeluTanh.apply(_lin(model, prefix + ".proj_mlp", n))      # its own GEMM: GELU wants a contiguous [M, 4 D] (a view of the fused output would be copied)
     # proj_out(cat[a, mlp]) without the [B, L, 5 D] concatenation: the mlp columns ride as the GEMM's K-segment extension (same bits)
-    return A.gate_residual(h, A.linear_cat2(a, mlp, _p(model, prefix + ".proj_out.weight"), _p(model, prefix + ".proj_out.bias")), gate)
+    w_o, b_o = _p(model, prefix + ".proj_out.weight"), _p(model, prefix + ".proj_out.bias")
+    lo = _lora(model, [prefix + ".proj_out"])
+    o = A.lora_linear_cat2(a, mlp, w_o, b_o, lo[0], lo[1]) if lo is not None else A.linear_cat2(a, mlp, w_o, b_o)
+    return A.gate_residual(h, o, gate)
 
 
 class _GatherRows(torch.autograd.Function):
