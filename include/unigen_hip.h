@@ -275,13 +275,17 @@ typedef struct ug_conv_desc {
 int ug_conv2d_nhwc(const ug_conv_desc* d, ug_stream_t stream);
 
 /* out = [SiLU](GroupNorm(x; G groups, eps, gamma, beta)), x / out NHWC [B][HW][C] (F.group_norm + F.silu in ResnetBlock2D / Attention.group_norm /
- * conv_norm_out). Deterministic two-pass statistics in fp64; workspace >= ug_groupnorm_workspace_bytes(B, HW, G), 8-byte aligned, no init needed. */
+ * conv_norm_out). Deterministic two-pass statistics in fp64 (per-thread sums over 64 rows: fp32 in the bf16 kernels, where they are exact for
+ * bf16 inputs of one magnitude; fp64 in the fp32 twin, which holds rel-L2 1e-5 up to a group mean of 64 standard deviations and returns beta
+ * exactly on a constant sample); workspace >= ug_groupnorm_workspace_bytes(B, HW, G), 8-byte aligned, no init needed.
+ * UG_ERR_UNSUPPORTED unless C % 8 == 0 and C / G divides 256; UG_ERR_BAD_SHAPE unless G divides C. */
 int64_t ug_groupnorm_workspace_bytes(int64_t B, int64_t HW, int32_t G);
 int ug_groupnorm_nhwc(const void* x, const void* gamma, const void* beta, void* out, void* workspace, int64_t workspace_bytes,
                       int64_t B, int64_t HW, int64_t C, int32_t G, float eps, int32_t silu, ug_stream_t stream);
 
 /* P[r][c] = softmax_c(scale * S[r][c]), S fp32 (ug_gemm_bf16 with UG_EPI_F32), P bf16: the VAE mid-block attention has one head of dim C
- * (F.scaled_dot_product_attention in AttnProcessor2_0), run as scores GEMM -> this -> P.V GEMM. */
+ * (F.scaled_dot_product_attention in AttnProcessor2_0), run as scores GEMM -> this -> P.V GEMM. Rows may be views (ld_s, ld_p >= cols); any
+ * sign of scale. The fp32 twin takes scale s - max in fp64, so a common offset of the scores does not reach the probabilities. */
 int ug_softmax_rows(const float* S, int64_t ld_s, void* P, int64_t ld_p, int64_t rows, int64_t cols, float scale, ug_stream_t stream);
 
 /* Layout changes at the VAE boundary: NCHW [B][C][HW] <-> NHWC [B][HW][Cp], Cp >= C (extra channels zero / ignored). div != 0 applies the

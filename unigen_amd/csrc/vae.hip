@@ -21,6 +21,7 @@
 #include "ug_common.h"
 #include "gemm_epilogue.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -196,9 +197,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
     const T* xb = x + ((int64_t)b * HW) * C;
     for (int c0 = 0; c0 < C; c0 += 256) {
         const int c = c0 + threadIdx.x;
-        float s = 0.f, q = 0.f;
+        // bf16 (product): fp32 sums, exact while a chunk's sums fit 24 bits. fp32 twin: fp64 sums - 64 fp32 additions of v and of the rounded v v lose
+        // 1e-4 of a group's variance once its mean is 64 standard deviations, which every normalised output of the group then carries
+        typename std::conditional<ElemT<T>::kF32, double, float>::type s = 0, q = 0;
         if (c < C)
-            for (int64_t r = r0; r < r1; ++r) { const float v = ElemT<T>::ld(xb + r * C + c); s += v; q += v * v; }
+            for (int64_t r = r0; r < r1; ++r) { const decltype(s) v = ElemT<T>::ld(xb + r * C + c); s += v; q += v * v; }
         red[threadIdx.x][0] = s; red[threadIdx.x][1] = q;
         __syncthreads();
         if (c < C && threadIdx.x % cg == 0) {            // cg divides 256 (host check): a group never straddles two passes
@@ -343,23 +346,31 @@ __global__ __launch_bounds__(256) void gn_apply_fast_kernel(const bf16_t* __rest
     for (; r < r1; r += RPP) one(*(const u32x4*)(xp + r * C), op + r * C);
 }
 
-// P[r][:] = softmax(scale * S[r][:]) : S fp32 [rows][ld_s], P element type T [rows][ld_p]; one block per row
+// P[r][:] = softmax(scale * S[r][:]) : S fp32 [rows][ld_s], P element type T [rows][ld_p]; one block per row.
+// The argument scale s - max is taken in fp32 by the bf16 kernel and in fp64 by the fp32 twin: the fp32 product scale s is rounded at the
+// magnitude of s, so scores with a large common offset (1e4: 1e-4 absolute at scale 0.3) carry that into every probability - inside half a
+// bf16 ulp, outside the twin's 1e-5.
+__device__ inline float sm_max(float a, float b) { return fmaxf(a, b); }
+__device__ inline double sm_max(double a, double b) { return fmax(a, b); }
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ S, int64_t ld_s, T* __restrict__ P, int64_t ld_p, int cols, float scale) {
+    using A = typename std::conditional<ElemT<T>::kF32, double, float>::type;
+    __shared__ A redm[256];
     __shared__ float red[256];
     const float* s = S + (int64_t)blockIdx.x * ld_s;
     T* p = P + (int64_t)blockIdx.x * ld_p;
-    float mx = -INFINITY;
-    for (int c = threadIdx.x; c < cols; c += 256) mx = fmaxf(mx, s[c] * scale);
-    red[threadIdx.x] = mx; __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    mx = red[0]; __syncthreads();
+    const A sc = scale;
+    A mx = -INFINITY;
+    for (int c = threadIdx.x; c < cols; c += 256) mx = sm_max(mx, (A)s[c] * sc);
+    redm[threadIdx.x] = mx; __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) redm[threadIdx.x] = sm_max(redm[threadIdx.x], redm[threadIdx.x + o]); __syncthreads(); }
+    mx = redm[0]; __syncthreads();
     float sum = 0.f;
-    for (int c = threadIdx.x; c < cols; c += 256) sum += expf(s[c] * scale - mx);
+    for (int c = threadIdx.x; c < cols; c += 256) sum += expf((float)((A)s[c] * sc - mx));
     red[threadIdx.x] = sum; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
     const float inv = 1.0f / red[0];
-    for (int c = threadIdx.x; c < cols; c += 256) ElemT<T>::st(p + c, expf(s[c] * scale - mx) * inv);
+    for (int c = threadIdx.x; c < cols; c += 256) ElemT<T>::st(p + c, expf((float)((A)s[c] * sc - mx)) * inv);
 }
 
 // bf16 product form for cols == 1024 NV (NV <= 16: the VAE's 4096 / 16384 tokens): the row is read ONCE (16-byte loads, 4 NV values per thread in
