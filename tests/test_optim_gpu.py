@@ -4,6 +4,8 @@ no host synchronisation, and three training steps of the tiny model whose infere
 import pytest
 import torch
 
+from tests.step_kernel_ref import AdamWRef64 as _Ref64          # the fp64 recurrence, shared with the kernel sweep
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 SIZES = [1, 7, 4095, (1 << 20) + 3]
@@ -34,28 +36,6 @@ def _rel(a, b):
 
 def _cat(ts):
     return torch.cat([t.detach().double().flatten().cpu() for t in ts])
-
-
-class _Ref64:
-    """fp64 restatement of torch.optim.AdamW's recurrence (decoupled weight decay)."""
-
-    def __init__(self, params):
-        self.p = [p.detach().double().clone() for p in params]
-        self.m = [torch.zeros_like(x) for x in self.p]
-        self.v = [torch.zeros_like(x) for x in self.p]
-        self.t = 0
-
-    def step(self, grads, lr, wd, betas=(0.9, 0.999), eps=1e-8):
-        self.t += 1
-        b1, b2 = betas
-        for i in range(len(self.p)):
-            g = grads[i].double()
-            lr_i, wd_i = (lr[i], wd[i]) if isinstance(lr, list) else (lr, wd)
-            self.p[i] *= 1 - lr_i * wd_i
-            self.m[i] += (1 - b1) * (g - self.m[i])
-            self.v[i] = b2 * self.v[i] + (1 - b2) * g * g
-            denom = self.v[i].sqrt() / (1 - b2 ** self.t) ** 0.5 + eps
-            self.p[i] -= lr_i / (1 - b1 ** self.t) * self.m[i] / denom
 
 
 def test_clip_grad_norm_matches_fp64_and_torch(gpu):

@@ -68,6 +68,12 @@ class AdamwGroup(C.Structure):
                 ("_pad", f32)]
 
 
+def optim_tensor(*, grad: int, grad_dtype: int, numel: int, param: int = 0, param_dtype: int = UG_DT_F32, master: int = 0, exp_avg: int = 0,
+                 exp_avg_sq: int = 0, group: int = 0) -> OptimTensor:
+    """One ug_optim_tensor from raw device addresses (0 = NULL): any element alignment, any of the four (grad dtype, master) forms."""
+    return OptimTensor(param or None, grad or None, master or None, exp_avg or None, exp_avg_sq or None, numel, param_dtype, grad_dtype, group, 0)
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/unigen_hip.h
 SIGNATURES = {
     "ug_version": (i32, []),
