@@ -1,5 +1,6 @@
 """CPU float64 references of the forward projection kernels: the stand-alone q/k RMSNorm + RoPE pass (ug_qk_rmsnorm_rope), the GEMM's fused
-q/k epilogue (UG_EPI_QKV_ROPE) and the GEMM with a LoRA K-segment under every epilogue.
+q/k epilogue (UG_EPI_QKV_ROPE), the GEMM with a LoRA K-segment under every epilogue and (second half: flat buffers, sampled rows, the dispatcher's
+path restated) the base GEMM, AdaLN modulate and the small linear of tests/test_fuzz_gemm_gpu.py.
 
 Every function takes the operands exactly as the kernel sees them (bf16 or fp32 values, here widened to float64; the buffers and row maps of
 the C ABI) and returns two whole output buffers: the exact result (nothing rounded) and a rounding-point variant that rounds to bf16 where the
@@ -222,3 +223,183 @@ def lora_operands(g, M, N, K, r, r_pad=None, cancel=False):
         t[:, K:] = bf16(0.02 * t[:, K:])                  # the rest of the rank and the bias at the size of what is left
         b = bf16(0.02 * b)
     return a, w, b, t, lb
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the base GEMM (no LoRA segment), AdaLN modulate and the small linear: references of tests/test_fuzz_gemm_gpu.py. Operands are the FLAT
+# buffers of the C ABI (any device; only the rows asked for are gathered and widened to float64 on the CPU), strides in elements.
+# ----------------------------------------------------------------------------------------------------------------------------------
+EPI_F32 = 4
+F32_TOTAL, F32_ROW, FLOOR = 1e-5, 1e-4, 2.0 ** -9
+TILE = 256
+
+
+def _flat_rows(buf, base, width):
+    """buf[base[i] + j], j < width, of a flat buffer -> float64 on the CPU"""
+    idx = base[:, None] + torch.arange(width)[None, :]
+    return buf.reshape(-1)[idx.to(buf.device)].cpu().to(F64)
+
+
+def gemm(a, w, bias, *, M, N, K, rows=None, epilogue=EPI_BIAS, lda=None, ldw=None, a_map=(0, 0), residual=None, ldr=0, r_map=(0, 0), gate=None,
+         gate_ld=0, rows_per_sample=0, alpha=1.0, groups=1, a_gstride=0, w_gstride=0, bias_gstride=0, r_gstride=0, gate_gstride=0,
+         gelu_from_n=0, **_):
+    """ug_gemm_bf16 without a LoRA segment on the logical rows `rows` (default: all M) of every group: v = A[g][map(m)] . W[g][n] + bias[g][n];
+    UG_EPI_F32: v itself (fp32 out, nothing rounded); else the epilogue on v (GELU from column gelu_from_n, R[g][map(m)] + gate[g][m //
+    rows_per_sample] v, R + alpha v with alpha as the fp32 the descriptor carries). Returns (exact, variant) [groups, len(rows), N]: the LOGICAL
+    values; gemm_dest gives where the kernel stores them (C row map, column split, group stride)."""
+    rows = torch.arange(M) if rows is None else rows
+    lda, ldw = lda or K, ldw or K
+    cols = torch.arange(N)
+    alpha = float(torch.tensor(alpha, dtype=torch.float32))
+    ex, va = [], []
+    for g in range(max(groups, 1)):
+        A = _flat_rows(a, g * a_gstride + rowmap(rows, *a_map) * lda, K)
+        W = _flat_rows(w, g * w_gstride + cols * ldw, K)
+        acc = A @ W.t()
+        if bias is not None:
+            acc = acc + _flat_rows(bias, torch.tensor([g * bias_gstride]), N)
+        R = G = None
+        if epilogue in (EPI_RES_GATE, EPI_RES_SCALE):
+            R = _flat_rows(residual, g * r_gstride + rowmap(rows, *r_map) * ldr, N)
+        if epilogue == EPI_RES_GATE:
+            G = _flat_rows(gate, g * gate_gstride + (rows // rows_per_sample) * gate_ld, N)
+        for rnd, dst in ((False, ex), (True, va)):
+            v = bf16(acc) if rnd and epilogue != EPI_F32 else acc
+            dst.append(_epilogue(v, epilogue, rnd, cols, R=R, gate=G, alpha=alpha, gelu_from_n=gelu_from_n))
+    return torch.stack(ex), torch.stack(va)
+
+
+def gemm_dest(rows, *, N, ldc, c_map=(0, 0), groups=1, c_gstride=0, c_shift_from_n=0, c_shift=0, **_):
+    """element offsets from the C base of the logical elements (rows x [0, N)) of every group: [groups, len(rows), N]"""
+    cols = torch.arange(N, device=rows.device)
+    dst = cols + c_shift * (cols >= c_shift_from_n).long() if c_shift_from_n > 0 else cols
+    base = rowmap(rows, *c_map) * ldc
+    return (torch.arange(max(groups, 1), device=rows.device) * c_gstride)[:, None, None] + base[None, :, None] + dst[None, None, :]
+
+
+def gemm_store(out, vals, *, M, ldc, c_map=(0, 0), groups=1, c_gstride=0, c_shift_from_n=0, c_shift=0, **_):
+    """the whole C buffer after the call: `out` (flat, the buffer before the call) with vals [groups, M, N] stored; everything else untouched"""
+    o = out.to(F64).clone()
+    m, cols = torch.arange(M), torch.arange(vals.shape[-1])
+    rows_phys = int(rowmap(m, *c_map).max()) + 1
+    for g in range(max(groups, 1)):
+        view = o[g * c_gstride:].as_strided((rows_phys, ldc), (ldc, 1))
+        _store(view, m, cols, c_map, c_shift_from_n, c_shift, vals[g])
+    return o
+
+
+def sample_rows(M, *, boundaries=(), seed=0, per_tile=8):
+    """the logical rows a large case is judged on in float64: first and last row of every 256-row tile, per_tile seeded rows of each, the rows
+    on both sides of every multiple of each period in `boundaries` (rows per sample, rows per batch of the row maps; periods <= 8 have no
+    'inside' and are left to the seeded rows), the last 8 rows."""
+    import random
+    s = set(range(max(0, M - 8), M))
+    for t0 in range(0, M, TILE):
+        t1 = min(t0 + TILE, M)
+        s |= {t0, t1 - 1}
+        s |= set(random.Random(seed * 100003 + t0).sample(range(t0, t1), min(per_tile, t1 - t0)))
+    for p in boundaries:
+        if p > 8:
+            for b in range(p, M, p):
+                s |= {b - 1, b}
+    return torch.tensor(sorted(s))
+
+
+def tail_from(rows, M):
+    """index into the sorted row set `rows` of the first row of the last partial tile (of the last tile if M is a multiple of 256)"""
+    t0 = (M - 1) // TILE * TILE
+    return int((rows < t0).sum())
+
+
+def judge(got, truth, var=None, rows_from=None):
+    """the judging function of the forward sweeps: (rel-L2, worst row, worst row of the tail) of `got` against the fp64 truth and their bounds -
+    max(1.5 x the rounding-point variant's own figure, 2^-9) where a variant is given (bf16 outputs), else the fp32 twins' 1e-5 / 1e-4 / 1e-4.
+    -> (figures, bounds, ok)"""
+    k = err(got, truth, rows_from=rows_from)
+    b = (F32_TOTAL, F32_ROW, F32_ROW) if var is None else tuple(max(1.5 * e, FLOOR) for e in err(var, truth, rows_from=rows_from))
+    return k, b, all(x <= y for x, y in zip(k, b))
+
+
+def gemm_path(c, ncu, force=0, workspace=True):
+    """launch<EPI> / splitk_plan of csrc/gemm.hip restated: which kernel a descriptor without a LoRA segment runs on a chip of `ncu` CUs under
+    UG_GEMM_FORCE_TILE = force, with or without the caller's workspace -> (tile, rounds of the persistent walk, K-slices of the split-K tail
+    (1: none), tail tiles padded to 8, wide16 bits: 1 = 16-byte epilogue accesses, 2 = one row map per tile). The 128^2 kernel: (128, 1, 1, 0, 0).
+    c: M, N, K, epilogue, groups, a_map, c_map, r_map, lda, ldw, ldc, ldr, c_gstride, r_gstride, c_off / r_off (elements the C / R base sits
+    off a 16-byte boundary, x 2 bytes)."""
+    M, N, K, epi, groups = c["M"], c["N"], c["K"], c["epilogue"], max(c.get("groups", 1), 1)
+    cdiv = lambda x, y: (x + y - 1) // y
+    t256, t128 = cdiv(M, 256) * cdiv(N, 256) * groups, cdiv(M, 128) * cdiv(N, 128) * groups
+    nkt = K // 64
+
+    def plan(tiles):
+        rem = tiles % ncu
+        if rem == 0 or rem * 2 > ncu or not workspace or nkt < 96:
+            return 0, 1
+        rem8 = (rem + 7) // 8 * 8
+        cand = min(ncu // rem8, 8, nkt // 4)
+        if cand < 2 or rem8 * cand > 256:             # ug_gemm_workspace_bytes(): 4096 + 256 slabs of 256^2 fp32
+            return 0, 1
+        return rem8, cand
+
+    big = M >= 192 and N >= 192 and t256 / (cdiv(t256, 256) * 256) >= 0.6 * t128 / (cdiv(t128, 512) * 512)
+    if not big and epi != EPI_F32 and M >= 192 and N >= 192 and t256 < ncu:
+        nsl = plan(t256)[1]
+        if nsl > 1:
+            t_split = 1.53 * nkt / nsl + 22.0 + 2.5 * nsl
+            t_128 = cdiv(t128, 2 * ncu) * nkt * (0.97 if t128 <= ncu else 1.27)
+            big = t_split < 0.9 * t_128
+    if force == 128:
+        big = False
+    if force == 256:
+        big = True
+    a_rpb, a_bs = c.get("a_map", (0, 0))
+    lda, ldw = c.get("lda") or K, c.get("ldw") or K
+    if a_rpb > 0 and a_bs < a_rpb:
+        big = False
+    jumps = cdiv(255, a_rpb) if a_rpb > 0 else 0
+    a_jump = (a_bs - a_rpb) * jumps if a_rpb > 0 and a_bs > a_rpb else 0
+    if ((255 + a_jump) * lda + K) * 2 + 256 >= 1 << 31 or (255 * ldw + K) * 2 + 256 >= 1 << 31:
+        big = False
+    if not big:
+        return 128, 1, 1, 0, 0
+    res = epi in (EPI_RES_GATE, EPI_RES_SCALE)
+    ldc, ldr = c.get("ldc") or N, c.get("ldr") or N
+    wide = N % 8 == 0 and ldc % 8 == 0 and c.get("c_gstride", 0) % 8 == 0 and c.get("c_off", 0) % 8 == 0 and \
+        (not res or (ldr % 8 == 0 and c.get("r_gstride", 0) % 8 == 0 and c.get("r_off", 0) % 8 == 0))
+    contig = c.get("c_map", (0, 0))[0] % 256 == 0 and (not res or c.get("r_map", (0, 0))[0] % 256 == 0)
+    rem8, nsl = plan(t256)
+    return 256, cdiv(t256, ncu), nsl, rem8, int(wide) | (2 if contig else 0)
+
+
+# ---- AdaLN modulate ----
+def adaln_modulate(x, shift, scale, *, rows, D, rows_per_sample, mod_ld, ldx=None, x_map=(0, 0), eps=1e-6, rnd=bf16):
+    """ug_adaln_modulate: out[r] = LayerNorm(x[map(r)][:D]; eps, biased variance, no affine) (1 + scale[r // rows_per_sample]) +
+    shift[r // rows_per_sample]; x, shift, scale flat buffers (modulation row b at b * mod_ld). Returns (exact, variant) [rows, D]; the variant
+    rounds bf16(LN), bf16(1 + scale), bf16(n s1), then + shift rounded by the store."""
+    r = torch.arange(rows)
+    X = _flat_rows(x, rowmap(r, *x_map) * (ldx or D), D)
+    b = (r // rows_per_sample) * mod_ld
+    sh, sc = _flat_rows(shift, b, D), _flat_rows(scale, b, D)
+    mean = X.mean(-1, keepdim=True)
+    n = (X - mean) * torch.rsqrt(((X - mean) ** 2).mean(-1, keepdim=True) + float(torch.tensor(eps, dtype=torch.float32)))
+    return n * (1.0 + sc) + sh, rnd(rnd(rnd(n) * rnd(1.0 + sc)) + sh)
+
+
+# ---- small linear ----
+def silu(x):
+    return x * torch.sigmoid(x)
+
+
+def small_linear_bf16(x, w, bias, *, M, N, K, act_in=0, residual=None, ldx=None, ldw=None, ldr=None):
+    """ug_small_linear_bf16: out[m][n] = R[m][n] + bf16(sum_k act(x[m][k]) W[n][k] + b[n]) (act_in 1: SiLU). As for the GEMM's v, the exact
+    result rounds nothing - bf16(.) of an fp32 sum is not a function of the operands that a second implementation can reproduce bit for bit.
+    Returns (exact, variant) [M, N]; the variant takes bf16(silu(x)) as the operand, rounds bf16(acc + b), and + R is rounded by the store."""
+    X = _flat_rows(x, torch.arange(M) * (ldx or K), K)
+    W = _flat_rows(w, torch.arange(N) * (ldw or K), K)
+    b = 0.0 if bias is None else _flat_rows(bias, torch.tensor([0]), N)
+    R = None if residual is None else _flat_rows(residual, torch.arange(M) * (ldr or N), N)
+    ex = (silu(X) if act_in else X) @ W.t() + b
+    va = bf16((bf16(silu(X)) if act_in else X) @ W.t() + b)
+    if R is not None:
+        ex, va = ex + R, bf16(va + R)
+    return ex, va

@@ -300,3 +300,284 @@ def test_qk_rope_fusable_defaults_describe_an_identity_launch(monkeypatch):
     assert ops.qk_rope_fusable(4 * 4608, 7 * 3072, 2 * 3072, 128, BF) == ops.qk_rope_fusable(4 * 4608, 7 * 3072, 2 * 3072, 128, BF, c_rpb=0, rope_rpb=0)
     assert not ops.qk_rope_fusable(4 * 4032, 3 * 3072, 2 * 3072, 128, BF, c_rpb=4032)
     assert not ops.qk_rope_fusable(32 * 128, 3 * 1536, 2 * 1536, 64, BF, rope_rpb=128)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the base GEMM, AdaLN modulate and small linear references (tests/test_fuzz_gemm_gpu.py): pins, the path table, sensitivity
+# ----------------------------------------------------------------------------------------------------------------------------------
+from tests import test_fuzz_gemm_gpu as TG  # noqa: E402  (data and helpers only; nothing in it touches a GPU at import)
+
+CPU = torch.device("cpu")
+
+
+def _logical(c, o, g=0):
+    """logical operands of group g of a case, by plain loops / slices (independent of fwd_ref's index arithmetic)"""
+    M, N, K = c["M"], c["N"], c["K"]
+    m = torch.arange(M)
+    A = _gather(o["a"][g * c["a_gstride"]:][:c["a_rows"] * c["lda"]].view(-1, c["lda"]).to(F64), m, *c["a_map"])[:, :K]
+    W = o["w"][g * c["w_gstride"]:][:N * c["ldw"]].view(N, c["ldw"])[:, :K].to(F64)
+    b = None if o["bias"] is None else o["bias"][g * c["bias_gstride"]:][:N].to(F64)
+    R = G = None
+    if c["epilogue"] in (FR.EPI_RES_GATE, FR.EPI_RES_SCALE):
+        src = o["c0"][TG.PAD + c["c_off"]:] if c["alias"] else o["r"][c["r_off"]:]
+        R = _gather(src[g * c["r_gstride"]:][:c["c_rows"] * c["ldr"]].view(-1, c["ldr"]).to(F64), m, *c["r_map"])[:, :N]
+    if c["epilogue"] == FR.EPI_RES_GATE:
+        G = o["gate"][g * c["gate_gstride"]:][:c["gate_rows"] * c["gate_ld"]].view(-1, c["gate_ld"])[:, :N].to(F64)[m // c["rows_per_sample"]]
+    return A, W, b, R, G
+
+
+_PIN_CASES = [
+    TG._case("pin res_gate", (0,), 300, 520, 128, FR.EPI_RES_GATE, groups=3, rps=70, a_map=(100, 117), c_map=(100, 104), alias=True, c_off=4),
+    TG._case("pin res_scale", (0,), 150, 260, 64, FR.EPI_RES_SCALE, groups=2, a_map=(50, 0)),
+    TG._case("pin gelu split", (0,), 130, 768, 64, FR.EPI_BIAS_GELU, split=(256, 264), bias=False),
+    TG._case("pin f32", (0,), 77, 36, 192, FR.EPI_F32, groups=2, c_map=(40, 50)),
+]
+
+
+@pytest.mark.parametrize("c", _PIN_CASES, ids=lambda c: c["name"])
+def test_gemm_reference(c):
+    o = TG.gemm_operands(c, 5, CPU)
+    exact, var = TG.gemm_reference(c, o, torch.arange(c["M"]))
+    for g in range(c["groups"]):
+        A, W, b, R, G = _logical(c, o, g)
+        y = F.linear(A, W, b)
+        if c["epilogue"] == FR.EPI_BIAS_GELU:
+            y = torch.cat([y[:, :c["gelu_from_n"]], F.gelu(y[:, c["gelu_from_n"]:], approximate="tanh")], 1)
+        elif c["epilogue"] == FR.EPI_RES_GATE:
+            y = R + R_gate(G, y)
+        elif c["epilogue"] == FR.EPI_RES_SCALE:
+            y = R + float(torch.tensor(0.7, dtype=torch.float32)) * y
+        assert rel(exact[g], y) < TOL
+        assert torch.equal(var[g], exact[g]) if c["epilogue"] == FR.EPI_F32 else torch.equal(var[g], FR.bf16(var[g]))
+    # a subset of rows = the same rows of the whole; the store: logical elements land where gemm_dest says, everything else keeps its value
+    rows = torch.tensor([0, 3, c["M"] // 2, c["M"] - 1])
+    assert torch.equal(TG.gemm_reference(c, o, rows)[0], exact[:, rows])
+    base = o["c0"][TG.PAD + c["c_off"]:]
+    buf = FR.gemm_store(base, var, **c)
+    dest = FR.gemm_dest(torch.arange(c["M"]), **c)
+    prow = [(i // c["c_map"][0]) * c["c_map"][1] + i % c["c_map"][0] if c["c_map"][0] else i for i in range(c["M"])]
+    n = c["N"] - 1
+    assert int(dest[-1, 5, n]) == (c["groups"] - 1) * c["c_gstride"] + prow[5] * c["ldc"] + n + (c["c_shift"] if c["c_shift_from_n"] and n >= c["c_shift_from_n"] else 0)
+    w = torch.zeros(buf.numel(), dtype=torch.bool)
+    w[dest.reshape(-1)] = True
+    assert torch.equal(buf[dest], var) and torch.equal(buf[~w], base.to(F64)[~w]) and int(w.sum()) == dest.numel()
+
+
+def R_gate(G, y):
+    return R._gate(G, y)
+
+
+def test_gemm_path_table_at_256_cus():
+    """every committed case takes the dispatch path it is there for (a dispatcher change that uncovers a path fails here, without a GPU)"""
+    for c in TG.GEMM_CASES:
+        assert FR.gemm_path(c, 256) == c["path"], (c["name"], FR.gemm_path(c, 256))
+        if c["path_nows"]:
+            assert FR.gemm_path(c, 256, workspace=False) == c["path_nows"], c["name"]
+            assert c["path"][2] > 1 and c["path_nows"][2] == 1
+    paths = {c["path"] for c in TG.GEMM_CASES}
+    assert {p[1] for p in paths} >= {1, 2, 3} and {p[4] for p in paths if p[0] == 256} == {1, 2, 3} and {p[0] for p in paths} == {128, 256}
+    wide = next(c for c in TG.GEMM_CASES if c["a_sparse"])
+    assert FR.gemm_path(dict(wide, lda=wide["lda"] - 64), 256)[0] == 256           # just below 2^31 bytes the same shape stays on the 256^2 kernel
+    assert all(FR.gemm_path(c, 256, force=128)[0] == 128 for c in TG.GEMM_CASES)
+
+
+def _reduced(c, **kw):
+    """a reduced copy of a committed case: same epilogue, maps and options at a size whose full fp64 truth is cheap"""
+    args = dict(M=600, N=1032 if c["N"] % 8 == 0 else 1028, K=min(c["K"], 256))
+    args.update(kw)
+    return TG._case(c["name"], c["path"], args["M"], args["N"], args["K"], c["epilogue"], groups=args.get("groups", c["groups"]), bias=c["has_bias"],
+                    rps=args.get("rps", c["rows_per_sample"] and min(c["rows_per_sample"], 100)), a_map=args.get("a_map", (0, 0)),
+                    c_map=args.get("c_map", (0, 0)), alias=c["alias"], split=args.get("split"))
+
+
+def _ratio(slip, exact, var, rows_from):
+    k, b, ok = FR.judge(slip, exact, var=var, rows_from=rows_from)
+    return max((x / y if x == x else float("inf")) for x, y in zip(k, b)), ok
+
+
+def _caught(name, slip, exact, var, rows_from=None, margin=10.0):
+    r, ok = _ratio(slip, exact, var, rows_from)
+    print(f"{name}: {r:.1f} x the bound")
+    assert not ok and r >= margin, (name, r)
+
+
+def test_sensitivity_gemm():
+    by = {c["name"]: c for c in TG.GEMM_CASES}
+    # RES_GATE with sample boundaries inside tiles
+    c = _reduced(by["rounds2 19x17 tiles ragged, rps 100"])
+    o = TG.gemm_operands(c, 1, CPU)
+    m = torch.arange(c["M"])
+    ref = lambda **kw: TG.gemm_reference(dict(c, **kw.pop("case", {})), dict(o, **kw), m)
+    exact, var = ref()
+    rf = FR.tail_from(m, c["M"])
+    last = (m + 1) % c["rows_per_sample"] == 0                       # the last row of each sample takes the next sample's gate row
+    s = var.clone()
+    s[0, last[:-1].nonzero().flatten()] = TG.gemm_reference(c, dict(o, gate=o["gate"][c["gate_ld"]:]), m[:-1][last[:-1]])[1][0]
+    _caught("gate one sample off next to a boundary", s, exact, var, rf)
+    _caught("bias of column n + 1", ref(bias=torch.roll(o["bias"], -1))[1], exact, var, rf)
+    _caught("last K-tile dropped", ref(case=dict(K=c["K"] - 64))[1], exact, var, rf)
+    wv = o["w"].clone().view(c["N"], c["ldw"])
+    wv[:, 64:128] = 0
+    _caught("one K-slice dropped", ref(w=wv.reshape(-1))[1], exact, var, rf)
+    wv[:, 64:128] = 2 * o["w"].view(c["N"], c["ldw"])[:, 64:128]
+    _caught("one K-slice added twice", ref(w=wv.reshape(-1))[1], exact, var, rf)
+    s = var.clone()
+    s[0, -1] = TG.SENT
+    _caught("row M - 1 unwritten", s, exact, var, rf)
+    dest = FR.gemm_dest(m, **c)
+    wmask = torch.zeros(o["c0"].numel() - TG.PAD, dtype=torch.bool)
+    wmask[dest.reshape(-1)] = True
+    one_more = FR.gemm_store(torch.cat([o["c0"][TG.PAD:], o["c0"][:c["ldc"]]]), torch.cat([var, var[:, -1:]], 1), **dict(c, M=c["M"] + 1))
+    assert not bool((one_more[:wmask.numel()][~wmask] == TG.SENT).all()), "row M written: the sentinel check sees it"
+    # a round-2 tile's row replaced by the same row of the tile `CUs` earlier (4 'CUs', tiles in row-major order): judged on all rows, and by
+    # the full-output screen's row check (the form that sees it on a row outside the fp64 sample)
+    s = var.clone()
+    s[0, 300, 0:256] = var[0, 44, 0:256]                             # tile (1, 0) <- tile (0, 0), in-tile row 44
+    _caught("a round-2 row from the tile CUs earlier", s, exact, var, rf)
+    sr = TG.screen(c, o, False)
+    bound = FR.judge(var, exact, var=var, rows_from=rf)[1][1]
+    rows_e = TG._row_err(s[0], sr)
+    assert float(rows_e[300]) >= 10 * bound and float(TG._row_err(var[0], sr).max()) <= bound
+    assert FR.err(TG.screen(c, o, True), exact[0])[0] <= 1e-5
+    # RES_SCALE: alpha dropped
+    c = _reduced(by["tail 8 of 264, res_scale"])
+    o = TG.gemm_operands(c, 2, CPU)
+    exact, var = TG.gemm_reference(c, o, m)
+    _caught("alpha dropped", TG.gemm_reference(dict(c, alpha=1.0), o, m)[1], exact, var, rf)
+    # groups: group g reads group g + 1's weights / gate
+    c = _reduced(by["6 groups on the 256^2 kernel"], M=300, N=520, groups=3, rps=1)
+    o = TG.gemm_operands(c, 3, CPU)
+    m3 = torch.arange(300)
+    exact, var = TG.gemm_reference(c, o, m3)
+    c2 = dict(c, groups=2)
+    _caught("group g reads group g + 1's weights", TG.gemm_reference(c2, dict(o, w=o["w"][c["w_gstride"]:]), m3)[1], exact[:2], var[:2], 256)
+    _caught("group g reads group g + 1's gate", TG.gemm_reference(c2, dict(o, gate=o["gate"][c["gate_gstride"]:]), m3)[1], exact[:2], var[:2], 256)
+    # the column split: the shift applied one tile early
+    c = _reduced(by["tail 14 of 270, column split"], N=1024, split=(512, 264))
+    o = TG.gemm_operands(c, 4, CPU)
+    exact, var = TG.gemm_reference(c, o, m)
+    early = FR.gemm_store(o["c0"][TG.PAD:], var, **dict(c, c_shift_from_n=256))
+    _caught("column shift one tile early", early[FR.gemm_dest(m, **c)], exact, var, rf)
+    _caught("GELU one tile early", TG.gemm_reference(dict(c, gelu_from_n=256), o, m)[1], exact, var, rf)
+    # slips a bf16 bound cannot see (docs/PARITY_TOLERANCES.md names them): both differ from the variant by rounding-boundary flips only
+    A, W, b, _, _ = _logical(c, o)
+    v = A @ W.t() + b
+    pre = torch.where(torch.arange(c["N"])[None] >= 512, FR.bf16(FR.gelu_tanh(v)), FR.bf16(v))
+    print("GELU before the rounding of v: %.2f x the bound (not seen)" % _ratio(pre[None], exact, var, rf)[0])
+    c = _reduced(by["rounds2 19x17 tiles ragged, rps 100"])
+    o = TG.gemm_operands(c, 1, CPU)
+    exact, var = TG.gemm_reference(c, o, m)
+    print("residual added before the rounding: %.2f x the bound (not seen)" % _ratio(FR.bf16(exact), exact, var, rf)[0])
+
+
+def test_screen_share_of_the_variant():
+    """the share of the rounding-point variant's elements more than one bf16 ulp from the screen's rounded result (here torch's CPU fp32 matmul), on
+    sampled rows of every large committed case: the kernel is allowed max(4 x SCREEN_SHARE, 0.1 %)"""
+    worst = 0.0
+    for i, c in enumerate(TG.GEMM_CASES):
+        if not TG._large(c) or c["epilogue"] == FR.EPI_F32:
+            continue
+        small = dict(c, M=min(c["M"], 16 * max(c["rows_per_sample"], 1), 520), N=min(c["N"], 2056 if c["N"] % 8 == 0 else 2052))
+        small = TG._case(c["name"], c["path"], small["M"], small["N"], c["K"], c["epilogue"], bias=c["has_bias"], rps=c["rows_per_sample"],
+                         a_map=c["a_map"] if c["a_map"][0] <= 100 else (0, 0), alias=c["alias"],
+                         split=(1024, c["c_shift"]) if c["c_shift"] else None)
+        o = TG.gemm_operands(small, 7000 + i, CPU)
+        rows = FR.sample_rows(small["M"], boundaries=(small["rows_per_sample"],), seed=i, per_tile=4)[:24]
+        var = TG.gemm_reference(small, o, rows)[1][0]
+        share = float(TG._ulp_far(var.float(), TG.screen(small, o, False)[rows]).float().mean())
+        worst = max(worst, share)
+        print(f"{c['name']}: {share:.2e}")
+    print(f"worst share {worst:.2e}; committed SCREEN_SHARE {TG.SCREEN_SHARE:.2e}; the kernel's allowance {TG.SHARE_BOUND:.2e}")
+    assert worst <= TG.SCREEN_SHARE
+
+
+# ---- AdaLN modulate ----
+def test_adaln_modulate_reference():
+    for i, case in enumerate(TG.ADALN_CASES):
+        D, rows, rps, xmap, ex, eo, m1 = case
+        if rows > 200:
+            continue
+        xb, mod, const = TG.adaln_data(case, 9000 + i, BF16)
+        exact, var = FR.adaln_modulate(xb, mod, mod.reshape(-1)[D:], **TG._adaln_kw(case))
+        x = _gather(xb, torch.arange(rows), *xmap)[:, :D]
+        b = torch.arange(rows) // rps
+        y = F.layer_norm(x, (D,), None, None, float(torch.tensor(1e-6, dtype=torch.float32))) * (1 + mod[b, D:2 * D]) + mod[b, :D]
+        assert rel(exact, y) < TOL, case
+        assert torch.equal(exact[const], mod[b, :D][const]) and torch.equal(var[const], mod[b, :D][const])
+        if rps > 1 and xmap[0] == 0:           # the oracle's per-sample form (AdaLayerNormZero / _mod)
+            n = rows // rps * rps
+            yo = R._mod(R.layer_norm(x[:n].view(-1, rps, D), eps=float(torch.tensor(1e-6, dtype=torch.float32))), mod[:n // rps, D:2 * D], mod[:n // rps, :D])
+            assert rel(exact[:n], yo.reshape(n, D)) < TOL
+        ob = R._mod(R.layer_norm(x.to(BF16)[:, None]), mod[b, D:2 * D].to(BF16)[:, None], mod[b, :D].to(BF16)[:, None])[:, 0].to(F64)   # bf16 eager rounding points
+        assert float((var != ob).to(F64).mean()) < 0.05, (case, float((var != ob).to(F64).mean()))
+
+
+BF16 = torch.bfloat16
+
+
+def test_adaln_fp32_layer_norm_boundary():
+    """torch's own fp32 F.layer_norm against fp64 on the sweep's rows: it stays inside the twins' 1e-5 / 1e-4 at every row mean of the sweep (up to
+    ADALN_TWIN_MAX_MEAN standard deviations), so the twin is held to them on all of ADALN_MEANS; the figures per mean are printed."""
+    assert max(TG.ADALN_MEANS) <= TG.ADALN_TWIN_MAX_MEAN
+    for D in (64, 1536, 4096):
+        g = _g(D)
+        for mean in TG.ADALN_MEANS + (256.0, 1024.0):
+            x = ((torch.randn(256, D, generator=g, dtype=F64) + mean) * 3.0).float()
+            k = FR.err(F.layer_norm(x, (D,), None, None, 1e-6), F.layer_norm(x.to(F64), (D,), None, None, 1e-6))
+            print(f"F.layer_norm fp32, D {D}, mean {mean:g} sd: rel-L2 {k[0]:.2e} worst row {k[1]:.2e}")
+            if mean <= TG.ADALN_TWIN_MAX_MEAN:
+                assert k[0] <= FR.F32_TOTAL and k[1] <= FR.F32_ROW, (D, mean, k)
+
+
+def test_sensitivity_adaln():
+    case = (200, 130, 50, (65, 70), 0, 8, False)
+    D, rows, rps = case[:3]
+    xb, mod, const = TG.adaln_data(case, 1, BF16)
+    kw = TG._adaln_kw(case)
+    exact, var = FR.adaln_modulate(xb, mod, mod.reshape(-1)[D:], **kw)
+    rf = (rows - 1) // 4 * 4
+    _caught("shift / scale swapped", FR.adaln_modulate(xb, mod.reshape(-1)[D:], mod, **kw)[1], exact, var, rf)
+    _caught("another sample's modulation row", FR.adaln_modulate(xb, mod.reshape(-1)[kw["mod_ld"]:], mod.reshape(-1)[kw["mod_ld"] + D:],
+                                                                 **dict(kw, rows=100))[1], exact[:100], var[:100], 96)
+    # eps dropped: 0 x rsqrt(0) on a constant row is NaN, which fails every comparison
+    x = _gather(xb, torch.arange(rows), *case[3])[:, :D]
+    b = torch.arange(rows) // rps
+    noeps = (x - x.mean(-1, keepdim=True)) * torch.rsqrt(x.var(-1, unbiased=False, keepdim=True)) * (1 + mod[b, D:2 * D]) + mod[b, :D]
+    assert len(const) and noeps[const].isnan().all() and not FR.judge(FR.bf16(noeps), exact, var=var, rows_from=rf)[2]
+    # unbiased variance: 1 / (2 D) relative - below a bf16 bound from D = 64 up (named in the document); the fp32 twin's bounds see it at every D <= 4096
+    for D in (64, 4096):
+        x = torch.randn(16, D, generator=_g(D), dtype=F64)
+        e = F.layer_norm(x, (D,), None, None, 1e-6)
+        u = (x - x.mean(-1, keepdim=True)) * torch.rsqrt(x.var(-1, unbiased=True, keepdim=True) + 1e-6)
+        _caught(f"unbiased variance at D {D} (fp32 twin's bounds)", u, e, None)
+        print("  against a bf16 bound: %.2f x (below the 10 x margin)" % _ratio(FR.bf16(u), e, FR.bf16(e), None)[0])
+
+
+# ---- small linear ----
+def test_small_linear_reference_and_sensitivity():
+    case = (15, 24, 520, True, True, True)
+    M, N, K = case[:3]
+    x, w, b, r = TG.small_linear_data(case, 1)
+    kw = dict(M=M, N=N, K=K, ldx=K + 8, ldw=K + 16, ldr=N + 8)
+    exact, var = FR.small_linear_bf16(x, w, b, act_in=1, residual=r, **kw)
+    assert float(x.abs().max()) == 30.0
+    assert rel(exact, r[:, :N] + F.linear(F.silu(x[:, :K]), w[:, :K], b)) < TOL
+    assert rel(FR.small_linear_bf16(x, w, None, act_in=0, **kw)[0], F.linear(x[:, :K], w[:, :K])) < TOL
+    ob = (r[:, :N].to(BF16) + F.linear(F.silu(x[:, :K].to(BF16)), w[:, :K].to(BF16), b.to(BF16))).to(F64)        # the oracle's bf16 evaluation (adaln_zero's linear)
+    assert float((var != ob).to(F64).mean()) < 0.05
+    _caught("SiLU dropped", FR.small_linear_bf16(x, w, b, act_in=0, residual=r, **kw)[1], exact, var)
+    _caught("the last 8 of K dropped", FR.small_linear_bf16(x, w, b, act_in=1, residual=r, **dict(kw, K=K - 8))[1], exact, var)
+    dup = var.clone()
+    dup[:, N - 2] = var[:, N - 1]
+    _caught("column N - 1 duplicated into N - 2", dup, exact, var)
+    # the same two local slips at the sweep's largest sizes: printed (the per-row bound's margin shrinks as sqrt(8 / K), sqrt(2 / N))
+    case = (3, 1000, 4096, True, True, False)
+    x, w, b, _ = TG.small_linear_data(case, 2)
+    kw = dict(M=3, N=1000, K=4096, ldx=4104, ldw=4112)
+    exact, var = FR.small_linear_bf16(x, w, b, act_in=1, **kw)
+    r1, ok1 = _ratio(FR.small_linear_bf16(x, w, b, act_in=1, **dict(kw, K=4088))[1], exact, var, None)
+    dup = var.clone()
+    dup[:, 998] = var[:, 999]
+    r2, ok2 = _ratio(dup, exact, var, None)
+    print(f"K 4096: last 8 of K dropped {r1:.1f} x; N 1000: duplicated column {r2:.1f} x")
+    assert not ok1 and not ok2
