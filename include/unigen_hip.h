@@ -518,6 +518,35 @@ int ug_grad_scale(const ug_optim_tensor* table, int32_t n_tensors, const int32_t
 int ug_adamw_step(const ug_optim_tensor* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, const ug_adamw_group* groups_host,
                   int32_t n_groups, const float* coef, ug_stream_t stream);
 
+/* ---- flow-matching training objective (csrc/objective.hip; reference train.py:589-613 noisy model input, :644-652 loss). Contiguous tensors;
+ * `void*` tensors are bf16 (fp32 in the `_f32` twins), `float*` ones fp32 in both. 16-byte accesses where the base pointers are 16-byte aligned,
+ * scalar accesses otherwise and on a sample's unaligned head and tail. No atomics: results are bitwise reproducible. ---- */
+enum { UG_FLOW_NONE = 0, UG_FLOW_SIGMA_SQRT = 1, UG_FLOW_COSMAP = 2, UG_FLOW_LOGIT_NORMAL = 3, UG_FLOW_MODE = 4 };   /* args.weighting_scheme */
+
+/* x, noise [B][C][H][W]; u [B] uniform draws in [0, 1); sigma_table [T] (the scheduler's training sigmas, device memory). Per sample
+ *   idx = min((int)(u * T), T - 1)  (clamped: the reference indexes out of range when u * T rounds up to T), s32 = sigma_table[idx],
+ *   timestep = (s32 * T) / 1000  (two fp32 operations: scheduler.timesteps, then :630), sigma = bf16(s32) (s32 in the twin),
+ *   weight (fp32, from that sigma) = 1 | sigma^-2 (UG_FLOW_SIGMA_SQRT) | 2 / (pi (1 - 2 sigma + 2 sigma^2)) (UG_FLOW_COSMAP);
+ * per element
+ *   noisy = bf16(bf16(bf16(1 - sigma) * x) + bf16(sigma * noise))   (no intermediate rounding in the twin),   target = bf16(noise - x).
+ * pack = 1 writes noisy and target in FluxPipeline._pack_latents layout [B][(H/2)(W/2)][4C] (H, W even), pack = 0 in [B][C][H][W]. */
+int ug_flow_noise(const void* x, const void* noise, const float* u, const float* sigma_table, int64_t T, int32_t scheme, int32_t pack, int64_t B,
+                  int64_t C, int64_t H, int64_t W, void* noisy, void* target, float* sigma, float* timestep, float* weight, ug_stream_t stream);
+int ug_flow_noise_f32(const void* x, const void* noise, const float* u, const float* sigma_table, int64_t T, int32_t scheme, int32_t pack, int64_t B,
+                      int64_t C, int64_t H, int64_t W, void* noisy, void* target, float* sigma, float* timestep, float* weight, ug_stream_t stream);
+/* pred, target [B][n], weight [B] -> loss_per_sample[b] = mean_i(weight[b] * (pred - target)^2), loss[0] = mean_b of those; fp32 accumulation in
+ * both forms. Two launches: per-block partial sums into the caller-owned fp32 workspace, then one block that adds them in a fixed order. */
+int64_t ug_flow_loss_workspace_bytes(int64_t B, int64_t n);
+int ug_flow_loss(const void* pred, const void* target, const float* weight, int64_t B, int64_t n, float* loss_per_sample, float* loss,
+                 void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+int ug_flow_loss_f32(const void* pred, const void* target, const float* weight, int64_t B, int64_t n, float* loss_per_sample, float* loss,
+                     void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+/* grad[b][i] = gout[0] * 2 weight[b] (pred - target) / (n B) in pred's dtype, one rounding; gout: autograd's upstream gradient of loss[0], a DEVICE
+ * fp32 scalar. fp32 order of operations: (((gout * 1/B) * 1/n) * weight[b]) * (2 (pred - target)), which is torch autograd's through the eager lines. */
+int ug_flow_loss_bwd(const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad, ug_stream_t stream);
+int ug_flow_loss_bwd_f32(const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad,
+                         ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

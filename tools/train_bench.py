@@ -3,7 +3,10 @@ random weights and inputs: seconds per step, samples/s, peak memory. Not the hea
 SURVEY 8(f) rank-4 row. --optim adds the optimizer step of train.py:658-660 (unigen_amd.optim.AdamW(max_grad_norm=1.0): clipping fused, fp32 masters)
 to each timed step. --lora R trains rank-R LoRA adapters on the attention projections of the control branch instead, everything else frozen
 (HipModule.set_lora_trainable; UniGenFlux only), and also times the same differentiable forward with the adapters switched off.
-usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim] [--lora R]"""
+--objective SCHEME runs every step through unigen_amd.objective.train_step (train.py:589-662: noisy input, timesteps and loss weighting from the
+HIP objective kernels, loss, backward, the --optim optimizer) instead of the inline MSE against a fixed target, times the whole step, and then
+times the objective's own launches (prepare + loss forward / backward, HIP events) beside the torch-eager restatement of the same lines.
+usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim] [--lora R] [--objective SCHEME]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,7 +24,11 @@ ap.add_argument("--no-gradnorm", action="store_true", help="skip the per-step gr
 ap.add_argument("--shapes", action="store_true", help="per-shape table of the last step's GEMM / attention launches (grouped by FLOPs per launch)")
 ap.add_argument("--optim", action="store_true", help="time unigen_amd.optim.AdamW(lr=1e-4, weight_decay=1e-2, max_grad_norm=1.0).step() after each backward")
 ap.add_argument("--lora", type=int, default=0, metavar="R", help="train rank-R adapters on the control branch's attention projections, base and control modules frozen")
+ap.add_argument("--objective", default=None, metavar="SCHEME", help="run the step through unigen_amd.objective.train_step with this weighting scheme (none, sigma_sqrt, cosmap, "
+                "logit_normal, mode); implies --optim (same AdamW, clipping fused into its step)")
 a = ap.parse_args()
+if a.objective:
+    a.optim = True
 if a.lora and a.sd3:
     ap.error("--lora is implemented for UniGenFlux only")
 dev, BF = torch.device("cuda:0"), torch.bfloat16
@@ -44,6 +51,7 @@ if a.sd3:
     t = torch.full((B,), 600.0, device=dev)
     fwd = lambda: model(timestep=t, **inp)
     target = rn(B, 16, hw, hw)
+    latents = rn(B, c.in_channels, hw, hw).to(BF)
 else:
     cfg = {} if a.layers is None else {"num_layers": a.layers[0], "num_single_layers": a.layers[1]}
     model = UniGenFlux.from_config(cfg, device=dev, dtype=BF)
@@ -67,6 +75,7 @@ else:
     t = torch.full((B,), 0.75, device=dev, dtype=BF)
     fwd = lambda: model(timestep=t, img_ids=ids, txt_ids=txt, condition_ids=ids, **inp)
     target = rn(B, N, 64)
+    latents = rn(B, 16, 2 * grid, 2 * grid).to(BF)
 n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
 n_all = sum(p.numel() for p in model.parameters())
 from unigen_amd import ops
@@ -75,6 +84,13 @@ if a.optim:
     from unigen_amd.optim import AdamW
     opt = AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0)
 times, opt_times = [], []
+objective = batch = None
+if a.objective:
+    from unigen_amd.objective import FlowMatchObjective, train_step
+    objective = FlowMatchObjective(a.objective, pack=not a.sd3, shift=3.0 if a.sd3 else 1.0, timestep_scale=1000.0 if a.sd3 else 1.0)
+    batch = dict({k: v for k, v in inp.items() if k != "hidden_states"}, latents=latents)
+    if not a.sd3:
+        batch.update(img_ids=ids, txt_ids=txt, condition_ids=ids)
 timer = None
 if a.lora:                         # the same differentiable forward with every adapter switched off (no adapter launch): what the adapters add to it
     from unigen_amd.lora import enable_lora
@@ -93,6 +109,16 @@ for step in range(a.steps + 1):
         timer = ops.KernelTimer(kinds=("gemm", "attn", "attn_bwd")); ops.set_timer(timer)
     for p in model.parameters():
         p.grad = None
+    if objective is not None:          # the whole of train.py:589-662 in one call; clipping is fused into the optimizer's step (as with --optim alone)
+        from unigen_amd import autograd as A_
+        torch.cuda.synchronize(); t0 = time.time()
+        res = train_step(model, opt, objective, batch, max_grad_norm=None, generator=g)
+        A_.clear_activation_cache()
+        torch.cuda.synchronize(); t1 = time.time()
+        if step and timer is None:
+            times.append((t1 - t0, 0.0)); opt_times.append(0.0)
+        print(f"step {step}: loss {float(res['step_loss']):.5f} grad-norm {float(opt.last_grad_norm):.4e} train_step {t1 - t0:.3f}s", flush=True)
+        continue
     torch.cuda.synchronize(); t0 = time.time()
     out, losses, _ = fwd()
     torch.cuda.synchronize(); t1 = time.time()
@@ -116,7 +142,48 @@ fw, bw = min(x[0] for x in times), min(x[1] for x in times)
 extra = {}
 if opt is not None:
     op = min(opt_times)
-    extra = dict(optimizer_s=round(op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5))
+    extra = dict(optimizer_s=round(op, 4), step_s=round(fw + bw + op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5))
+if objective is not None:              # the step is timed as a whole: forward_s holds it, backward_s / optimizer_s are 0
+    extra.update(objective=a.objective, step_s=round(fw, 4))
+    # the objective's own launches by HIP events, beside the torch-eager restatement of train.py:598-613 and :644-652 (without get_sigmas' host
+    # synchronisation per sample, which eager cannot avoid in the reference: this comparison favours eager)
+    from unigen_amd.pipeline import pack_latents
+    pred = (rn(*((B, 16, a.size // 8, a.size // 8) if a.sd3 else (B, N, 64))).to(BF)).requires_grad_(True)
+    noise, u = torch.randn_like(latents), torch.rand(B, device=dev)
+    table, T_ = objective.sigma_table(dev), objective.num_train_timesteps
+
+    def hip_lines():
+        noisy, tgt, ts, sig, w = objective.prepare(latents, noise=noise, u=u)
+        objective.loss(pred, tgt, w)[0].backward()
+
+    def eager_lines():
+        s32 = table[(u * T_).long().clamp(max=T_ - 1)]
+        ts = s32 * T_ / 1000
+        sig = s32.to(BF).reshape(-1, 1, 1, 1)
+        noisy = (1.0 - sig) * latents + sig * noise
+        tgt = noise - latents
+        if not a.sd3:
+            noisy, tgt = pack_latents(noisy), pack_latents(tgt)
+        weighting = torch.ones_like(sig) if a.objective != "cosmap" else 2 / (3.141592653589793 * (1 - 2 * sig + 2 * sig ** 2))
+        if a.objective == "sigma_sqrt":
+            weighting = (sig ** -2.0).float()
+        flow = torch.mean((weighting.float().reshape(B, *([1] * (pred.dim() - 1))) * (pred.float() - tgt.float()) ** 2).reshape(B, -1), 1)
+        flow.mean().backward()
+
+    def timed(fn, reps=50):
+        for _ in range(5):
+            fn(); pred.grad = None
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(3):
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(reps):
+                fn(); pred.grad = None
+            e1.record(); torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) / reps)
+        return best
+    hip_ms, eager_ms = timed(hip_lines), timed(eager_lines)
+    extra.update(objective_hip_ms=round(hip_ms, 4), objective_eager_ms=round(eager_ms, 4), objective_share_of_step=round(hip_ms * 1e-3 / fw, 6))
 if a.lora:
     extra.update(lora_rank=a.lora, lora_sites=len(model._lora_sites), forward_adapters_off_s=round(min(fw_off[1:]), 3), backward_over_forward=round(bw / fw, 2))
 print("TRAIN_BENCH", json.dumps(dict(**extra, model="UniGenSD3" if a.sd3 else "UniGenFlux", batch=B, size=a.size, layers=[model.config.num_layers, getattr(model.config, "num_single_layers", 0)], checkpointing=bool(a.ckpt),

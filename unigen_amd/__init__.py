@@ -3,3 +3,14 @@
 Layout: csrc/ (HIP kernels + C ABI -> libunigen_hip.so), lib.py (ctypes binding), ops.py (tensor front end),
 flux.py (UniGenFlux / MultiCondtionUniGenFlux host engine), pipeline.py (denoise loop / UniGenFLUXPipeline surface)."""
 __version__ = "0.1.0"
+
+# the training surface, imported on first use (importing the package itself needs neither torch nor the HIP library)
+_LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training_sigmas": "objective", "sample_density": "objective"}
+__all__ = sorted(_LAZY)
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module(f".{_LAZY[name]}", __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -145,7 +145,16 @@ SIGNATURES.update({
     "ug_lora_wgrad_bf16": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64, vp]),
     "ug_lora_wgrad_workspace_bytes": (i64, [i64, i64, i64]),
 })
-_F32_TWINS = {"ug_lora_wgrad_f32": "ug_lora_wgrad_bf16", "ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",
+# flow-matching training objective (csrc/objective.hip)
+UG_FLOW_NONE, UG_FLOW_SIGMA_SQRT, UG_FLOW_COSMAP, UG_FLOW_LOGIT_NORMAL, UG_FLOW_MODE = 0, 1, 2, 3, 4
+SIGNATURES.update({
+    "ug_flow_noise": (i32, [vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "ug_flow_loss_workspace_bytes": (i64, [i64, i64]),
+    "ug_flow_loss": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
+    "ug_flow_loss_bwd": (i32, [vp, vp, vp, vp, i64, i64, vp, vp]),
+})
+_F32_TWINS = {"ug_flow_noise_f32": "ug_flow_noise", "ug_flow_loss_f32": "ug_flow_loss", "ug_flow_loss_bwd_f32": "ug_flow_loss_bwd",
+              "ug_lora_wgrad_f32": "ug_lora_wgrad_bf16","ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",
               "ug_adaln_modulate_bwd_f32": "ug_adaln_modulate_bwd", "ug_qk_rmsnorm_rope_bwd_f32": "ug_qk_rmsnorm_rope_bwd",
               "ug_attn_prob_f32": "ug_attn_prob", "ug_attn_dscore_f32": "ug_attn_dscore", "ug_rowdot_f32": "ug_rowdot",
               "ug_gemm_f32": "ug_gemm_bf16", "ug_small_linear_f32": "ug_small_linear_bf16", "ug_adaln_modulate_f32": "ug_adaln_modulate",

@@ -784,3 +784,70 @@ def gate_residual(x: Optional[torch.Tensor], a: torch.Tensor, gate: torch.Tensor
     L.check(_fn("ug_gate_residual", dt)(_p(x), x.stride(0) if x is not None else 0, a.data_ptr(), a.stride(0), gate.data_ptr(), gate.stride(0), rows_per_sample,
                                         y.data_ptr(), D, rows, D, _stream()), "ug_gate_residual")
     return y
+
+
+FLOW_SCHEMES = {"none": L.UG_FLOW_NONE, "sigma_sqrt": L.UG_FLOW_SIGMA_SQRT, "cosmap": L.UG_FLOW_COSMAP, "logit_normal": L.UG_FLOW_LOGIT_NORMAL,
+                "mode": L.UG_FLOW_MODE}
+
+
+def _chk_f32_vec(t: torch.Tensor, name: str, n: int) -> None:
+    _chk(t, name, f32)
+    if t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: expected {n} contiguous fp32 values, got {tuple(t.shape)}")
+
+
+def flow_noise(x: torch.Tensor, noise: torch.Tensor, u: torch.Tensor, sigma_table: torch.Tensor, *, scheme: str = "none", pack: bool = True):
+    """x, noise [B, C, H, W]; u [B] fp32 draws in [0, 1); sigma_table [T] fp32 -> noisy, target (x's dtype; [B, (H/2)(W/2), 4C] when `pack`, else
+    x's shape), sigma, timestep, weight ([B] fp32): train.py:598-613 and the loss weighting of :644 in one launch (ug_flow_noise / _f32)."""
+    dt = _act(x, "x")
+    if x.dim() != 4 or noise.shape != x.shape:
+        raise ValueError(f"flow_noise: x and noise must share a [B, C, H, W] shape, got {tuple(x.shape)} and {tuple(noise.shape)}")
+    if scheme not in FLOW_SCHEMES:
+        raise ValueError(f"flow_noise: unknown weighting scheme {scheme!r} (one of {sorted(FLOW_SCHEMES)})")
+    _chk(noise, "noise", dt)
+    B, Cc, H, W = x.shape
+    _chk_f32_vec(u, "u", B)
+    _chk(sigma_table, "sigma_table", f32)
+    if sigma_table.dim() != 1 or not sigma_table.is_contiguous():
+        raise ValueError("flow_noise: sigma_table must be a contiguous 1-d tensor")
+    x, noise = x.contiguous(), noise.contiguous()
+    shape = (B, (H // 2) * (W // 2), Cc * 4) if pack else (B, Cc, H, W)
+    noisy, target = torch.empty(shape, device=x.device, dtype=dt), torch.empty(shape, device=x.device, dtype=dt)
+    svw = torch.empty(3, B, device=x.device, dtype=f32)
+    L.check(_fn("ug_flow_noise", dt)(x.data_ptr(), noise.data_ptr(), u.data_ptr(), sigma_table.data_ptr(), sigma_table.numel(), FLOW_SCHEMES[scheme],
+                                     1 if pack else 0, B, Cc, H, W, noisy.data_ptr(), target.data_ptr(), svw[0].data_ptr(), svw[1].data_ptr(),
+                                     svw[2].data_ptr(), _stream()), "ug_flow_noise")
+    return noisy, target, svw[0], svw[1], svw[2]
+
+
+def _flow_pair(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, who: str):
+    dt = _act(pred, "pred")
+    _chk(target, "target", dt)
+    if pred.dim() < 2 or pred.shape != target.shape:
+        raise ValueError(f"{who}: pred and target must share a [B, ...] shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    B = pred.shape[0]
+    _chk_f32_vec(weight, "weight", B)
+    return dt, B, pred.numel() // B, pred.contiguous(), target.contiguous()
+
+
+def flow_loss(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+    """pred, target [B, ...]; weight [B] fp32 -> (loss_per_sample [B], loss []) fp32: mean over a sample of weight * (pred - target)^2 and the mean of
+    those over the batch (train.py:648-652), fp32 accumulation, bit-identical run to run. `workspace`: >= ug_flow_loss_workspace_bytes(B, n) bytes."""
+    dt, B, n, pred, target = _flow_pair(pred, target, weight, "flow_loss")
+    nbytes = int(L.load().ug_flow_loss_workspace_bytes(B, n))
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+    per_sample, loss = torch.empty(B, device=pred.device, dtype=f32), torch.empty((), device=pred.device, dtype=f32)
+    L.check(_fn("ug_flow_loss", dt)(pred.data_ptr(), target.data_ptr(), weight.data_ptr(), B, n, per_sample.data_ptr(), loss.data_ptr(), workspace.data_ptr(),
+                                    workspace.numel() * workspace.element_size(), _stream()), "ug_flow_loss")
+    return per_sample, loss
+
+
+def flow_loss_bwd(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, gout: torch.Tensor) -> torch.Tensor:
+    """d loss / d pred of flow_loss, scaled by the device fp32 scalar `gout` (read by the kernel: no host copy), in pred's dtype and shape."""
+    dt, B, n, pred, target = _flow_pair(pred, target, weight, "flow_loss_bwd")
+    _chk_f32_vec(gout, "gout", 1)
+    grad = torch.empty_like(pred)
+    L.check(_fn("ug_flow_loss_bwd", dt)(pred.data_ptr(), target.data_ptr(), weight.data_ptr(), gout.data_ptr(), B, n, grad.data_ptr(), _stream()),
+            "ug_flow_loss_bwd")
+    return grad
