@@ -547,6 +547,48 @@ int ug_flow_loss_bwd(const void* pred, const void* target, const float* weight, 
 int ug_flow_loss_bwd_f32(const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad,
                          ug_stream_t stream);
 
+/* ---- text encoders (csrc/text.hip; unigen_amd/text.py: T5EncoderModel, CLIPTextModel - the reference runs transformers' modules at train.py:381-395,
+ * :523-569 and at the top of every pipeline call through src/text_encoder.py). Their matrix work is ug_gemm_bf16, the embedding ug_gather_rows. ---- */
+/* ug_flash_attn_fwd with, before the softmax, an additive bias of the relative position and / or a causal mask:
+ *   s_qk = softmax_scale * q.k + (rel_table ? rel_table[h][(k - q) + rel_len - 1] : 0);   causal != 0: keys k > q get probability 0.
+ * rel_table: fp32 [heads][2 * rel_len - 1] (ug_t5_rel_table), rel_len >= max(Lq, Lkv) and <= 4096: a head's slice is loaded into LDS once per
+ * workgroup; no [heads][Lq][Lkv] tensor exists anywhere. T5 passes softmax_scale = 1 (T5Attention does not scale), CLIP dh^-0.5 with causal = 1 and no
+ * table. dh = 64 with a table or a mask; with neither the call IS ug_flash_attn_fwd (same kernel, same bits). */
+int ug_flash_attn_fwd_bias(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                           const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                           const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                           void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                           int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                           float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream);
+int ug_flash_attn_fwd_bias_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                               const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                               const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                               void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                               int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                               float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream);
+/* table[h][j] = weight[bucket(j - (L - 1))][h] for j in [0, 2L - 1): T5Attention.compute_bias as a function of k - q alone. weight: block 0's
+ * relative_attention_bias.weight [num_buckets][heads] (bf16; fp32 in the twin), table fp32 in both. bucket(): T5's bidirectional rule - the upper half of
+ * the buckets for k > q; within a half, distances n < max_exact = num_buckets / 4 have their own bucket, larger ones
+ * min(max_exact + (int)(log(n / max_exact) / log(max_distance / max_exact) * (num_buckets / 2 - max_exact)), num_buckets / 2 - 1), in fp32. */
+int ug_t5_rel_table(const void* weight, int32_t num_buckets, int32_t max_distance, int32_t heads, int64_t L, float* table, ug_stream_t stream);
+int ug_t5_rel_table_f32(const void* weight, int32_t num_buckets, int32_t max_distance, int32_t heads, int64_t L, float* table, ug_stream_t stream);
+/* T5LayerNorm: out = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))), statistics in fp32, no mean subtraction, the module's two rounding points (none in the
+ * twin). Rows of any width D that is a multiple of 8, 16-byte aligned; one pass over the row up to D = 4608. */
+int ug_rmsnorm_rows(const void* x, int64_t ldx, const void* w, void* out, int64_t ldo, int64_t rows, int64_t D, float eps, ug_stream_t stream);
+int ug_rmsnorm_rows_f32(const void* x, int64_t ldx, const void* w, void* out, int64_t ldo, int64_t rows, int64_t D, float eps, ug_stream_t stream);
+/* nn.LayerNorm with weight and bias: out = bf16((x - mean) * rsqrt(var + eps) * w + b), var = mean((x - mean)^2), fp32 arithmetic, one rounding. */
+int ug_layernorm_rows(const void* x, int64_t ldx, const void* w, const void* bias, void* out, int64_t ldo, int64_t rows, int64_t D, float eps,
+                      ug_stream_t stream);
+int ug_layernorm_rows_f32(const void* x, int64_t ldx, const void* w, const void* bias, void* out, int64_t ldo, int64_t rows, int64_t D, float eps,
+                          ug_stream_t stream);
+/* out[m][n] = bf16( bf16(gelu_new(ab[m][n])) * ab[m][F + n] ), n < F: T5DenseGatedActDense between wi_0 | wi_1 (one GEMM over the stacked weight writes
+ * ab [M][2F]) and wo. gelu_new(x) = 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))). F a multiple of 8. */
+int ug_gated_gelu(const void* ab, int64_t ld, void* out, int64_t ldo, int64_t M, int64_t F, ug_stream_t stream);
+int ug_gated_gelu_f32(const void* ab, int64_t ld, void* out, int64_t ldo, int64_t M, int64_t F, ug_stream_t stream);
+/* y = x * sigmoid(1.702 x): CLIP-L's hidden_act "quick_gelu". n contiguous elements, a multiple of 8; y may alias x. */
+int ug_quick_gelu(const void* x, void* y, int64_t n, ug_stream_t stream);
+int ug_quick_gelu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

@@ -851,3 +851,81 @@ def flow_loss_bwd(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor
     L.check(_fn("ug_flow_loss_bwd", dt)(pred.data_ptr(), target.data_ptr(), weight.data_ptr(), gout.data_ptr(), B, n, grad.data_ptr(), _stream()),
             "ug_flow_loss_bwd")
     return grad
+
+
+# ---- text encoders (csrc/text.hip) ----------------------------------------------------------------------------------------------------
+def flash_attn_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batches: int, heads: int, dh: int, Lq: int, Lkv: int,
+                    q_strides, k_strides, v_strides, o_strides, scale: float, rel_table: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """flash_attn with an additive relative-position bias (rel_table fp32 [heads, 2 * rel_len - 1], indexed by k - q) and / or a causal mask."""
+    dt = _act(q, "q")
+    _chk(k, "k", dt); _chk(v, "v", dt); _chk(out, "out", dt)
+    rel_len = 0
+    if rel_table is not None:
+        _chk(rel_table, "rel_table", torch.float32)
+        if rel_table.dim() != 2 or rel_table.shape[0] != heads or rel_table.shape[1] % 2 != 1 or not rel_table.is_contiguous():
+            raise ValueError(f"rel_table: expected a contiguous [heads = {heads}, 2 * rel_len - 1] table, got {tuple(rel_table.shape)}")
+        rel_len = (rel_table.shape[1] + 1) // 2
+    ev = _timer.begin("attn") if _timer is not None else None
+    L.check(_fn("ug_flash_attn_fwd_bias", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+                                            v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, _p(rel_table),
+                                            rel_len, 1 if causal else 0, _stream()), "ug_flash_attn_fwd_bias")
+    if ev is not None:
+        _timer.end("attn", 4.0 * batches * heads * Lq * Lkv * dh * (0.5 if causal else 1.0), ev, tag=(batches, heads, Lq, Lkv, dh))
+    return out
+
+
+def t5_rel_table(weight: torch.Tensor, L_: int, *, num_buckets: int, max_distance: int) -> torch.Tensor:
+    """fp32 [heads, 2L - 1]: T5's relative-position bias as a function of k - q, from relative_attention_bias.weight [num_buckets, heads]."""
+    dt = _act(weight, "weight")
+    if weight.dim() != 2 or weight.shape[0] != num_buckets or not weight.is_contiguous():
+        raise ValueError(f"weight: expected a contiguous [num_buckets = {num_buckets}, heads] tensor, got {tuple(weight.shape)}")
+    heads = weight.shape[1]
+    table = torch.empty(heads, 2 * L_ - 1, dtype=torch.float32, device=weight.device)
+    L.check(_fn("ug_t5_rel_table", dt)(weight.data_ptr(), num_buckets, max_distance, heads, L_, table.data_ptr(), _stream()), "ug_t5_rel_table")
+    return table
+
+
+def rmsnorm_rows(x: torch.Tensor, w: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T5LayerNorm over the last dimension of x [rows, D]."""
+    dt = _act(x, "x")
+    _chk(w, "w", dt)
+    rows, D = x.shape
+    out = torch.empty(rows, D, dtype=dt, device=x.device) if out is None else out
+    _chk(out, "out", dt)
+    assert w.numel() == D and out.shape == x.shape
+    L.check(_fn("ug_rmsnorm_rows", dt)(x.data_ptr(), x.stride(0), w.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream()), "ug_rmsnorm_rows")
+    return out
+
+
+def layernorm_rows(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.LayerNorm (weight and bias) over the last dimension of x [rows, D]."""
+    dt = _act(x, "x")
+    _chk(w, "w", dt); _chk(b, "b", dt)
+    rows, D = x.shape
+    out = torch.empty(rows, D, dtype=dt, device=x.device) if out is None else out
+    _chk(out, "out", dt)
+    assert w.numel() == D and b.numel() == D and out.shape == x.shape
+    L.check(_fn("ug_layernorm_rows", dt)(x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream()),
+            "ug_layernorm_rows")
+    return out
+
+
+def gated_gelu(ab: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m, n] = gelu_new(ab[m, n]) * ab[m, F + n]; ab [M, 2F]."""
+    dt = _act(ab, "ab")
+    M, F2 = ab.shape
+    out = torch.empty(M, F2 // 2, dtype=dt, device=ab.device) if out is None else out
+    _chk(out, "out", dt)
+    assert F2 % 2 == 0 and out.shape == (M, F2 // 2)
+    L.check(_fn("ug_gated_gelu", dt)(ab.data_ptr(), ab.stride(0), out.data_ptr(), out.stride(0), M, F2 // 2, _stream()), "ug_gated_gelu")
+    return out
+
+
+def quick_gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x * sigmoid(1.702 x), contiguous; out may be x itself."""
+    dt = _act(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "out", dt)
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
+    L.check(_fn("ug_quick_gelu", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_quick_gelu")
+    return out

@@ -156,10 +156,13 @@ class UniGenFLUXPipeline:
     delegated to attributes the caller attaches (`encode_prompt`, `vae`, `image_processor`), with the reference's keyword arguments."""
 
     def __init__(self, transformer=None, scheduler_config: Optional[dict] = None, vae_scale_factor: int = 8, encode_prompt=None, vae=None,
-                 image_processor=None):
+                 image_processor=None, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None):
         self.transformer = transformer
         self.vae_scale_factor = vae_scale_factor
         self.default_sample_size = 128
+        # native text encoders (unigen_amd.text: CLIPTextModel, T5EncoderModel), used when no `encode_prompt` callable is attached; without
+        # tokenizers a prompt is the pair (CLIP token ids [B, 77], T5 token ids [B, L])
+        self.text_encoder, self.text_encoder_2, self.tokenizer, self.tokenizer_2 = text_encoder, text_encoder_2, tokenizer, tokenizer_2
         sc = dict(shift=1.0, use_dynamic_shifting=False, base_image_seq_len=256, max_image_seq_len=4096, base_shift=0.5, max_shift=1.15)
         sc.update(scheduler_config or {})
         self.scheduler = SimpleNamespace(config=sc)
@@ -185,7 +188,8 @@ class UniGenFLUXPipeline:
                 from .vae import AutoencoderKL
                 vae = AutoencoderKL.from_pretrained(os.path.join(root, "vae"))
         return cls(transformer=transformer, scheduler_config=sc, encode_prompt=kwargs.get("encode_prompt"), vae=vae,
-                   image_processor=kwargs.get("image_processor"))
+                   image_processor=kwargs.get("image_processor"), text_encoder=kwargs.get("text_encoder"), text_encoder_2=kwargs.get("text_encoder_2"),
+                   tokenizer=kwargs.get("tokenizer"), tokenizer_2=kwargs.get("tokenizer_2"))
 
     def to(self, device=None, dtype=None):
         if device is not None:
@@ -203,9 +207,22 @@ class UniGenFLUXPipeline:
         """self.encode_prompt(...) with the reference's kwargs (src/UniGenPipeline.py:575-619). Pre-computed embeds pass through."""
         if prompt is None:
             return prompt_embeds, pooled_prompt_embeds
+        if self.encode_prompt is None and self.text_encoder is not None and self.text_encoder_2 is not None:
+            from .text import encode_prompt
+            encoders = [self.text_encoder, self.text_encoder_2]
+            if self.tokenizer is not None and self.tokenizer_2 is not None:
+                out = encode_prompt(encoders, [self.tokenizer, self.tokenizer_2], prompt, max_sequence_length, device=device,
+                                    num_images_per_prompt=num_images_per_prompt)
+            else:
+                if not (isinstance(prompt, (list, tuple)) and len(prompt) == 2 and all(isinstance(t, torch.Tensor) for t in prompt)):
+                    raise TypeError(f"`{what}`: no tokenizers are attached, so it must be the pair (CLIP token ids [B, 77], T5 token ids [B, L])")
+                out = encode_prompt(encoders, [None, None], None, max_sequence_length, device=device, num_images_per_prompt=num_images_per_prompt,
+                                    text_input_ids_list=list(prompt))
+            return out[0], out[1]
         if self.encode_prompt is None:
             raise NotImplementedError(f"`{what}` given as text but no text encoder is attached: set `pipe.encode_prompt` to a callable with "
-                                      "FluxPipeline.encode_prompt's signature (CLIP/T5 are outside this package), or pass the embeds")
+                                      "FluxPipeline.encode_prompt's signature, attach `pipe.text_encoder` (CLIPTextModel) and `pipe.text_encoder_2` "
+                                      "(T5EncoderModel) of unigen_amd.text, or pass the embeds")
         out = self.encode_prompt(prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
                                  num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length, lora_scale=None)
         return out[0], out[1]
