@@ -589,6 +589,50 @@ int ug_gated_gelu_f32(const void* ab, int64_t ld, void* out, int64_t ldo, int64_
 int ug_quick_gelu(const void* x, void* y, int64_t n, ug_stream_t stream);
 int ug_quick_gelu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
 
+/* ---- image front end (csrc/image.hip; unigen_amd/image.py: VaeImageProcessor, canny; unigen_amd/condition.py - the reference builds its canny
+ * condition with cv2.Canny(img, 100, 200) in src/condition.py:63-67 and sends every image through diffusers' VaeImageProcessor). Integer or exactly
+ * specified fp32 arithmetic: one right answer per element. Images are uint8 NHWC [B, H, W, C]; `bstride` / `rstride` are the BYTE distances between
+ * samples and between rows, the pixels of a row are contiguous. B, H < 65536. No alignment is required; aligned bases and strides take the wide paths.
+ * No fp32 twins: nothing here rounds. ---- */
+/* Stage 1 of Canny: 3x3 Sobel in x and y with replicated borders and the L1 magnitude |dx| + |dy|, contiguous [B, H, W] each. C is 1 or 3; with 3
+ * channels the channel with the largest magnitude supplies all three values, the first one on a tie. */
+int ug_canny_grad(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int16_t* dx, int16_t* dy,
+                  int32_t* mag, ug_stream_t stream);
+/* Stage 2: non-maximum suppression and the double threshold of cv::Canny with L2gradient = false (fixed-point tangent test, TG22 = 13573; magnitudes
+ * outside the image are 0). map [B, H, W]: 2 = strong (mag > high), 0 = candidate (kept, mag > low), 1 = not an edge. low > high swaps the two. */
+int ug_canny_nms(const int16_t* dx, const int16_t* dy, const int32_t* mag, int64_t B, int64_t H, int64_t W, int32_t low, int32_t high, uint8_t* map,
+                 ug_stream_t stream);
+/* Stage 3: every candidate that is 8-connected to a strong pixel through candidates becomes strong (in place, in `map`); out = 255 there, else 0.
+ * Runs as sweeps of one launch each - a workgroup takes its tile to a local fixed point, no workgroup waits on another - and reads the 4-byte device
+ * word `flag` after each sweep (a stream synchronisation per sweep: this stage sits outside the denoise loop and cannot be graph-captured). *sweeps
+ * (host, may be NULL) receives their number, at most the value returned by the bound function below, H * W + 1. */
+int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W, uint8_t* out, int64_t out_bstride, int64_t out_rstride, int32_t* flag,
+                        int32_t* sweeps, ug_stream_t stream);
+int64_t ug_canny_max_sweeps(int64_t H, int64_t W);
+/* The three stages in one call on a caller-owned, 16-byte aligned workspace of the size the query returns. */
+int64_t ug_canny_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int ug_canny_u8(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t low, int32_t high, uint8_t* out,
+                int64_t out_bstride, int64_t out_rstride, void* workspace, int64_t workspace_bytes, int32_t* sweeps, ug_stream_t stream);
+/* PIL's Image.resize for 8-bit images (ImagingResample, 8bpc): horizontal pass, then vertical pass, a uint8 image between them; a pass whose size does
+ * not change is skipped and needs no tables. Per output coordinate o of a pass: bounds[2 o] = first input coordinate, bounds[2 o + 1] = taps n <= k,
+ * coef[o * k + i] = 22-bit fixed-point weights (device tables, built on the host: unigen_amd/image.py resample_tables). A value is
+ * clip((2^21 + sum_i in[first + i] * coef[i]) >> 22, 0, 255). tmp: [B, Hin, Wout, C] bytes, needed when both sizes change. C is 1 or 3. */
+int ug_img_resize_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t Hin, int64_t Win, int32_t C, uint8_t* dst,
+                     int64_t dst_bstride, int64_t dst_rstride, int64_t Hout, int64_t Wout, const int32_t* xbounds, const int32_t* xcoef, int32_t xk,
+                     const int32_t* ybounds, const int32_t* ycoef, int32_t yk, uint8_t* tmp, ug_stream_t stream);
+/* PIL's convert("L") of an RGB image: (19595 R + 38470 G + 7471 B + 0x8000) >> 16, [B, H, W, 3] -> [B, H, W, 1]. */
+int ug_img_rgb_to_l(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t H, int64_t W, uint8_t* dst, int64_t dst_bstride,
+                    int64_t dst_rstride, ug_stream_t stream);
+/* uint8 NHWC -> contiguous NCHW [B, Cout, H, W] of dst_dtype (UG_DT_F32 or UG_DT_BF16): v / 255.0f (IEEE division), then 2.0f * . - 1.0f when
+ * `normalize`, every operation rounded in fp32; bf16 is that value rounded to nearest-even. C is 1 or 3; Cout = C, or 3 with C = 1 (gray replicated). */
+int ug_img_u8_to_chw(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t H, int64_t W, int32_t C, void* dst, int32_t dst_dtype,
+                     int32_t Cout, int32_t normalize, ug_stream_t stream);
+/* Contiguous NCHW [B, C, H, W] of src_dtype -> uint8 NHWC with the rounding points of diffusers' denormalize + numpy_to_pil: x * 0.5 + 0.5 in the
+ * input's dtype (skipped with denormalize = 0: a processor built with do_normalize = False), clamp to [0, 1], to fp32, * 255.0f, round half to even.
+ * C from 1 to 4. */
+int ug_img_chw_to_u8(const void* src, int32_t src_dtype, int64_t B, int32_t C, int64_t H, int64_t W, uint8_t* dst, int64_t dst_bstride, int64_t dst_rstride,
+                     int32_t denormalize, ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

@@ -162,6 +162,19 @@ SIGNATURES.update({
     "ug_gated_gelu": (i32, [vp, i64, vp, i64, i64, i64, vp]),
     "ug_quick_gelu": (i32, [vp, vp, i64, vp]),
 })
+# image front end (csrc/image.hip): integer / exactly specified fp32 arithmetic, no fp32 twins
+SIGNATURES.update({
+    "ug_canny_grad": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "ug_canny_nms": (i32, [vp, vp, vp, i64, i64, i64, i32, i32, vp, vp]),
+    "ug_canny_hysteresis": (i32, [vp, i64, i64, i64, vp, i64, i64, vp, C.POINTER(i32), vp]),
+    "ug_canny_max_sweeps": (i64, [i64, i64]),
+    "ug_canny_workspace_bytes": (i64, [i64, i64, i64]),
+    "ug_canny_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, i32, i32, vp, i64, i64, vp, i64, C.POINTER(i32), vp]),
+    "ug_img_resize_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "ug_img_rgb_to_l": (i32, [vp, i64, i64, i64, i64, i64, vp, i64, i64, vp]),
+    "ug_img_u8_to_chw": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i32, i32, i32, vp]),
+    "ug_img_chw_to_u8": (i32, [vp, i32, i64, i32, i64, i64, vp, i64, i64, i32, vp]),
+})
 _F32_TWINS = {"ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
               "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu",
               "ug_flow_noise_f32": "ug_flow_noise", "ug_flow_loss_f32": "ug_flow_loss", "ug_flow_loss_bwd_f32": "ug_flow_loss_bwd",

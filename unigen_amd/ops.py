@@ -929,3 +929,125 @@ def quick_gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
     L.check(_fn("ug_quick_gelu", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_quick_gelu")
     return out
+
+
+# ---- image front end (csrc/image.hip): uint8 NHWC [B, H, W, C] tensors, byte strides per sample and per row -------------------------------------------
+u8 = torch.uint8
+
+
+def _img(x: torch.Tensor, name: str, channels=(1, 3)):
+    """-> (B, H, W, C, sample stride, row stride) of a uint8 [B, H, W, C] GPU tensor whose pixels are contiguous within a row."""
+    if not x.is_cuda:
+        raise L.UniGenHipError(f"{name}: expected a GPU tensor (unigen_amd has no CPU path)")
+    if x.dtype != u8 or x.dim() != 4:
+        raise TypeError(f"{name}: expected a uint8 [B, H, W, C] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, H, W, Cc = x.shape
+    if Cc not in channels:
+        raise ValueError(f"{name}: {Cc} channels (expected one of {channels})")
+    if (Cc > 1 and x.stride(3) != 1) or (W > 1 and x.stride(2) != Cc):
+        raise ValueError(f"{name}: the pixels of a row must be contiguous (strides {x.stride()})")
+    return B, H, W, Cc, x.stride(0), x.stride(1)
+
+
+def canny_grad(x: torch.Tensor):
+    """Stage 1 of Canny -> (dx int16, dy int16, mag int32), each [B, H, W]."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    dx, dy = torch.empty(B, H, W, dtype=torch.int16, device=x.device), torch.empty(B, H, W, dtype=torch.int16, device=x.device)
+    mag = torch.empty(B, H, W, dtype=torch.int32, device=x.device)
+    L.check(L.load().ug_canny_grad(x.data_ptr(), sb, sr, B, H, W, Cc, dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), _stream()), "ug_canny_grad")
+    return dx, dy, mag
+
+
+def canny_nms(dx: torch.Tensor, dy: torch.Tensor, mag: torch.Tensor, low: int, high: int) -> torch.Tensor:
+    """Stage 2 -> map uint8 [B, H, W]: 2 strong, 0 candidate, 1 not an edge."""
+    _chk(dx, "dx", torch.int16); _chk(dy, "dy", torch.int16); _chk(mag, "mag", torch.int32)
+    assert dx.is_contiguous() and dy.is_contiguous() and mag.is_contiguous() and dx.shape == dy.shape == mag.shape and dx.dim() == 3
+    B, H, W = dx.shape
+    out = torch.empty(B, H, W, dtype=u8, device=dx.device)
+    L.check(L.load().ug_canny_nms(dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), B, H, W, low, high, out.data_ptr(), _stream()), "ug_canny_nms")
+    return out
+
+
+def canny_max_sweeps(H: int, W: int) -> int:
+    return int(L.load().ug_canny_max_sweeps(H, W))
+
+
+def canny_hysteresis(emap: torch.Tensor):
+    """Stage 3 on a copy of `emap` -> (edges uint8 [B, H, W] 255 / 0, sweeps). Synchronises the stream once per sweep."""
+    _chk(emap, "emap", u8)
+    assert emap.dim() == 3
+    B, H, W = emap.shape
+    work = emap.contiguous().clone()
+    out = torch.empty(B, H, W, dtype=u8, device=emap.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=emap.device)
+    sweeps = C.c_int32(0)
+    L.check(L.load().ug_canny_hysteresis(work.data_ptr(), B, H, W, out.data_ptr(), H * W, W, flag.data_ptr(), C.byref(sweeps), _stream()), "ug_canny_hysteresis")
+    return out, sweeps.value
+
+
+def canny_u8(x: torch.Tensor, low: int = 100, high: int = 200):
+    """cv2.Canny(x, low, high) per image of a uint8 [B, H, W, C] batch -> (edges uint8 [B, H, W], sweeps of the hysteresis)."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    lib = L.load()
+    ws = torch.empty(int(lib.ug_canny_workspace_bytes(B, H, W)), dtype=u8, device=x.device)
+    out = torch.empty(B, H, W, dtype=u8, device=x.device)
+    sweeps = C.c_int32(0)
+    L.check(lib.ug_canny_u8(x.data_ptr(), sb, sr, B, H, W, Cc, low, high, out.data_ptr(), H * W, W, ws.data_ptr(), ws.numel(), C.byref(sweeps), _stream()),
+            "ug_canny_u8")
+    return out, sweeps.value
+
+
+def img_resize_u8(x: torch.Tensor, height: int, width: int, xtables=None, ytables=None) -> torch.Tensor:
+    """PIL's 8-bit resampling with host-built tables (unigen_amd.image.resample_tables, on the device): `xtables` / `ytables` = (bounds int32 [out, 2],
+    coef int32 [out, k], k) of the pass that changes the width / the height, None for a pass that is skipped."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    if (xtables is None) != (W == width) or (ytables is None) != (H == height):
+        raise ValueError("img_resize_u8: tables are needed for exactly the passes whose size changes")
+    for t, n in ((xtables, width), (ytables, height)):
+        if t is not None:
+            _chk(t[0], "bounds", torch.int32); _chk(t[1], "coef", torch.int32)
+            assert t[0].is_contiguous() and t[1].is_contiguous() and tuple(t[0].shape) == (n, 2) and tuple(t[1].shape) == (n, t[2])
+    out = torch.empty(B, height, width, Cc, dtype=u8, device=x.device)
+    tmp = torch.empty(B, H, width, Cc, dtype=u8, device=x.device) if (xtables is not None and ytables is not None) else None
+    xb, xc, xk = (xtables[0].data_ptr(), xtables[1].data_ptr(), xtables[2]) if xtables is not None else (None, None, 0)
+    yb, yc, yk = (ytables[0].data_ptr(), ytables[1].data_ptr(), ytables[2]) if ytables is not None else (None, None, 0)
+    L.check(L.load().ug_img_resize_u8(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), height * width * Cc, width * Cc, height, width, xb, xc, xk, yb, yc, yk,
+                                      _p(tmp), _stream()), "ug_img_resize_u8")
+    return out
+
+
+def img_rgb_to_l(x: torch.Tensor) -> torch.Tensor:
+    """PIL's convert("L"): [B, H, W, 3] -> [B, H, W, 1]."""
+    B, H, W, Cc, sb, sr = _img(x, "x", channels=(3,))
+    out = torch.empty(B, H, W, 1, dtype=u8, device=x.device)
+    L.check(L.load().ug_img_rgb_to_l(x.data_ptr(), sb, sr, B, H, W, out.data_ptr(), H * W, W, _stream()), "ug_img_rgb_to_l")
+    return out
+
+
+def _img_dt(dtype) -> int:
+    if dtype not in (bf16, f32):
+        raise TypeError(f"image tensors are torch.float32 or torch.bfloat16, got {dtype}")
+    return L.UG_DT_F32 if dtype == f32 else L.UG_DT_BF16
+
+
+def img_u8_to_chw(x: torch.Tensor, normalize: bool = True, dtype=f32, replicate: bool = False) -> torch.Tensor:
+    """uint8 [B, H, W, C] -> `dtype` [B, C, H, W] as 2 (v / 255) - 1 (or v / 255); `replicate` turns a gray image into three equal channels."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    cout = 3 if (replicate and Cc == 1) else Cc
+    out = torch.empty(B, cout, H, W, dtype=dtype, device=x.device)
+    L.check(L.load().ug_img_u8_to_chw(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), _img_dt(dtype), cout, int(bool(normalize)), _stream()), "ug_img_u8_to_chw")
+    return out
+
+
+def img_chw_to_u8(x: torch.Tensor, denormalize: bool = True) -> torch.Tensor:
+    """fp32 / bf16 [B, C, H, W] -> uint8 [B, H, W, C] with diffusers' rounding points (denormalize, clamp, * 255, round half to even)."""
+    if not x.is_cuda:
+        raise L.UniGenHipError("x: expected a GPU tensor (unigen_amd has no CPU path)")
+    if x.dim() != 4 or not 1 <= x.shape[1] <= 4:
+        raise ValueError(f"x: expected [B, C <= 4, H, W], got {tuple(x.shape)}")
+    dt = _img_dt(x.dtype)
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    out = torch.empty(B, H, W, Cc, dtype=u8, device=x.device)
+    L.check(L.load().ug_img_chw_to_u8(x.data_ptr(), dt, B, Cc, H, W, out.data_ptr(), H * W * Cc, W * Cc, int(bool(denormalize)), _stream()), "ug_img_chw_to_u8")
+    return out

@@ -233,7 +233,8 @@ class UniGenFLUXPipeline:
         `num_images_per_prompt` times next to its prompt (repeat_interleave), then device / dtype."""
         if not isinstance(image, torch.Tensor):
             if self.image_processor is None:
-                raise NotImplementedError("control_image is not a tensor and no image processor is attached: set `pipe.image_processor` (.preprocess(image, height=, width=))")
+                raise NotImplementedError("control_image is not a tensor and no image processor is attached: set `pipe.image_processor` (.preprocess(image, height=, width=)), "
+                                          "e.g. unigen_amd.image.VaeImageProcessor(vae_scale_factor=2 * pipe.vae_scale_factor)")
             image = self.image_processor.preprocess(image, height=height, width=width)
         repeat_by = batch_size if image.shape[0] == 1 else num_images_per_prompt
         return image.repeat_interleave(repeat_by, dim=0).to(device=device, dtype=dtype)
@@ -435,7 +436,8 @@ class UniGenSD3Pipeline:
         classifier-free guidance (unless guess_mode) and a one-channel map (depth) repeated to three channels."""
         if not isinstance(image, torch.Tensor):
             if self.image_processor is None:
-                raise NotImplementedError("control_image is not a tensor and no image processor is attached: set `pipe.image_processor` (.preprocess(image, height=, width=))")
+                raise NotImplementedError("control_image is not a tensor and no image processor is attached: set `pipe.image_processor` (.preprocess(image, height=, width=)), "
+                                          "e.g. unigen_amd.image.VaeImageProcessor(vae_scale_factor=2 * pipe.vae_scale_factor)")
             image = self.image_processor.preprocess(image, height=height, width=width)
         repeat_by = batch_size if image.shape[0] == 1 else num_images_per_prompt
         image = image.repeat_interleave(repeat_by, dim=0).to(device=device, dtype=dtype)
