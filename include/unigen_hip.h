@@ -211,7 +211,7 @@ int ug_moe_gate_topk(const void* x, const void* c, int64_t ld, const void* wg, i
 
 /* Capacity rule of topkgating (drop_policy "probs"): expert e keeps the `capacity` (= max(ceil(S / E * K), 4) for the reference's settings) largest
  * entries of its column of [logit if e is one of the token's K choices, else 0] over ALL S tokens - a chosen logit below zero loses to every
- * non-chooser's zero - ties in token order; a choice survives if its entry is kept. Writes slot int32 [K][S] (-1 = dropped; slots in token order
+ * non-chooser's zero - ties in token order, -0.0 and +0.0 being equal (a chosen -0.0 ties with the zeros); a choice survives if its entry is kept. Writes slot int32 [K][S] (-1 = dropped; slots in token order
  * among the kept), token_of_slot int32 [E][capacity] (-1 = empty), weights fp32 [K][S] = the kept choices' gate probabilities over their sum
  * clamped at FLT_EPSILON, exp_counts int64 [E] = choosers before the drop, l_aux fp32 scalar = (E / K) * sum_e mean_s(gates[s][e]) * exp_counts[e] / S. */
 int ug_moe_capacity_topk(const float* gates, const float* logits, const int32_t* idx, int64_t S, int32_t E, int32_t K, int64_t capacity,

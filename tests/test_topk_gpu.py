@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import unigen_ref as R
+from tests import moe_ref as M
 from tests.util import report, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -77,17 +78,12 @@ def test_topk_routing_dispatch_combine(gpu, S, E, D, K):
     yh, yc, xs, cs = _rand(g, E, C, D), _rand(g, E, C, D), _rand(g, S, D), _rand(g, S, D)
     o = torch.empty(S, D, device=gpu, dtype=BF)
     ops.moe_combine_topk(yh.to(gpu), yc.to(gpu), w, idx, slot, o, E=E, capacity=C, xs=xs.to(gpu), cs=cs.to(gpu))
-    # einsum("sec,ecm->sm") in bf16: fp32 sum over the kept choices IN CHOICE ORDER of bf16(weight) * y, one rounding; then the CoMoE residual sums
-    wb = w.cpu().to(BF).float()
-    eh, ec = torch.zeros(S, D), torch.zeros(S, D)
-    for k in range(K):
-        kept = rslot[k] >= 0
-        rows = (ridx[k] * C + rslot[k].clamp_min(0))
-        eh += torch.where(kept[:, None], wb[k][:, None] * yh.float().view(E * C, D)[rows], torch.zeros(()))
-        ec += torch.where(kept[:, None], wb[k][:, None] * yc.float().view(E * C, D)[rows], torch.zeros(()))
-    ref = (xs + eh.to(BF)) + (cs + ec.to(BF))
-    m = report(f"moe_topk_combine_S{S}", o, ref)
-    assert m["rel_l2"] <= 2e-3 and m["mismatch_frac"] <= 0.02, m          # fma vs mul + add inside the fp32 sum moves the odd last bit
+    # einsum("sec,ecm->sm") in bf16: fp32 sum over the kept choices IN CHOICE ORDER of bf16(weight) * y, one rounding; then the CoMoE residual sums.
+    # The products of bf16 values are exact in fp32, so the kernel's fma chain is a chain of plain fp32 additions, which tests/moe_ref.py's float64
+    # chain rounded to fp32 after each step predicts bit for bit (docs/PARITY_TOLERANCES.md, "MoE routing, dispatch and combine sweep").
+    ref, bound = M.combine_topk(yh, yc, w.cpu(), ridx, rslot, BF, xs=xs, cs=cs)
+    m = report(f"moe_topk_combine_S{S}", o, ref.to(BF))
+    assert float(bound.max()) == 0 and m["mismatch_frac"] == 0.0, m
 
 
 def test_topk_fp32_twin_and_repeatability(gpu):

@@ -264,9 +264,11 @@ __global__ __launch_bounds__(256) void moe_weights_top2_kernel(const float* __re
     weights[S + s] = g2 / den;
 }
 
-// order-preserving map of a float onto unsigned (larger float <-> larger key), for the radix select below
+// order-preserving map of a float onto unsigned (larger float <-> larger key), for the radix select below. -0.0 takes +0.0's key: the two compare
+// equal (torch.topk), so a chooser's -0.0 logit ties with the non-choosers' zeros and the tie goes by token order like any other.
 __device__ __forceinline__ unsigned ug_fkey(float v) {
-    const unsigned u = __float_as_uint(v);
+    unsigned u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -358,13 +360,16 @@ __global__ __launch_bounds__(256) void moe_weights_topk_kernel(const float* __re
                                                                const int32_t* __restrict__ slot, int S, int E, int K, float* __restrict__ weights) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
-    float g[GATE_MAXE], den = 0.f;
+    // the sum of up to 16 terms and the division in fp64, one rounding to fp32: an fp32 sum alone is off by up to K - 1 roundings, more than the
+    // 2 ulps the weights are held to (docs/PARITY_TOLERANCES.md, "MoE routing, dispatch and combine sweep")
+    float g[GATE_MAXE];
+    double den = 0.0;
     for (int k = 0; k < K; ++k) {
         g[k] = slot[(int64_t)k * S + s] >= 0 ? gates[(int64_t)s * E + idx[(int64_t)k * S + s]] : 0.f;
-        den += g[k];
+        den += (double)g[k];
     }
-    den = fmaxf(den, 1.1920928955078125e-07f);
-    for (int k = 0; k < K; ++k) weights[(int64_t)k * S + s] = g[k] / den;
+    den = fmax(den, 1.1920928955078125e-07);
+    for (int k = 0; k < K; ++k) weights[(int64_t)k * S + s] = (float)((double)g[k] / den);
 }
 
 // l_aux = E * sum_e mean_s(gates[s][e]) * (n_e / S), n_e = tokens whose FIRST choice is e: exp_counts[e] (top-1: the same thing) or, when
