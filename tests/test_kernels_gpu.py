@@ -433,6 +433,42 @@ def test_flash_attn_head_dim_64(gpu, B, H, Lq, Lkv):
     assert m["rel_l2"] <= 4e-3, m
 
 
+@pytest.mark.parametrize("Lkv", [64, 65, 191])
+def test_flash_attn_head_dim_64_buffer_and_pointer_dma_same_bits(gpu, Lkv):
+    """The one thing the head-width-64 dispatcher chooses is the form of the K / V LDS-DMAs: buffer form when K and V share a row stride that is a
+    multiple of 16 elements, pointer form otherwise. Round 6 measured the two bit-identical; here the same values go through both (V copied into a
+    buffer of row stride D + 8: a multiple of 8, not of 16, and not K's). Lq = 257: two workgroups, the second one ragged; Lkv = one whole tile, a
+    one-key ragged tile, three tiles with a ragged tail. O and the base-2 log-sum-exp rows must be equal bit for bit, and each run within the
+    stated head-width-64 forward bounds (docs/PARITY_TOLERANCES.md: O rel-L2 <= 4e-3; lse2 within 2^-16 (1 + |lse2|) + 2^-9 / ln 2) of the fp64 softmax."""
+    from unigen_amd import ops
+    B, H, Lq, dh = 1, 2, 257, 64
+    D = H * dh
+    g = torch.Generator().manual_seed(64 + Lkv)
+    q, kv = _rand(g, B, Lq, D), _rand(g, B, Lkv, 2 * D)
+    qd, kvd = q.to(gpu), kv.to(gpu)
+    v2 = torch.zeros(B, Lkv, D + 8, device=gpu, dtype=BF)
+    v2[:, :, :D] = kvd[:, :, D:]
+    q64, k64, v64 = (x.view(B, -1, H, dh).transpose(1, 2).double() for x in (q, kv[:, :, :D], kv[:, :, D:]))
+    s = q64 @ k64.transpose(-1, -2) * dh ** -0.5
+    ref_o = (torch.softmax(s, dim=-1) @ v64).transpose(1, 2).reshape(B, Lq, D)
+    ref_lse2 = torch.logsumexp(s, dim=-1) / math.log(2.0)
+    lse_tol = 2.0 ** -16 * (1.0 + ref_lse2.abs()) + 2.0 ** -9 / math.log(2.0)
+    runs = []
+    for name, vbuf, v_strides in (("buffer", kvd[0, 0, D:], (2 * D, Lkv * 2 * D)), ("pointer", v2, (D + 8, Lkv * (D + 8)))):
+        out = torch.zeros(B, Lq, D, device=gpu, dtype=BF)
+        lse = torch.zeros(B, H, Lq, device=gpu, dtype=torch.float32)
+        ops.flash_attn(qd, kvd, vbuf, out, batches=B, heads=H, dh=dh, Lq=Lq, Lkv=Lkv, q_strides=(D, Lq * D), k_strides=(2 * D, Lkv * 2 * D),
+                       v_strides=v_strides, o_strides=(D, Lq * D), lse=lse)
+        m = report(f"flash_attn64_{name}_dma_{Lq}x{Lkv}", out, ref_o)
+        lse_err = (lse.double().cpu() - ref_lse2).abs()
+        print(f"flash_attn64_{name}_dma_{Lq}x{Lkv}: lse2 max err {float(lse_err.max()):.3e} (smallest bound {float(lse_tol.min()):.3e})")
+        assert m["rel_l2"] <= 4e-3, (name, m)
+        assert bool((lse_err <= lse_tol).all()), (name, float(lse_err.max()))
+        runs.append((out, lse))
+    assert torch.equal(runs[0][0], runs[1][0]), "O differs between the buffer-form and the pointer-form DMAs"
+    assert torch.equal(runs[0][1], runs[1][1]), "lse2 differs between the buffer-form and the pointer-form DMAs"
+
+
 def test_grouped_residual_gate_gather_rowbcast_plain_dispatch(gpu):
     from unigen_amd import lib as L, ops
     g = torch.Generator().manual_seed(9)
