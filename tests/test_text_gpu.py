@@ -25,17 +25,7 @@ from tests.util import rel_l2
 pytestmark = pytest.mark.gpu
 BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "text_tiny.safetensors")
-FP32_TERM = 2.0 ** -20
-
-
-def half_ulp(v):
-    """half a bf16 ulp at the magnitude of v (taken a hair above it: an fp32 evaluation may sit on the other side of a power of two)"""
-    return R.bf16_ulp(v.abs() * (1 + 2.0 ** -18)) / 2
-
-
-def worst_row(got, ref):
-    g, r = got.double().reshape(-1, got.shape[-1]), ref.double().reshape(-1, ref.shape[-1])
-    return float(((g - r).norm(dim=-1) / r.norm(dim=-1).clamp_min(1e-30)).max())
+FP32_TERM, half_ulp, worst_row = R.FP32_TERM, R.half_ulp, R.worst_row       # shared with the sweep (tests/test_fuzz_text_gpu.py)
 
 
 # ---- attention -------------------------------------------------------------------------------------------------------------------

@@ -210,3 +210,158 @@ def test_new_abi_symbols():
     assert b"rel_len" in cdll.ug_last_error()
     assert cdll.ug_rmsnorm_rows(16, 12, 16, 16, 12, 1, 12, 1e-6, None) == lib.UG_ERR_UNSUPPORTED
     assert cdll.ug_quick_gelu(16, 16, 12, None) == lib.UG_ERR_UNSUPPORTED and cdll.ug_gated_gelu(16, 8, 16, 8, 1, 8, None) == lib.UG_ERR_BAD_SHAPE
+
+
+# ---- the sweep's references, cases and bounds (tests/test_fuzz_text_gpu.py) ------------------------------------------------------------------
+@pytest.mark.parametrize("Lq,Lkv", ((5, 77), (200, 33), (129, 128)))
+def test_bias_at_unequal_lengths_equals_transformers(Lq, Lkv):
+    """a table longer than the launch needs: the extra entries do not matter"""
+    pytest.importorskip("transformers")
+    from transformers.models.t5.modeling_t5 import T5Attention, T5Config
+    att = T5Attention(T5Config(**R.T5_TINY), has_relative_attention_bias=True)
+    with torch.no_grad():
+        bias = att.compute_bias(Lq, Lkv)[0]                          # [H, Lq, Lkv] fp32
+    w = att.relative_attention_bias.weight.detach()
+    for rel_len in (max(Lq, Lkv), max(Lq, Lkv) + 37):
+        assert torch.equal(R.bias_from_table(R.t5_rel_table(w, rel_len, 32, 128), Lq, Lkv), bias)
+
+
+def _sweep_and_fixed():
+    return [R.attn_sweep_spec(i) for i in range(R.N_ATTN_SWEEP)] + list(R.ATTN_FIXED.values())
+
+
+def _case(spec):
+    return R.attn_fixed_case(spec["id"]) if spec["id"] in R.ATTN_FIXED else R.attn_sweep_case(spec["i"])
+
+
+def test_attention_sweep_grid():
+    specs = [R.attn_sweep_spec(i) for i in range(R.N_ATTN_SWEEP)]
+    assert {s["B"] for s in specs} == {1, 2, 3} and {s["H"] for s in specs} == {1, 3, 5, 12}
+    assert {(s["mode"], s["regime"]) for s in specs} == set(R.ATTN_COMBOS) and len(R.ATTN_COMBOS) == 14
+    assert {s["rel_len"] - max(s["Lq"], s["Lkv"]) for s in specs if s["bias"]} == {0, 1, 37}
+    assert all(s["Lq"] in R.ATTN_LENGTHS and s["Lkv"] in R.ATTN_LENGTHS and s["B"] * s["H"] * s["Lq"] * s["Lkv"] <= R.ATTN_CAP for s in specs)
+    assert any(s["Lq"] != s["Lkv"] and s["rel_len"] > max(s["Lq"], s["Lkv"]) for s in specs)
+    lays = [s["layout"] for s in specs]
+    assert {l["shared"] for l in lays} == {True, False} and {l["o"]["off"] for l in lays} == {0, 4}
+    assert any(l["o"]["colpad"] % 8 == 4 for l in lays) and all(l["o"]["colpad"] % 4 == 0 and l[n]["colpad"] % 8 == 0 for l in lays for n in "qkv")
+    assert len({s["id"] for s in specs}) == len(specs)
+    f = R.ATTN_FIXED
+    assert (f["rel4096"]["rel_len"], f["rel4096"]["H"]) == (4096, 3) and R.attn_fixed_case("rel4096")["table"].shape == (3, 8191)
+    assert [(f[n]["Lq"], f[n]["Lkv"], f[n]["mode"]) for n in ("q1_kv520", "q520_kv1", "causal_129x33", "causal_33x257")] == \
+        [(1, 520, "bias"), (520, 1, "bias"), (129, 33, "causal"), (33, 257, "causal")]
+
+
+def test_attention_layout_round_trip():
+    """the buffers hold the case where the strides say, NaN elsewhere; the output reader finds the region and a touched sentinel"""
+    for i in (0, 2):
+        c = R.attn_sweep_case(i)
+        bufs = R.attn_buffers(c, torch.bfloat16)
+        for n, L in (("q", c["Lq"]), ("k", c["Lkv"]), ("v", c["Lkv"])):
+            t = bufs[n]
+            got = torch.as_strided(t["buf"], (c["B"], L, t["width"]), (t["bs"], t["rs"], 1), t["off"])
+            assert torch.equal(got.double().view(c["B"], L, c["H"], 64), c[n]) and t["rs"] % 8 == 0 and t["bs"] % 8 == 0
+            held = c["B"] * (c["Lq"] + 2 * c["Lkv"]) * t["width"] if c["layout"]["shared"] else got.numel()
+            assert int(torch.isnan(t["buf"]).sum()) == t["buf"].numel() - held
+        o = bufs["o"]
+        assert o["rs"] % 4 == 0 and o["bs"] % 4 == 0 and (o["off"] - R.GUARD) == c["layout"]["o"]["off"]
+        got, intact = R.attn_read_output(c, o, o["buf"])
+        assert intact and bool((got == R.SENT_O).all())
+        o["buf"][o["off"] + c["H"] * 64] = 1.0                     # the first pad column of row 0, or the next row's first element without a pad
+        assert R.attn_read_output(c, o, o["buf"])[1] == (c["layout"]["o"]["colpad"] == 0 and c["Lq"] > 1)
+
+
+@pytest.mark.parametrize("slip", list(R.ATTN_SLIPS))
+def test_every_attention_slip_misses_the_gpu_bound(slip):
+    """A kernel that commits the slip, rounding where the product path rounds, misses the bound that tests/test_fuzz_text_gpu.py applies (the same
+    judge), on at least one case of a mode in which the slip can happen; the right reference, rounded the same way, passes it."""
+    caught = []
+    for spec in _sweep_and_fixed():
+        if spec["mode"] not in R.ATTN_SLIPS[slip]:
+            continue
+        c = _case(spec)
+        truth, variant = R.attn_refs(c)
+        wrong = R.attention(c["q"], c["k"], c["v"], c["scale"], c["table"], c["causal"], rnd=R.bf, slip=slip)
+        ratio = R.attn_judge(wrong, truth, variant, True)[0]
+        assert R.attn_judge(variant, truth, variant, True)[0] <= 1.0
+        if not ratio <= 1.0:
+            caught.append((spec["id"], ratio))
+        if len(caught) >= 2:
+            break
+    print(f"TEXT slip {slip}: caught by {caught}")
+    assert caught, f"no case tells {slip} from the right kernel"
+
+
+def test_attention_regimes_do_what_they_claim():
+    seen = set()
+    for i in range(R.N_ATTN_SWEEP):
+        spec = R.attn_sweep_spec(i)
+        if spec["regime"] == "gaussian" or (spec["regime"], spec["mode"]) in seen:
+            continue
+        seen.add((spec["regime"], spec["mode"]))
+        c = R.attn_sweep_case(i)
+        Lq, Lkv = c["Lq"], c["Lkv"]
+        s = torch.einsum("bqhd,bkhd->bhqk", c["q"], c["k"]) * c["scale"]
+        if c["bias"]:
+            s = s + R.bias_from_table(c["table"].double(), Lq, Lkv)[None]
+        qpos, kpos = torch.arange(Lq)[:, None], torch.arange(Lkv)[None, :]
+        if c["causal"]:
+            s = s.masked_fill(kpos > qpos, float("-inf"))
+        assert torch.isfinite(s.amax(-1)).all() and float(s[torch.isfinite(s)].abs().max()) < 1e4        # every score finite in fp32, by far
+        p = torch.softmax(s, -1)
+        if c["regime"] in ("rising", "falling"):
+            nt = (Lkv + 63) // 64
+            pad = torch.full((*s.shape[:-1], nt * 64 - Lkv), float("-inf"), dtype=s.dtype)
+            tiles = torch.cat([s, pad], -1).view(*s.shape[:-1], nt, 64)[:, :, c["rows"]]               # [B, H, rows, tiles, 64]
+            tmax, full = tiles.amax(-1), torch.isfinite(tiles).sum(-1) >= 16                           # a tile counts where the row sees 16 of its keys
+            up = tmax[..., 1:] > tmax[..., :-1] if c["regime"] == "rising" else tmax[..., 1:] < tmax[..., :-1]
+            vis = full[..., 1:] & full[..., :-1]
+            run3 = (up[..., 1:] & up[..., :-1] & vis[..., 1:] & vis[..., :-1]).any(-1)                   # three consecutive tiles, each above the last
+            have3 = (vis.sum(-1) >= 2)
+            assert len(c["rows"]) * 2 >= Lq and bool(have3.any()) and float(run3[have3].double().mean()) >= 0.99, spec["id"]
+            if c["regime"] == "rising":
+                assert float((up & vis).sum()) >= 0.95 * float(vis.sum()), spec["id"]      # and nearly every tile raises a chosen row's maximum
+        elif c["regime"] == "spike_tail":
+            key = c["spike_key"]
+            assert Lkv % 64 and Lkv // 64 * 64 <= key < Lkv and len(c["rows"]) > 0
+            assert float(p[:, :, c["rows"], key].min()) > 0.5, spec["id"]
+            assert abs(len(c["rows"]) - (Lq + 3) // 4) <= (0 if not c["causal"] else Lq)
+        elif c["regime"] == "far_bias":
+            near = ((kpos - qpos).abs() <= 16).to(p.dtype)
+            assert float((p * near).sum(-1).min()) >= 0.5, spec["id"]
+            assert float(c["table"][:, (torch.arange(c["table"].shape[1]) - (c["rel_len"] - 1)).abs() == 40].min()) < -55       # (the other side may be an entry that no launch reads)
+    assert len(seen) == 11
+
+
+def test_constant_and_zero_rows_have_zero_variance():
+    kinds = set()
+    for c in R.norm_sweep_cases():
+        x, w, b = R.norm_data(c)
+        for r, kind in enumerate(R.norm_row_kinds(c)):
+            kinds.add((kind, c["D"] > 4608))
+            if kind in ("constant", "zero"):
+                mu = x[r].mean()
+                assert float(((x[r] - mu) ** 2).mean()) == 0.0 and torch.equal(R.layernorm(x[r:r + 1], w, b, 1e-5)[0], b)
+                assert torch.equal(R.layernorm_bound(x[r:r + 1], w, b, 1e-5, True)[0][0], b)
+                if kind == "zero":
+                    assert not R.rmsnorm(x[r:r + 1], w, 1e-6).any()
+            if kind == "big_mean" and c["D"] >= 512:                 # (eight such values all round to the mean)
+                assert 300 < float(x[r].mean().abs() / x[r].std()) < 3000
+    assert kinds == {(k, wide) for k in R.NORM_KINDS for wide in (False, True)}          # each kind on both sides of the register-resident limit
+    cases = R.norm_sweep_cases()
+    assert {(c["D"], c["rows"]) for c in cases} == {(D, r) for D in R.NORM_D for r in R.NORM_ROWS}
+    assert {(c["ldx"] - c["D"], c["ldo"] - c["D"]) for c in cases} == {(a, b) for a in R.NORM_PADS for b in R.NORM_PADS}
+    acts = R.act_sweep_cases()
+    assert {(c["M"], c["F"]) for c in acts} == {(m, f) for m in R.ACT_M for f in R.ACT_F}
+    assert {(c["ld"] - 2 * c["F"], c["ldo"] - c["F"]) for c in acts} == {(a, b) for a in R.ACT_PADS for b in R.ACT_PADS}
+    x = R.all_finite_bf16()
+    assert torch.equal(R.bf(x), x) and x.unique().numel() == 65279 and int((x == 0).sum()) == 2        # +0 and -0 are one value, two patterns
+
+
+def test_elementwise_excess_handles_overflow_only_where_the_truth_overflows():
+    truth = torch.tensor([1e39, -1e39, 1.0, 1e39, 1.0], dtype=torch.float64)
+    got = torch.tensor([float("inf"), float("-inf"), 1.0, float("-inf"), float("inf")], dtype=torch.float64)
+    bound = torch.full_like(truth, 1e-3)
+    assert R.elementwise_excess(got[:3], truth[:3], bound[:3], True) == 0.0
+    assert R.elementwise_excess(got[3:4], truth[3:4], bound[3:4], True) == float("inf")
+    assert R.elementwise_excess(got[4:], truth[4:], bound[4:], False) == float("inf")
+    assert R.elementwise_excess(torch.tensor([float("nan")], dtype=torch.float64), truth[2:3], bound[2:3], True) == float("inf")
