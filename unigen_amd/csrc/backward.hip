@@ -721,10 +721,6 @@ int rowdot_impl(const void* a, int64_t lda, const void* b, int64_t ldb, float* o
 
 }  // namespace
 
-#define UG_TWINS(NAME, IMPL, PARAMS, ARGS)                                              \
-    extern "C" int NAME PARAMS { return IMPL<bf16_t> ARGS; }                            \
-    extern "C" int NAME##_f32 PARAMS { return IMPL<float> ARGS; }
-
 UG_TWINS(ug_transpose, transpose_impl,
          (const void* src, int64_t ld_src, int64_t src_bstride, void* dst, int64_t ld_dst, int64_t dst_bstride, int64_t batch, int64_t rows, int64_t cols,
           int64_t rows_pad, ug_stream_t stream),

@@ -36,6 +36,12 @@ int ug_env_int(const char* name, int dflt);
 #define UG_TUNE(name, dflt) (dflt)
 #endif
 
+// the bf16 entry point NAME and its fp32 verification twin NAME_f32 from one implementation template IMPL<T>: PARAMS is the parenthesised
+// parameter list of both, ARGS the parenthesised arguments handed to IMPL
+#define UG_TWINS(NAME, IMPL, PARAMS, ARGS)                                              \
+    extern "C" int NAME PARAMS { return IMPL<bf16_t> ARGS; }                            \
+    extern "C" int NAME##_f32 PARAMS { return IMPL<float> ARGS; }
+
 static inline bool ug_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // ---- bf16 <-> f32 (device) -------------------------------------------------------------
