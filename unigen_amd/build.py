@@ -2,7 +2,7 @@
 
     python -m unigen_amd.build [--force]     the PRODUCT library unigen_amd/libunigen_hip.so: one kernel per dispatch decision, tuning constants fixed
     python -m unigen_amd.build --probe       tools/probe/libunigen_hip_probe.so: the same sources with -DUG_PROBE_BUILD plus the probe-only sources of
-                                             tools/probe/csrc/ (the GEMM and attention-forward kernels that lost their A/B), i.e. every measured-and-
+                                             tools/probe/csrc/ (the GEMM, attention-forward and attention-backward kernels that lost their A/B), i.e. every measured-and-
                                              dropped kernel variant compiled in and the UG_* tuning switches read from the environment again (A/B tools
                                              only; select it with UG_LIB_PATH). Objects go to tools/probe/obj/, never next to the product's.
 
@@ -23,11 +23,11 @@ LIB = os.path.join(HERE, "libunigen_hip.so")
 PROBE_DIR = os.path.join(ROOT, "tools", "probe")
 PROBE_LIB = os.path.join(PROBE_DIR, "libunigen_hip_probe.so")
 SOURCES = ["core.hip", "gemm.hip", "attention.hip", "elementwise.hip", "moe.hip", "verify_f32.hip", "probe.hip", "vae.hip", "backward.hip", "optim.hip", "lora_bwd.hip", "objective.hip", "text.hip", "image.hip"]
-PROBE_ONLY_SOURCES = ["gemm_pwg.hip", "gemm_tn.hip", "lora_down.hip", "attn_fwd_variants.hip"]      # tools/probe/csrc/: kernels that lost their A/B, not in the product library
+PROBE_ONLY_SOURCES = ["gemm_pwg.hip", "gemm_tn.hip", "lora_down.hip", "attn_fwd_variants.hip", "attn_bwd_variants.hip"]      # tools/probe/csrc/: kernels that lost their A/B, not in the product library
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # attention: scores are finite or -inf, never NaN; without IEEE mode hipcc drops the NaN-quieting v_max x,x it adds per fmaxf operand
 ATTN_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee"]
-EXTRA = {"attention.hip": ATTN_FLAGS, "attn_fwd_variants.hip": ATTN_FLAGS}
+EXTRA = {"attention.hip": ATTN_FLAGS, "attn_fwd_variants.hip": ATTN_FLAGS, "attn_bwd_variants.hip": ATTN_FLAGS}
 # UG_EXTRA_HIPCC_FLAGS: extra flags for a diagnostic build (e.g. -DUG_DIAG_STAMPS); such a build must be made with force=True both ways
 FLAGS = os.environ.get("UG_EXTRA_HIPCC_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
 

@@ -473,20 +473,21 @@ __global__ __launch_bounds__(512, DH == 128 ? 2 : 4) void flash_attn_kernel(
 
 // =====================================================================================================================
 // Attention BACKWARD (the autograd of F.scaled_dot_product_attention, src/UniGenUtils.py:601) on the forward kernel's
-// tiling. One kernel, four modes; a workgroup OWNS 256 rows of one side (each wave 32, their fragments in registers as the B operand, the owned
-// row index on the LANE) and STREAMS 64-row tiles of the other side through the forward's swizzled LDS image (row reads for the score-like
-// products, transposed reads for the accumulating product):
+// tiling. This file holds the kernels the product dispatches: attn_bwd_kernel in its two query-owning modes (below), the fused dK / dV kernel
+// attn_bwd_dkv_kernel, the pair-scheme dQ kernel attn_bwd_dq_kernel and attn_delta_kernel. In attn_bwd_kernel a workgroup OWNS 256 queries (each
+// wave 32, their fragments in registers as the B operand, the query index on the LANE) and STREAMS 64-key tiles through the forward's swizzled
+// LDS image (row reads for the score-like products, transposed reads for the accumulating product):
 //   LSE : owns queries,  streams K       : S^T = K Q^T                         -> lse2[q] = log2 sum_k 2^(c S)          (lane-local statistics)
 //   DQ  : owns queries,  streams K, V    : S^T = K Q^T, dP^T = V dO^T, dS^T = P^T (dP^T - delta)  -> dQ^T += K^T dS^T, x scale at the end
-//   DK  : owns keys,     streams Q, dO   : S   = Q K^T, dP   = dO V^T, dS   = P   (dP   - delta)  -> dK^T += Q^T dS,     x scale at the end
-//   DV  : owns keys,     streams Q, dO   : S   = Q K^T, P                                               -> dV^T += dO^T P
-// with P = 2^(c S - lse2[q]), c = scale log2(e), delta[q] = sum_d dO[q][d] O[q][d]. In every mode the 32x32 accumulator of a score-like product
-// has the streamed index on its rows and the owned index on its lanes, so its registers, packed to bf16, ARE the B operand of the accumulating
-// product (the forward's P^T trick); lse / delta are per lane when queries are owned and per accumulator row when they are streamed. S is
-// recomputed per mode (8 product units against the minimum of 5) - still ~4x less time than moving fp32 score matrices through HBM.
-// Streamed tiles (and, when queries are streamed, their 64 lse2 / delta values) reach LDS by LDS-DMA one tile ahead; at dh 128 the LDS reads
-// of every matrix phase are software-pipelined by hand. Measured (tools/attn_bwd_ab.py, profiles/r02f_attn_bwd.log): 501 -> 595 TFLOP/s of the
-// algorithmic 10 B H Lq Lkv dh at dh 128 (4608^2), 395-420 -> 511-551 at dh 64.
+// with P = 2^(c S - lse2[q]), c = scale log2(e), delta[q] = sum_d dO[q][d] O[q][d]. The 32x32 accumulator of a score-like product has the
+// streamed index on its rows and the owned index on its lanes, so its registers, packed to bf16, ARE the B operand of the accumulating
+// product (the forward's P^T trick); lse / delta are per lane. The kernel was cut from a template of four modes and two staging forms: its
+// key-owning modes DK and DV (they stream Q, dO and the queries' statistics; the fused kernel below replaced them) and register staging of the
+// streamed tiles (HBM -> registers -> LDS instead of LDS-DMA) are the frozen copy attn_bwd_var_kernel in tools/probe/csrc/attn_bwd_variants.hip,
+// probe library only (UG_ATTN_BWD_FUSE_DKV=0, UG_ATTN_BWD_DMA=0). S is recomputed per kernel - still ~4x less time than moving fp32 score
+// matrices through HBM. Streamed tiles reach LDS by LDS-DMA one tile ahead; at dh 128 the LDS reads of every matrix phase are
+// software-pipelined by hand. Measured (tools/attn_bwd_ab.py, profiles/r02f_attn_bwd.log): 501 -> 595 TFLOP/s of the algorithmic
+// 10 B H Lq Lkv dh at dh 128 (4608^2), 395-420 -> 511-551 at dh 64.
 // Tried and removed (commit "Attention backward: hand-pipelined LDS reads ...", same log): an X|Y staggered variant as in the forward (wave
 // groups one segment apart, S of the whole tile and Z crossing the barriers in registers, three LDS-DMA buffers). Same bits, but at dh 128 it
 // needs ~300 registers (hipcc spilled 100: 211 TFLOP/s) and at dh 64 it measured 431-465 against the lock-step kernel's 453-492 of that day:
@@ -495,129 +496,129 @@ __global__ __launch_bounds__(512, DH == 128 ? 2 : 4) void flash_attn_kernel(
 // inside the lock-step kernel: +3 % / -6 % (dh 128 / 64) before the pipelining, -3 % after it.
 
 // =====================================================================================================================
-enum { BWD_LSE = 0, BWD_DQ = 1, BWD_DK = 2, BWD_DV = 3 };
+// What the three streaming kernels below share. A streamed tile image is NI runs of 1 KiB (RPI rows each); wave w owns runs w * NIW .. + NIW - 1 of
+// both streamed tiles and issues their LDS-DMAs itself - no staging registers, no ds_write. The swizzle is applied on the source side as in the forward.
+template <int DH> constexpr int BWD_NIW = KVB * 2 * DH / 1024 / 8;
+// per-lane byte offsets of a wave's runs inside a whole tile of each of the two streamed operands (row strides rs1, rs2)
+template <int DH>
+__device__ __forceinline__ void bwd_dma_offsets(int wave, int lane, int64_t rs1, int64_t rs2, unsigned (&d1o)[BWD_NIW<DH>], unsigned (&d2o)[BWD_NIW<DH>]) {
+    constexpr int RB = 2 * DH, NCH = DH / 8, RPI = 1024 / RB, NIW = BWD_NIW<DH>;
+#pragma unroll
+    for (int u = 0; u < NIW; ++u) {
+        const int row = (wave * NIW + u) * RPI + lane / NCH;
+        const int ch = (lane % NCH) ^ row_swz<DH>(row);
+        d1o[u] = (unsigned)(row * (int)rs1 + ch * 8) * 2u;
+        d2o[u] = (unsigned)(row * (int)rs2 + ch * 8) * 2u;
+    }
+}
+// this wave's share of the tile of rows row0 .. row0 + 63 of `base` (L rows) -> LDS at dst
+template <int DH>
+__device__ __forceinline__ void bwd_dma_stream(const bf16_t* base, int64_t rs, const unsigned (&off)[BWD_NIW<DH>], int row0, int L, int wave, int lane, unsigned dst) {
+    constexpr int RB = 2 * DH, NCH = DH / 8, RPI = 1024 / RB, NIW = BWD_NIW<DH>;
+    if (row0 + KVB <= L) {
+        const void* tb = uniform_ptr(base + (int64_t)row0 * rs);
+#pragma unroll
+        for (int u = 0; u < NIW; ++u) glds16_off(tb, off[u], dst + u * 1024);
+    } else {                                           // ragged last tile: rows past the end re-read the last row (masked by the caller)
+        int lane_r = lane;
+        asm volatile("" : "+v"(lane_r));
+#pragma unroll
+        for (int u = 0; u < NIW; ++u) {
+            const int row = (wave * NIW + u) * RPI + lane_r / NCH;
+            const int ch = (lane_r % NCH) ^ row_swz<DH>(row);
+            int sr = row0 + row; if (sr > L - 1) sr = L - 1;
+            glds16_ptr(base + (int64_t)sr * rs + ch * 8, dst + u * 1024);
+        }
+    }
+}
+// per-lane LDS read offsets: every swizzled offset is BASE ^ constant, re-derived from opaque copies of three bases (no per-fragment registers)
+template <int DH>
+__device__ __forceinline__ void bwd_read_bases(int lane, int& k_base, int& tlo_base, int& thi_base) {
+    constexpr int RB = 2 * DH;
+    const int r = lane & 31, h = lane >> 5;
+    k_base = RB * r + 16 * (h ^ row_swz<DH>(r));                           // row fragment s of 32-row block kb: kb * 32 * RB + (k_base ^ 32 s)
+    const int i16 = lane & 15, g16 = lane >> 4;
+    const int t_key = 4 * h + (i16 >> 2), t_lowch = 2 * (g16 & 1) + ((i16 & 3) >> 1), t_b8 = 8 * (i16 & 1);
+    tlo_base = RB * t_key + 16 * (t_lowch ^ row_swz<DH>(t_key)) + t_b8;              // d-block db, k-step ks: ks * 16 * RB + (base ^ 64 db)
+    thi_base = RB * (t_key + 8) + 16 * (t_lowch ^ row_swz<DH>(t_key + 8)) + t_b8;
+}
+template <int NDB>
+__device__ __forceinline__ void bwd_zero(f32x16 (&acc)[NDB]) {
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[db][i] = 0.f;
+}
+// one gradient row, acc^T[d][own row] x es -> bf16: lane (r, h) holds columns 32 db + 8 g4 + 4 h .. + 3 of its row (Orow: the row's head slice)
+template <int NDB>
+__device__ __forceinline__ void bwd_store_row(bf16_t* Orow, const f32x16 (&acc)[NDB], float es, int h) {
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            u32x2 w;
+            w.x = pack2bf(acc[db][4 * g4 + 0] * es, acc[db][4 * g4 + 1] * es);
+            w.y = pack2bf(acc[db][4 * g4 + 2] * es, acc[db][4 * g4 + 3] * es);
+            *(u32x2*)(Orow + 32 * db + 8 * g4 + 4 * h) = w;
+        }
+}
 
-template <int DH, int MODE, bool DMA>
+template <int DH, bool DQ>       // head dim 128 | 64; DQ: the dQ mode (own2 = dO, st2 = V, out = dQ), else the LSE mode (those three unused)
 __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
     const bf16_t* __restrict__ own1, int64_t o1_rs, int64_t o1_bs, const bf16_t* __restrict__ own2, int64_t o2_rs, int64_t o2_bs,
     const bf16_t* __restrict__ st1, int64_t s1_rs, int64_t s1_bs, const bf16_t* __restrict__ st2, int64_t s2_rs, int64_t s2_bs,
     float* __restrict__ lse2, const float* __restrict__ delta, int64_t stat_ld /* queries per (b, h) row of lse2 / delta */,
     bf16_t* __restrict__ out, int64_t out_rs, int64_t out_bs, int heads, int Lown, int Lst, int nOwn, float c, float scale) {
-    constexpr int RB = 2 * DH, NCH = DH / 8, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32, NT = 512, NST = (KVB * NCH) / NT;
-    constexpr bool OWN_Q = MODE == BWD_LSE || MODE == BWD_DQ;          // queries owned (statistics lane-local) or streamed
-    constexpr bool TWO = MODE == BWD_DQ || MODE == BWD_DK;             // second score-like product (dP)
-    constexpr int BUFSZ = 2 * TILE + (DMA ? 512 : 0);                      // DMA: + lse2[64] | delta[64] of the streamed rows (queries streamed)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][tile of st1 | tile of st2 (| statistics)]
+    constexpr int RB = 2 * DH, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32, NIW = BWD_NIW<DH>;
+    constexpr int BUFSZ = 2 * TILE + 512;      // the 512 bytes were the statistics slot (lse2[64] | delta[64]) of the streamed queries of the DK / DV modes: unused here, kept for the addresses
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][tile of st1 | tile of st2 | 512 unused bytes]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int ot = blockIdx.x % nOwn, bh = blockIdx.x / nOwn;
     const int head = bh % heads, b = bh / heads;
     const bf16_t* O1 = own1 + (int64_t)b * o1_bs + head * DH;
-    const bf16_t* O2 = TWO ? own2 + (int64_t)b * o2_bs + head * DH : nullptr;
+    const bf16_t* O2 = DQ ? own2 + (int64_t)b * o2_bs + head * DH : nullptr;
     const bf16_t* S1 = st1 + (int64_t)b * s1_bs + head * DH;
-    const bf16_t* S2 = (MODE != BWD_LSE) ? st2 + (int64_t)b * s2_bs + head * DH : nullptr;
+    const bf16_t* S2 = DQ ? st2 + (int64_t)b * s2_bs + head * DH : nullptr;
     const int own_row = ot * 256 + wave * 32 + r;
     const int own_ld = own_row < Lown ? own_row : Lown - 1;
-    bf16x8 f1[QS], f2[TWO ? QS : 1];
+    bf16x8 f1[QS], f2[DQ ? QS : 1];
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         f1[s] = *(const bf16x8*)(O1 + (int64_t)own_ld * o1_rs + 16 * s + 8 * h);
-        if constexpr (TWO) f2[s] = *(const bf16x8*)(O2 + (int64_t)own_ld * o2_rs + 16 * s + 8 * h);
+        if constexpr (DQ) f2[s] = *(const bf16x8*)(O2 + (int64_t)own_ld * o2_rs + 16 * s + 8 * h);
     }
     const float* stat_l = lse2 + (int64_t)bh * stat_ld;
-    const float* stat_d = (MODE == BWD_DQ || MODE == BWD_DK) ? delta + (int64_t)bh * stat_ld : nullptr;
+    const float* stat_d = DQ ? delta + (int64_t)bh * stat_ld : nullptr;
     float my_lse = 0.f, my_delta = 0.f;
-    if constexpr (MODE == BWD_DQ) { my_lse = stat_l[own_ld]; my_delta = stat_d[own_ld]; }
-    // staging: thread -> NST chunks of each streamed tile
-    int st_row[NST], st_ch[NST], st_off[NST];
-#pragma unroll
-    for (int u = 0; u < NST; ++u) {
-        const int cid = tid + NT * u;
-        st_row[u] = cid / NCH; st_ch[u] = cid % NCH;
-        st_off[u] = img_off<DH>(st_row[u], st_ch[u]);
-    }
-    u32x4 r1[DMA ? 1 : NST], r2[DMA ? 1 : NST];
-    // LDS-DMA staging (DMA): a tile image is NI runs of 1 KiB (RPI rows each), wave w owns runs w * NIW .. + NIW - 1 of both streamed tiles; the
-    // DMAs of tile t + 1 are issued at the top of tile t and waited for (vmcnt(0)) ahead of the barrier that ends it - no staging registers,
-    // no ds_write. The swizzle is applied on the source side as in the forward.
-    constexpr int RPI = 1024 / RB, NI = TILE / 1024, NIW = NI / 8;
+    if constexpr (DQ) { my_lse = stat_l[own_ld]; my_delta = stat_d[own_ld]; }
+    // LDS-DMA staging: the DMAs of tile t + 1 are issued at the top of tile t and waited for (vmcnt(0)) ahead of the barrier that ends it
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     unsigned d1o[NIW], d2o[NIW];
-#pragma unroll
-    for (int u = 0; u < NIW; ++u) {
-        const int row = (wv * NIW + u) * RPI + lane / NCH;
-        const int ch = (lane % NCH) ^ row_swz<DH>(row);
-        d1o[u] = (unsigned)(row * (int)s1_rs + ch * 8) * 2u;
-        d2o[u] = (unsigned)(row * (int)s2_rs + ch * 8) * 2u;
-    }
-    auto dma_stream = [&](const bf16_t* base, int64_t rs, const unsigned (&off)[NIW], int row0, unsigned dst) {
-        if (row0 + KVB <= Lst) {
-            const void* tb = uniform_ptr(base + (int64_t)row0 * rs);
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) glds16_off(tb, off[u], dst + u * 1024);
-        } else {                                       // ragged last tile: rows past the end re-read the last row (masked below)
-            int lane_r = lane;
-            asm volatile("" : "+v"(lane_r));
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) {
-                const int row = (wv * NIW + u) * RPI + lane_r / NCH;
-                const int ch = (lane_r % NCH) ^ row_swz<DH>(row);
-                int sr = row0 + row; if (sr > Lst - 1) sr = Lst - 1;
-                glds16_ptr(base + (int64_t)sr * rs + ch * 8, dst + u * 1024);
-            }
-        }
-    };
+    bwd_dma_offsets<DH>(wv, lane, s1_rs, s2_rs, d1o, d2o);
     auto stage_load = [&](int row0, int buf) {
-        if constexpr (DMA) {
-            const unsigned lb = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + buf * BUFSZ, l0 = lb + wv * NIW * 1024;
-            dma_stream(S1, s1_rs, d1o, row0, l0);
-            if constexpr (MODE != BWD_LSE) dma_stream(S2, s2_rs, d2o, row0, l0 + TILE);
-            if constexpr (!OWN_Q) {                    // the tile's 64 lse2 / delta values ride along (rows padded to a multiple of 64, zeros)
-                if (wv == 0) glds4_ptr(stat_l + row0 + lane, lb + 2 * TILE);
-                if (MODE == BWD_DK && wv == 1) glds4_ptr(stat_d + row0 + lane, lb + 2 * TILE + 256);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < NST; ++u) {
-                int row = row0 + st_row[u]; if (row > Lst - 1) row = Lst - 1;
-                r1[u] = *(const u32x4*)(S1 + (int64_t)row * s1_rs + st_ch[u] * 8);
-                if constexpr (MODE != BWD_LSE) r2[u] = *(const u32x4*)(S2 + (int64_t)row * s2_rs + st_ch[u] * 8);
-            }
-        }
+        const unsigned l0 = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + buf * BUFSZ + wv * NIW * 1024;
+        bwd_dma_stream<DH>(S1, s1_rs, d1o, row0, Lst, wv, lane, l0);
+        if constexpr (DQ) bwd_dma_stream<DH>(S2, s2_rs, d2o, row0, Lst, wv, lane, l0 + TILE);
     };
-    auto stage_write = [&](int buf) {
-        if constexpr (DMA) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-#pragma unroll
-            for (int u = 0; u < NST; ++u) {
-                *(u32x4*)(smem + buf * BUFSZ + st_off[u]) = r1[u];
-                if constexpr (MODE != BWD_LSE) *(u32x4*)(smem + buf * BUFSZ + TILE + st_off[u]) = r2[u];
-            }
-        }
-    };
-    // per-lane LDS read offsets: every swizzled offset is BASE ^ constant, re-derived from opaque copies of three bases (no per-fragment registers)
-    const int k_base = RB * r + 16 * (h ^ row_swz<DH>(r));                 // row fragment s of 32-row block kb: kb * 32 * RB + (k_base ^ 32 s)
+    auto stage_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+    // bwd_read_bases, spelled out: through the helper hipcc gives the LSE mode 112 / 110 registers (dh 128 / 64) instead of 97 / 82
+    const int k_base = RB * r + 16 * (h ^ row_swz<DH>(r));
     const int i16 = lane & 15, g16 = lane >> 4;
     const int t_key = 4 * h + (i16 >> 2), t_lowch = 2 * (g16 & 1) + ((i16 & 3) >> 1), t_b8 = 8 * (i16 & 1);
-    const int tlo_base = RB * t_key + 16 * (t_lowch ^ row_swz<DH>(t_key)) + t_b8;              // d-block db, k-step ks: ks * 16 * RB + (base ^ 64 db)
+    const int tlo_base = RB * t_key + 16 * (t_lowch ^ row_swz<DH>(t_key)) + t_b8;
     const int thi_base = RB * (t_key + 8) + 16 * (t_lowch ^ row_swz<DH>(t_key + 8)) + t_b8;
     // dh 128: the LDS reads of each matrix phase are software-pipelined by hand - the fragments of step j + PD are requested before the MFMAs
     // of step j (left to hipcc every MFMA pair sits right behind its own ds_read and s_waitcnt): 527 -> 548 TFLOP/s. At dh 64 (half the MFMAs
     // per read burst) the same pipeline measured 6 % slower than hipcc's order, which stays.
     constexpr bool PIPE = DH == 128;
     constexpr int PDS = 3, PDA = 1;
-    f32x16 acc[MODE == BWD_LSE ? 1 : NDB];
-    if constexpr (MODE != BWD_LSE) {
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[db][i] = 0.f;
-    }
+    f32x16 acc[DQ ? NDB : 1];
+    if constexpr (DQ) bwd_zero(acc);
     float m_run = -INFINITY, l_run = 0.f;
     const int ntiles = (Lst + KVB - 1) / KVB;
     stage_load(0, 0);
-    stage_write(0);
+    stage_wait();
     __syncthreads();
     for (int t = 0; t < ntiles; ++t) {
         const int cur = t & 1;
@@ -626,7 +627,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
         const unsigned char* B2 = B1 + TILE;
         bf16x8 zf[2][2];
         float tmax = -INFINITY;
-        f32x16 x1k[MODE == BWD_LSE ? 2 : 1];
+        f32x16 x1k[DQ ? 1 : 2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 x1, x2;
@@ -638,7 +639,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                 bf16x8 ab[PDS + 1][2];
                 auto rd = [&](int s5) {
                     ab[s5 % (PDS + 1)][0] = *(const bf16x8*)(B1 + kb * 32 * RB + (kb0 ^ (32 * s5)));
-                    if constexpr (TWO) ab[s5 % (PDS + 1)][1] = *(const bf16x8*)(B2 + kb * 32 * RB + (kb0 ^ (32 * s5)));
+                    if constexpr (DQ) ab[s5 % (PDS + 1)][1] = *(const bf16x8*)(B2 + kb * 32 * RB + (kb0 ^ (32 * s5)));
                 };
 #pragma unroll
                 for (int j = 0; j < PDS && j < QS; ++j) rd(j);
@@ -647,7 +648,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                     if (s5 + PDS < QS) rd(s5 + PDS);
                     __builtin_amdgcn_sched_barrier(0);
                     x1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab[s5 % (PDS + 1)][0], f1[s5], x1, 0, 0, 0);
-                    if constexpr (TWO) x2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab[s5 % (PDS + 1)][1], f2[s5], x2, 0, 0, 0);
+                    if constexpr (DQ) x2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab[s5 % (PDS + 1)][1], f2[s5], x2, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
@@ -655,7 +656,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                 for (int s5 = 0; s5 < QS; ++s5) {
                     const bf16x8 a1 = *(const bf16x8*)(B1 + kb * 32 * RB + (k_base ^ (32 * s5)));
                     x1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, f1[s5], x1, 0, 0, 0);
-                    if constexpr (TWO) {
+                    if constexpr (DQ) {
                         const bf16x8 a2 = *(const bf16x8*)(B2 + kb * 32 * RB + (k_base ^ (32 * s5)));
                         x2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, f2[s5], x2, 0, 0, 0);
                     }
@@ -663,7 +664,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
             }
             // streamed row of accumulator element i
             const int srow0 = t * KVB + kb * 32 + 4 * h;
-            if constexpr (MODE == BWD_LSE) {
+            if constexpr (!DQ) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     if (srow0 + (i & 3) + 8 * (i >> 2) >= Lst) x1[i] = -INFINITY;
@@ -672,45 +673,20 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                 x1k[kb] = x1;
             } else {
                 float z[16];
-                float sl[16], sd[16];
-                if constexpr (!OWN_Q && DMA) {         // statistics of the streamed rows from the LDS copy (broadcast reads), no global load in the loop
-                    const float* st = (const float*)(B1 + 2 * TILE);
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 a = *(const f32x4*)(st + kb * 32 + 4 * h + 8 * g);
-                        sl[4 * g] = a[0]; sl[4 * g + 1] = a[1]; sl[4 * g + 2] = a[2]; sl[4 * g + 3] = a[3];
-                        if constexpr (MODE == BWD_DK) {
-                            const f32x4 d4 = *(const f32x4*)(st + 64 + kb * 32 + 4 * h + 8 * g);
-                            sd[4 * g] = d4[0]; sd[4 * g + 1] = d4[1]; sd[4 * g + 2] = d4[2]; sd[4 * g + 3] = d4[3];
-                        }
-                    }
-                }
-                if constexpr (!OWN_Q && !DMA) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        int q0 = srow0 + 8 * g; if (q0 > (int)stat_ld - 4) q0 = (int)stat_ld - 4;       // stat rows are padded to a multiple of 64
-                        const f32x4 a = *(const f32x4*)(stat_l + q0);
-                        sl[4 * g] = a[0]; sl[4 * g + 1] = a[1]; sl[4 * g + 2] = a[2]; sl[4 * g + 3] = a[3];
-                        if constexpr (MODE == BWD_DK) {
-                            const f32x4 d4 = *(const f32x4*)(stat_d + q0);
-                            sd[4 * g] = d4[0]; sd[4 * g + 1] = d4[1]; sd[4 * g + 2] = d4[2]; sd[4 * g + 3] = d4[3];
-                        }
-                    }
-                }
-                // z = P (DV) or P (dP - delta) (DQ, DK: the softmax scale is applied once, to the accumulator, in the epilogue); rows past the
-                // end exist only in the ragged last tile
+                // z = P (dP - delta) (the softmax scale is applied once, to the accumulator, in the epilogue); keys past the end exist only in the
+                // ragged last tile
                 if (t * KVB + KVB <= Lst) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const float p = __builtin_amdgcn_exp2f(fmaf(x1[i], c, -(OWN_Q ? my_lse : sl[i])));
-                        z[i] = TWO ? p * (x2[i] - (OWN_Q ? my_delta : sd[i])) : p;
+                        const float p = __builtin_amdgcn_exp2f(fmaf(x1[i], c, -my_lse));
+                        z[i] = p * (x2[i] - my_delta);
                     }
                 } else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const bool valid = srow0 + (i & 3) + 8 * (i >> 2) < Lst;
-                        const float p = __builtin_amdgcn_exp2f(fmaf(x1[i], c, -(OWN_Q ? my_lse : sl[i])));
-                        const float v = TWO ? p * (x2[i] - (OWN_Q ? my_delta : sd[i])) : p;
+                        const float p = __builtin_amdgcn_exp2f(fmaf(x1[i], c, -my_lse));
+                        const float v = p * (x2[i] - my_delta);
                         z[i] = valid ? v : 0.f;
                     }
                 }
@@ -723,7 +699,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                 }
             }
         }
-        if constexpr (MODE == BWD_LSE) {
+        if constexpr (!DQ) {
             tmax = ug_max_halves(tmax);
             const float m_new = fmaxf(m_run, tmax);
             float sum = 0.f;
@@ -734,8 +710,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
             l_run = l_run * __builtin_amdgcn_exp2f((m_run - m_new) * c) + sum;
             m_run = m_new;
         } else {
-            // acc^T[d][own] += T^T[d][streamed] Z[streamed][own], T = st1 (DQ: K, DK: Q) or st2 (DV: dO)
-            const unsigned char* Tb = (MODE == BWD_DV) ? B2 : B1;
+            // dQ^T[d][query] += K^T[d][key] dS^T[key][query]
+            const unsigned char* Tb = B1;
             if constexpr (PIPE) {
                 int lo0 = tlo_base, hi0 = thi_base;
                 asm volatile("" : "+v"(lo0), "+v"(hi0));
@@ -764,29 +740,19 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_kernel(
                     }
             }
         }
-        if (t + 1 < ntiles) stage_write(cur ^ 1);
+        if (t + 1 < ntiles) stage_wait();
         __syncthreads();
     }
-    if constexpr (MODE == BWD_LSE) {
+    if constexpr (!DQ) {
         const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
         if (own_row < Lown && h == 0) lse2[(int64_t)bh * stat_ld + own_row] = __builtin_amdgcn_logf(l_tot) + m_run * c;     // v_log_f32 = log2
     } else if (own_row < Lown) {
-        bf16_t* Orow = out + (int64_t)b * out_bs + (int64_t)own_row * out_rs + head * DH;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const float es = TWO ? scale : 1.f;
-                u32x2 w;
-                w.x = pack2bf(acc[db][4 * g4 + 0] * es, acc[db][4 * g4 + 1] * es);
-                w.y = pack2bf(acc[db][4 * g4 + 2] * es, acc[db][4 * g4 + 3] * es);
-                *(u32x2*)(Orow + 32 * db + 8 * g4 + 4 * h) = w;
-            }
+        bwd_store_row(out + (int64_t)b * out_bs + (int64_t)own_row * out_rs + head * DH, acc, scale, h);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Fused dK / dV (round 3): the DK and DV modes above both recompute S = Q K^T over the same (keys, queries) - 8 product units per attention
+// Fused dK / dV (round 3): the key-owning DK and DV modes (tools/probe/csrc/attn_bwd_variants.hip) both recompute S = Q K^T over the same (keys, queries) - 8 product units per attention
 // against the minimum of 5. Fusing them on the 256-key ownership needs 128 accumulator + 64 owned-operand registers beside the score tiles:
 // over the 256 a two-wave-per-SIMD kernel has. This kernel splits the work of a 32-key block between the TWO waves of a pair instead:
 //   a workgroup owns 128 keys; waves p and p + 4 (p = 0..3) own the same 32 keys (K and V fragments in registers, key on the lane);
@@ -813,7 +779,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
     const bf16_t* __restrict__ qq, int64_t q_rs, int64_t q_bs, const bf16_t* __restrict__ dd, int64_t d_rs, int64_t d_bs,
     const float* __restrict__ lse2, const float* __restrict__ delta, int64_t stat_ld, bf16_t* __restrict__ dk, int64_t dk_rs, int64_t dk_bs,
     bf16_t* __restrict__ dv, int64_t dv_rs, int64_t dv_bs, int heads, int Lkv, int Lq, int nOwn, float c, float scale) {
-    constexpr int RB = 2 * DH, NCH = DH / 8, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32;
+    constexpr int RB = 2 * DH, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32, NIW = BWD_NIW<DH>;
     constexpr int BUFSZ = 2 * TILE + 512, NSTG = 3, ZOFF = NSTG * BUFSZ;   // [3][Q tile | dO tile | lse2[64] | delta[64]] then [2][8 waves] x 2 KiB of exchanged operands
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -839,49 +805,19 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
     // LDS-DMA staging as in attn_bwd_kernel (wave w owns runs w * NIW .. + NIW - 1 of both streamed tiles), but a ring of three stages: tile t + 2 is
     // requested right after the barrier of tile t (its stage was last read by the accumulation of tile t - 1, which every wave has left by then) and is
     // waited for ahead of the barrier of tile t + 1 - one barrier per tile certifies both the exchange and the landing.
-    constexpr int RPI = 1024 / RB, NI = TILE / 1024, NIW = NI / 8;
     unsigned d1o[NIW], d2o[NIW];
-#pragma unroll
-    for (int u = 0; u < NIW; ++u) {
-        const int row = (wave * NIW + u) * RPI + lane / NCH;
-        const int ch = (lane % NCH) ^ row_swz<DH>(row);
-        d1o[u] = (unsigned)(row * (int)q_rs + ch * 8) * 2u;
-        d2o[u] = (unsigned)(row * (int)d_rs + ch * 8) * 2u;
-    }
-    auto dma_stream = [&](const bf16_t* base, int64_t rs, const unsigned (&off)[NIW], int row0, unsigned dst) __attribute__((always_inline)) {
-        if (row0 + KVB <= Lq) {
-            const void* tb = uniform_ptr(base + (int64_t)row0 * rs);
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) glds16_off(tb, off[u], dst + u * 1024);
-        } else {                                       // ragged last tile: rows past the end re-read the last row (masked below)
-            int lane_r = lane;
-            asm volatile("" : "+v"(lane_r));
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) {
-                const int row = (wave * NIW + u) * RPI + lane_r / NCH;
-                const int ch = (lane_r % NCH) ^ row_swz<DH>(row);
-                int sr = row0 + row; if (sr > Lq - 1) sr = Lq - 1;
-                glds16_ptr(base + (int64_t)sr * rs + ch * 8, dst + u * 1024);
-            }
-        }
-    };
+    bwd_dma_offsets<DH>(wave, lane, q_rs, d_rs, d1o, d2o);
     auto stage_load = [&](int row0, int stg) __attribute__((always_inline)) {
         const unsigned lb = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + stg * BUFSZ, l0 = lb + wave * NIW * 1024;
-        dma_stream(Qb, q_rs, d1o, row0, l0);
-        dma_stream(Db, d_rs, d2o, row0, l0 + TILE);
+        bwd_dma_stream<DH>(Qb, q_rs, d1o, row0, Lq, wave, lane, l0);
+        bwd_dma_stream<DH>(Db, d_rs, d2o, row0, Lq, wave, lane, l0 + TILE);
         if (wave == 0) glds4_ptr(stat_l + row0 + lane, lb + 2 * TILE);          // the tile's 64 lse2 / delta values (rows padded to a multiple of 64, zeros)
         if (wave == 1) glds4_ptr(stat_d + row0 + lane, lb + 2 * TILE + 256);
     };
-    const int k_base = RB * r + 16 * (h ^ row_swz<DH>(r));                 // row fragment s of 32-row block kb: kb * 32 * RB + (k_base ^ 32 s)
-    const int i16 = lane & 15, g16 = lane >> 4;
-    const int t_key = 4 * h + (i16 >> 2), t_lowch = 2 * (g16 & 1) + ((i16 & 3) >> 1), t_b8 = 8 * (i16 & 1);
-    const int tlo_base = RB * t_key + 16 * (t_lowch ^ row_swz<DH>(t_key)) + t_b8;              // d-block db, k-step ks: ks * 16 * RB + (base ^ 64 db)
-    const int thi_base = RB * (t_key + 8) + 16 * (t_lowch ^ row_swz<DH>(t_key + 8)) + t_b8;
+    int k_base, tlo_base, thi_base;
+    bwd_read_bases<DH>(lane, k_base, tlo_base, thi_base);
     f32x16 acc[NDB];                                   // dK^T (half 0) or dV^T (half 1): [d][own key]
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[db][i] = 0.f;
+    bwd_zero(acc);
     const int ntiles = (Lq + KVB - 1) / KVB;
     stage_load(0, 0);
     if (ntiles > 1) stage_load(KVB, 1);
@@ -990,16 +926,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
     }
     if (own_row < Lkv) {
         bf16_t* Orow = (half ? dv + (int64_t)b * dv_bs + (int64_t)own_row * dv_rs : dk + (int64_t)b * dk_bs + (int64_t)own_row * dk_rs) + head * DH;
-        const float es = half ? 1.f : scale;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                u32x2 w;
-                w.x = pack2bf(acc[db][4 * g4 + 0] * es, acc[db][4 * g4 + 1] * es);
-                w.y = pack2bf(acc[db][4 * g4 + 2] * es, acc[db][4 * g4 + 3] * es);
-                *(u32x2*)(Orow + 32 * db + 8 * g4 + 4 * h) = w;
-            }
+        bwd_store_row(Orow, acc, half ? 1.f : scale, h);
     }
 }
 
@@ -1017,7 +944,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ kk, int64_t k_rs, int64_t k_bs, const bf16_t* __restrict__ vv, int64_t v_rs, int64_t v_bs,
     const float* __restrict__ lse2, const float* __restrict__ delta, int64_t stat_ld, bf16_t* __restrict__ dq, int64_t dq_rs, int64_t dq_bs,
     int heads, int Lq, int Lkv, int nOwn, float c, float scale) {
-    constexpr int RB = 2 * DH, NCH = DH / 8, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32;
+    constexpr int RB = 2 * DH, TILE = KVB * RB, QS = DH / 16, NDB = DH / 32, NIW = BWD_NIW<DH>;
     constexpr int BUFSZ = 2 * TILE;                    // [3][K tile | V tile]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1039,47 +966,17 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
         fo[s] = *(const bf16x8*)(Db + (int64_t)own_ld * d_rs + 16 * s + 8 * h);
     }
     const float my_lse = lse2[(int64_t)bh * stat_ld + own_ld], my_delta = delta[(int64_t)bh * stat_ld + own_ld];
-    constexpr int RPI = 1024 / RB, NI = TILE / 1024, NIW = NI / 8;
     unsigned d1o[NIW], d2o[NIW];
-#pragma unroll
-    for (int u = 0; u < NIW; ++u) {
-        const int row = (wave * NIW + u) * RPI + lane / NCH;
-        const int ch = (lane % NCH) ^ row_swz<DH>(row);
-        d1o[u] = (unsigned)(row * (int)k_rs + ch * 8) * 2u;
-        d2o[u] = (unsigned)(row * (int)v_rs + ch * 8) * 2u;
-    }
-    auto dma_stream = [&](const bf16_t* base, int64_t rs, const unsigned (&off)[NIW], int row0, unsigned dst) __attribute__((always_inline)) {
-        if (row0 + KVB <= Lkv) {
-            const void* tb = uniform_ptr(base + (int64_t)row0 * rs);
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) glds16_off(tb, off[u], dst + u * 1024);
-        } else {                                       // ragged last tile: rows past the end re-read the last key (masked below)
-            int lane_r = lane;
-            asm volatile("" : "+v"(lane_r));
-#pragma unroll
-            for (int u = 0; u < NIW; ++u) {
-                const int row = (wave * NIW + u) * RPI + lane_r / NCH;
-                const int ch = (lane_r % NCH) ^ row_swz<DH>(row);
-                int sr = row0 + row; if (sr > Lkv - 1) sr = Lkv - 1;
-                glds16_ptr(base + (int64_t)sr * rs + ch * 8, dst + u * 1024);
-            }
-        }
-    };
+    bwd_dma_offsets<DH>(wave, lane, k_rs, v_rs, d1o, d2o);
     auto stage_load = [&](int row0, int stg) __attribute__((always_inline)) {
         const unsigned l0 = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + stg * BUFSZ + wave * NIW * 1024;
-        dma_stream(Kb, k_rs, d1o, row0, l0);
-        dma_stream(Vb, v_rs, d2o, row0, l0 + TILE);
+        bwd_dma_stream<DH>(Kb, k_rs, d1o, row0, Lkv, wave, lane, l0);
+        bwd_dma_stream<DH>(Vb, v_rs, d2o, row0, Lkv, wave, lane, l0 + TILE);
     };
-    const int k_base = RB * r + 16 * (h ^ row_swz<DH>(r));
-    const int i16 = lane & 15, g16 = lane >> 4;
-    const int t_key = 4 * h + (i16 >> 2), t_lowch = 2 * (g16 & 1) + ((i16 & 3) >> 1), t_b8 = 8 * (i16 & 1);
-    const int tlo_base = RB * t_key + 16 * (t_lowch ^ row_swz<DH>(t_key)) + t_b8;
-    const int thi_base = RB * (t_key + 8) + 16 * (t_lowch ^ row_swz<DH>(t_key + 8)) + t_b8;
+    int k_base, tlo_base, thi_base;
+    bwd_read_bases<DH>(lane, k_base, tlo_base, thi_base);
     f32x16 acc[NDB];                                   // partial dQ^T [d][own query] over this wave's key blocks
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[db][i] = 0.f;
+    bwd_zero(acc);
     const int ntiles = (Lkv + KVB - 1) / KVB;
     stage_load(0, 0);
     if (ntiles > 1) stage_load(KVB, 1);
@@ -1266,6 +1163,57 @@ extern "C" int ug_flash_attn_fwd_lse(const void* q, int64_t q_row_stride, int64_
                                o_batch_stride, batches, heads, Lq, Lkv, dh, softmax_scale, lse2, lse_ld, stream);
 }
 
+// The three stages of the backward, in stream order: the rows' statistics (unless the forward supplied them), dQ, dK and dV. Every kernel takes
+// more than 64 KiB of dynamic LDS at head width 128: bwd_launch sets the attribute that allows it once per instantiation.
+template <auto KERNEL, typename... Args>
+static void bwd_launch(int64_t grid, int lds, hipStream_t s, Args... args) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(512), lds, s, args...);
+}
+static int64_t bwd_grid(const ug_attn_bwd_args& a, int L, int rows) { return (int64_t)((L + rows - 1) / rows) * a.heads * a.batches; }
+
+template <int DH>
+static void bwd_launch_lse(const ug_attn_bwd_args& a) {            // lse2 from Q and K: 256 queries per workgroup
+    bwd_launch<attn_bwd_kernel<DH, false>>(bwd_grid(a, a.Lq, 256), 2 * (2 * KVB * 2 * DH + 512), a.s, a.q, a.q_rs, a.q_bs, nullptr, 0, 0,
+                                           a.k, a.k_rs, a.k_bs, nullptr, 0, 0, a.lse2, a.delta, a.stat_ld, nullptr, 0, 0, a.heads, a.Lq, a.Lkv, (a.Lq + 255) / 256, a.c, a.scale);
+}
+#ifdef UG_PROBE_BUILD
+constexpr bool PAIR_DQ_64 = true;      // the probe library has the pair-scheme dQ kernel at head width 64 too (UG_ATTN_BWD_PAIR_DQ=2)
+#else
+constexpr bool PAIR_DQ_64 = false;     // product: pair_dq is only ever set at head width 128
+#endif
+template <int DH>
+static void bwd_launch_dq(const ug_attn_bwd_args& a, bool pair_dq) {
+    if constexpr (DH == 128 || PAIR_DQ_64) {
+        if (pair_dq) {                 // 128 queries per workgroup, [3][K tile | V tile]
+            bwd_launch<attn_bwd_dq_kernel<DH>>(bwd_grid(a, a.Lq, 128), 3 * (2 * KVB * 2 * DH), a.s, a.q, a.q_rs, a.q_bs, a.dout, a.do_rs, a.do_bs, a.k, a.k_rs, a.k_bs,
+                                               a.v, a.v_rs, a.v_bs, a.lse2, a.delta, a.stat_ld, a.dq, a.dq_rs, a.dq_bs, a.heads, a.Lq, a.Lkv, (a.Lq + 127) / 128,
+                                               a.c, a.scale);
+            return;
+        }
+    }
+    bwd_launch<attn_bwd_kernel<DH, true>>(bwd_grid(a, a.Lq, 256), 2 * (2 * KVB * 2 * DH + 512), a.s, a.q, a.q_rs, a.q_bs, a.dout, a.do_rs, a.do_bs, a.k, a.k_rs, a.k_bs,
+                                          a.v, a.v_rs, a.v_bs, a.lse2, a.delta, a.stat_ld, a.dq, a.dq_rs, a.dq_bs, a.heads, a.Lq, a.Lkv, (a.Lq + 255) / 256, a.c, a.scale);
+}
+template <int DH>
+static void bwd_launch_dkv(const ug_attn_bwd_args& a) {            // 128 keys per workgroup, [3][Q tile | dO tile | statistics] + the exchanged operands
+    bwd_launch<attn_bwd_dkv_kernel<DH>>(bwd_grid(a, a.Lkv, 128), 3 * (2 * KVB * 2 * DH + 512) + 2 * 8 * 2048, a.s, a.k, a.k_rs, a.k_bs, a.v, a.v_rs, a.v_bs, a.q, a.q_rs,
+                                        a.q_bs, a.dout, a.do_rs, a.do_bs, a.lse2, a.delta, a.stat_ld, a.dk, a.dk_rs, a.dk_bs, a.dv, a.dv_rs, a.dv_bs, a.heads,
+                                        a.Lkv, a.Lq, (a.Lkv + 127) / 128, a.c, a.scale);
+}
+template <int DH>
+static void bwd_stages(const ug_attn_bwd_args& a, bool need_lse, bool pair_dq) {
+#ifdef UG_PROBE_BUILD     // probe library: UG_ATTN_BWD_DMA=0 / UG_ATTN_BWD_FUSE_DKV=0 send a stage to the frozen template (tools/probe/csrc/attn_bwd_variants.hip)
+    const auto variant = [&](int stage) { return ug_attn_bwd_variants(stage, DH, a); };
+#else
+    const auto variant = [](int) { return false; };
+#endif
+    if (need_lse && !variant(UG_BWD_STAGE_LSE)) bwd_launch_lse<DH>(a);
+    if (!variant(UG_BWD_STAGE_DQ)) bwd_launch_dq<DH>(a, pair_dq);
+    if (!variant(UG_BWD_STAGE_DKV)) bwd_launch_dkv<DH>(a);
+}
+
 extern "C" int64_t ug_flash_attn_bwd_workspace_bytes(int64_t batches, int32_t heads, int64_t Lq) {
     if (batches <= 0 || heads <= 0 || Lq <= 0) return 0;
     return 2 * batches * heads * ((Lq + 63) / 64 * 64) * (int64_t)sizeof(float);
@@ -1292,22 +1240,19 @@ extern "C" int ug_flash_attn_bwd(const void* q, int64_t q_rs, int64_t q_bs, cons
     float* delta = (float*)workspace + batches * heads * stat_ld;
     hipStream_t s = (hipStream_t)stream;
     const float c = softmax_scale * 1.4426950408889634f;
-    const int bwd_dma = UG_TUNE("UG_ATTN_BWD_DMA", 1);     // LDS-DMA staging of the streamed tiles (0: through registers)
     const int nQ = (int)((Lq + 255) / 256), nK = (int)((Lkv + 255) / 256);
     const int64_t gq = (int64_t)nQ * heads * batches, gk = (int64_t)nK * heads * batches;
     UG_REQUIRE(gq < (1ll << 31) && gk < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: grid too large");
-    // fused dK / dV kernel (128 keys per workgroup; needs the LDS-DMA staging and equal row strides are NOT required); UG_ATTN_BWD_FUSE_DKV=0: the two modes
+    // fused dK / dV kernel: 128 keys per workgroup (equal row strides are NOT required)
     const int nK2 = (int)((Lkv + 127) / 128);
     const int64_t gk2 = (int64_t)nK2 * heads * batches;
     UG_REQUIRE(gk2 < (1ll << 31) && (int64_t)((Lq + 127) / 128) * heads * batches < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: grid too large");
-    const bool fuse_dkv = bwd_dma && UG_TUNE("UG_ATTN_BWD_FUSE_DKV", 1);
     // dQ on 128-query workgroups (attn_bwd_dq_kernel); UG_ATTN_BWD_PAIR_DQ=0: the 256-query DQ mode
-    const int nQ2 = (int)((Lq + 127) / 128);
-    const int64_t gq2 = (int64_t)nQ2 * heads * batches;
+    const int64_t gq2 = (int64_t)((Lq + 127) / 128) * heads * batches;
     // Measured (tools/attn_bwd_ab.py, profiles/r03y_attn_bwd_pair_dq.log): dh 128 at 4608^2 / 8704^2 +2.6 % / +2.5 % of the whole backward; dh 128 at
     // 1000^2 -7 %, dh 64 -3 % (half the MFMAs per wave and barrier) -> on by default only for head width 128 and >= 2048 queries (2 forces it everywhere)
     const int pdq = UG_TUNE("UG_ATTN_BWD_PAIR_DQ", 1);
-    const bool pair_dq = bwd_dma && gq2 < (1ll << 31) && (pdq == 2 || (pdq == 1 && dh == 128 && Lq >= 2048));
+    const bool pair_dq = gq2 < (1ll << 31) && (pdq == 2 || (pdq == 1 && dh == 128 && Lq >= 2048));
     (void)hipMemsetAsync(workspace, 0, (size_t)(2 * batches * heads * stat_ld) * sizeof(float), s);     // padded statistics rows read as 0
     const int64_t total = batches * Lq * heads;
     if (dh == 128)
@@ -1316,69 +1261,10 @@ extern "C" int ug_flash_attn_bwd(const void* q, int64_t q_rs, int64_t q_bs, cons
     else
         hipLaunchKernelGGL(attn_delta_kernel<64>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, s, (const bf16_t*)o, o_rs, o_bs, (const bf16_t*)dout, do_rs, do_bs,
                            delta, stat_ld, total, (int)heads, (int)Lq);
-#ifdef UG_PROBE_BUILD
-#define UG_BWD(DHV, MODEV, GRID, ...)                                                                                                                  \
-    do { if (bwd_dma) UG_BWD_(DHV, MODEV, true, GRID, __VA_ARGS__); else UG_BWD_(DHV, MODEV, false, GRID, __VA_ARGS__); } while (0)
-#define UG_BWD_SPLIT_DKV(DHV)                                                                                                                       \
-    do {                                                                                                                                            \
-        UG_BWD(DHV, BWD_DK, gk, k, k_rs, k_bs, v, v_rs, v_bs, q, q_rs, q_bs, dout, do_rs, do_bs, dk, dk_rs, dk_bs, Lkv, Lq, nK);                   \
-        UG_BWD(DHV, BWD_DV, gk, k, k_rs, k_bs, nullptr, 0, 0, q, q_rs, q_bs, dout, do_rs, do_bs, dv, dv_rs, dv_bs, Lkv, Lq, nK);                   \
-    } while (0)
-#else      /* product: LDS-DMA staging only; dK and dV always by the fused kernel (the two separate modes are probe-build variants) */
-#define UG_BWD(DHV, MODEV, GRID, ...) UG_BWD_(DHV, MODEV, true, GRID, __VA_ARGS__)
-#define UG_BWD_SPLIT_DKV(DHV) do { } while (0)
-#endif
-#define UG_BWD_(DHV, MODEV, DMAV, GRID, O1, O1R, O1B, O2, O2R, O2B, S1, S1R, S1B, S2, S2R, S2B, OUT, OR, OB, LOWN, LST, NOWN)                          \
-    do {                                                                                                                                                \
-        const int lds_ = 2 * (2 * KVB * 2 * DHV + (DMAV ? 512 : 0));                                                                                   \
-        static bool attr_ = false;        /* one per expansion site = per instantiation */                                                              \
-        if (!attr_) { (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<DHV, MODEV, DMAV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); attr_ = true; } \
-        hipLaunchKernelGGL((attn_bwd_kernel<DHV, MODEV, DMAV>), dim3((unsigned)(GRID)), dim3(512), lds_, s, (const bf16_t*)(O1), O1R, O1B, (const bf16_t*)(O2), O2R, O2B, \
-                           (const bf16_t*)(S1), S1R, S1B, (const bf16_t*)(S2), S2R, S2B, lse2, delta, stat_ld, (bf16_t*)(OUT), OR, OB, (int)heads, (int)(LOWN),   \
-                           (int)(LST), (int)(NOWN), c, softmax_scale);                                                                                 \
-    } while (0)
-#define UG_BWD_PAIR_DQ(DHV)                                                                                                                         \
-    do {                                                                                                                                            \
-        constexpr int ldsq_ = 3 * (2 * KVB * 2 * DHV);                                                                                              \
-        static bool attrq_ = false;                                                                                                                 \
-        if (!attrq_) { (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DHV>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsq_); attrq_ = true; } \
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DHV>), dim3((unsigned)gq2), dim3(512), ldsq_, s, (const bf16_t*)q, q_rs, q_bs, (const bf16_t*)dout, do_rs, do_bs, \
-                           (const bf16_t*)k, k_rs, k_bs, (const bf16_t*)v, v_rs, v_bs, lse2, delta, stat_ld, (bf16_t*)dq, dq_rs, dq_bs, (int)heads,        \
-                           (int)Lq, (int)Lkv, nQ2, c, softmax_scale);                                                                               \
-    } while (0)
-#define UG_BWD_PAIR_DQ_128() UG_BWD_PAIR_DQ(128)
-#ifdef UG_PROBE_BUILD
-#define UG_BWD_PAIR_DQ_64() UG_BWD_PAIR_DQ(64)
-#else      /* product: the pair-scheme dQ kernel only runs at head width 128 (pair_dq above); no head-width-64 instantiation */
-#define UG_BWD_PAIR_DQ_64() do { } while (0)
-#endif
-#define UG_BWD_ALL(DHV)                                                                                                                              \
-    do {                                                                                                                                              \
-        if (!lse_in) UG_BWD(DHV, BWD_LSE, gq, q, q_rs, q_bs, nullptr, 0, 0, k, k_rs, k_bs, nullptr, 0, 0, nullptr, 0, 0, Lq, Lkv, nQ);             \
-        if (pair_dq) {                                                                                                                             \
-            UG_BWD_PAIR_DQ_##DHV();                                                                                                                 \
-        } else {                                                                                                                                    \
-            UG_BWD(DHV, BWD_DQ, gq, q, q_rs, q_bs, dout, do_rs, do_bs, k, k_rs, k_bs, v, v_rs, v_bs, dq, dq_rs, dq_bs, Lq, Lkv, nQ);               \
-        }                                                                                                                                           \
-        if (fuse_dkv) {                                                                                                                            \
-            constexpr int lds_ = 3 * (2 * KVB * 2 * DHV + 512) + 2 * 8 * 2048;                                                                          \
-            static bool attr_ = false;                                                                                                              \
-            if (!attr_) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DHV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); attr_ = true; } \
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<DHV>), dim3((unsigned)gk2), dim3(512), lds_, s, (const bf16_t*)k, k_rs, k_bs, (const bf16_t*)v, v_rs, v_bs,  \
-                               (const bf16_t*)q, q_rs, q_bs, (const bf16_t*)dout, do_rs, do_bs, lse2, delta, stat_ld, (bf16_t*)dk, dk_rs, dk_bs, (bf16_t*)dv,   \
-                               dv_rs, dv_bs, (int)heads, (int)Lkv, (int)Lq, nK2, c, softmax_scale);                                                  \
-        } else {                                                                                                                                    \
-            UG_BWD_SPLIT_DKV(DHV);                                                                                                                  \
-        }                                                                                                                                           \
-    } while (0)
-    if (dh == 128) UG_BWD_ALL(128); else UG_BWD_ALL(64);
-#undef UG_BWD_ALL
-#undef UG_BWD_PAIR_DQ
-#undef UG_BWD_PAIR_DQ_128
-#undef UG_BWD_PAIR_DQ_64
-#undef UG_BWD_SPLIT_DKV
-#undef UG_BWD
-#undef UG_BWD_
+    const ug_attn_bwd_args a = {(const bf16_t*)q, q_rs, q_bs, (const bf16_t*)k, k_rs, k_bs, (const bf16_t*)v, v_rs, v_bs, (const bf16_t*)dout, do_rs, do_bs,
+                                (bf16_t*)dq, dq_rs, dq_bs, (bf16_t*)dk, dk_rs, dk_bs, (bf16_t*)dv, dv_rs, dv_bs, lse2, delta, stat_ld,
+                                batches, (int)heads, (int)Lq, (int)Lkv, c, softmax_scale, s};
+    if (dh == 128) bwd_stages<128>(a, !lse_in, pair_dq); else bwd_stages<64>(a, !lse_in, pair_dq);
     UG_CHECK_LAUNCH("ug_flash_attn_bwd");
     return UG_OK;
 }

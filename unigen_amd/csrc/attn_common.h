@@ -1,5 +1,5 @@
-// Device helpers shared by the attention kernels (attention.hip: the forward kernel and the backward kernels; tools/probe/csrc/attn_fwd_variants.hip:
-// the forward forms that lost their A/B): LDS-DMA issue in pointer and buffer form, the XOR-swizzled K/V tile image, transposed LDS reads and the
+// Device helpers shared by the attention kernels (attention.hip: the forward kernel and the backward kernels; tools/probe/csrc/attn_fwd_variants.hip,
+// attn_bwd_variants.hip: the forward and backward forms that lost their A/B): LDS-DMA issue in pointer and buffer form, the XOR-swizzled K/V tile image, transposed LDS reads and the
 // NaN-free max helpers. Sources that include this are built with -fno-honor-nans -mno-amdgpu-ieee (unigen_amd/build.py, EXTRA).
 #pragma once
 #include "ug_common.h"
@@ -10,6 +10,20 @@ int ug_attn_fwd_variants(const void* q, int64_t q_row_stride, int64_t q_batch_st
                          const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
                          int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale, float* lse_out, int64_t lse_ld,
                          ug_stream_t stream);
+#endif
+
+// what ug_flash_attn_bwd has validated and derived, for the launch helpers of its three stages
+struct ug_attn_bwd_args {
+    const bf16_t* q; int64_t q_rs, q_bs; const bf16_t* k; int64_t k_rs, k_bs; const bf16_t* v; int64_t v_rs, v_bs; const bf16_t* dout; int64_t do_rs, do_bs;
+    bf16_t* dq; int64_t dq_rs, dq_bs; bf16_t* dk; int64_t dk_rs, dk_bs; bf16_t* dv; int64_t dv_rs, dv_bs;
+    float* lse2; const float* delta; int64_t stat_ld;      // statistics rows [batches][heads][stat_ld]
+    int64_t batches; int heads, Lq, Lkv; float c /* scale * log2(e) */, scale; hipStream_t s;
+};
+enum { UG_BWD_STAGE_LSE = 0, UG_BWD_STAGE_DQ = 1, UG_BWD_STAGE_DKV = 2 };
+#ifdef UG_PROBE_BUILD
+// the backward forms that are not in the product (attn_bwd_variants.hip, probe library only): launches `stage` and returns true if the
+// UG_ATTN_BWD_DMA / UG_ATTN_BWD_FUSE_DKV switches send it to one of them, else returns false and the caller launches the shipped kernel
+bool ug_attn_bwd_variants(int stage, int dh, const ug_attn_bwd_args& a);
 #endif
 
 namespace {
