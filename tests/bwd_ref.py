@@ -51,11 +51,15 @@ def err(got: torch.Tensor, truth: torch.Tensor, mag=None, rows_from=None):
 # attention: S = q k^T, c = scale log2(e), lse2 = log2 sum_k 2^(c S), P = 2^(c S - lse2), O = P v;  backward with dO:
 # dP = dO v^T, delta = rowsum(dO . O) (O: the output the backward reads), dS = P (dP - delta), dq = scale dS k, dk = scale dS^T q, dv = P^T dO
 # ----------------------------------------------------------------------------------------------------------------------------------
-def attention(q, k, v, do, scale, o=None, lsum_bf16=False, backward=True):
+def attention(q, k, v, do, scale, o=None, lsum_bf16=False, backward=True, fwd_tile=64, fwd_lazy=8.0):
     """q, do [..., Lq, dh], k, v [..., Lkv, dh] (float64 holding the kernel's operands); o: the forward output the backward reads (the kernel's
     bf16 O), None = the exact O. Returns a dict of every intermediate plus the rounding-point variants:
       O_r   = bf16(bf16(p) v / l), p = 2^(c S - rowmax), l = sum p (lsum_bf16: sum bf16(p), the head-width-64 forward's denominator)
+      O_l   = the same roundings along flash_attn_kernel's own trajectory (forward_lazy below): its reference point is not the row maximum
+              (O_l and everything derived from it - moves, last_move, lse2_l, *_rl - are left out with fwd_tile=None)
+      moves, last_move [..., Lq]: how often a row's reference point moved, and the last key tile in which it did
       dq_r, dk_r, dv_r: P and dS rounded to bf16 as operands, the products exact, the results rounded to bf16
+      dq_rl, dk_rl, dv_rl: the same with P = 2^(c S - lse2_l), lse2_l the LSE the forward kernel itself leaves (forward_lazy)
       dq_m, dk_m: the same products with |dO| |v|^T + rowsum(|dO| |O|) in place of dP - delta (cancellation-free magnitude: the two fp32 dot
                   products and their difference are where a kernel's error is absolute, not relative)."""
     q, k, v, do = (t.to(F64) for t in (q, k, v, do))
@@ -70,6 +74,9 @@ def attention(q, k, v, do, scale, o=None, lsum_bf16=False, backward=True):
     pb = bf16(p)
     O_r = bf16((pb @ v) / (pb.sum(-1, keepdim=True) if lsum_bf16 else p.sum(-1, keepdim=True)))
     out = dict(S=S, lse2=lse2, P=P, O=O, O_r=O_r)
+    if fwd_tile is not None:
+        O_l, moves, last_move, lse2_l = forward_lazy(cs, v, lsum_bf16, fwd_tile, fwd_lazy)
+        out.update(O_l=O_l, moves=moves, last_move=last_move, lse2_l=lse2_l)
     if not backward:
         return out
     ob = O if o is None else o.to(F64)
@@ -82,7 +89,165 @@ def attention(q, k, v, do, scale, o=None, lsum_bf16=False, backward=True):
                dq=scale * dS @ k, dk=scale * dS.transpose(-1, -2) @ q, dv=P.transpose(-1, -2) @ do,
                dq_r=bf16(scale * dSb @ k), dk_r=bf16(scale * dSb.transpose(-1, -2) @ q), dv_r=bf16(Pb.transpose(-1, -2) @ do),
                dq_m=scale * dSm @ k, dk_m=scale * dSm.transpose(-1, -2) @ q)
+    if fwd_tile is None:
+        return out
+    # the same variants with P recomputed from the forward's own statistics lse2_l, as attn_bwd_dkv_kernel / attn_bwd_kernel do when the caller
+    # passes the forward's LSE (`lse_in`): at head width 64 that LSE is the log of a sum of bf16-rounded probabilities
+    Pl = torch.exp2(cs - lse2_l[..., None])
+    Plb, dSlb = bf16(Pl), bf16(Pl * (dP - delta[..., None]))
+    out.update(dq_rl=bf16(scale * dSlb @ k), dk_rl=bf16(scale * dSlb.transpose(-1, -2) @ q), dv_rl=bf16(Plb.transpose(-1, -2) @ do))
     return out
+
+
+def forward_lazy(cs, v, lsum_bf16=False, tile=64, lazy=8.0):
+    """The forward output with flash_attn_kernel's rounding points along the kernel's trajectory (csrc/attention.hip, do_SM); cs = c S
+    [..., Lq, Lkv] and v [..., Lkv, dh] in float64. Per row and `tile` keys: the reference point m becomes the tile's maximum in the first tile,
+    and later only where that maximum exceeds m by more than `lazy` (`up = (tmax - m_run) * c > 8.0f`; one maximum per row and tile: the kernel
+    joins its two lane halves, ug_max_halves); p = 2^(cs - m) (`exp2f(fmaf(s, c, -mc))`); bf16(p) multiplies v (`pack2bf`, the P.V operand);
+    the accumulator and l are rescaled by 2^(m_old - m_new) (`alpha`); l adds p, or bf16(p) with lsum_bf16 (LSUM: the head-width-64 row sums
+    come from the packed fragments); the output is bf16(acc / l). Everything else is float64.
+    -> (O_l, moves, last_move, lse2_l): moves [..., Lq] counts how often a row's m moved (the first tile included), last_move the last tile where
+    it did, lse2_l = m + log2(l) the statistics the kernel leaves for the backward (`lse_out[...] = logf(l_tot) + m_run * c`: with lsum_bf16 the
+    log of the sum of ROUNDED probabilities, off by up to 2^-9 / ln 2 on a peaked row)."""
+    cs, v = cs.to(F64), v.to(F64)
+    lead, Lkv = cs.shape[:-1], cs.shape[-1]
+    m = torch.full(lead, -math.inf, dtype=F64)
+    l = torch.zeros(lead, dtype=F64)
+    acc = torch.zeros(*lead, v.shape[-1], dtype=F64)
+    moves = torch.zeros(lead, dtype=torch.long)
+    last_move = torch.full(lead, -1, dtype=torch.long)
+    for t, k0 in enumerate(range(0, Lkv, tile)):
+        ct = cs[..., k0:k0 + tile]
+        tmax = ct.amax(-1)
+        up = (tmax - m) > lazy if t else torch.ones(lead, dtype=torch.bool)
+        m_new = torch.where(up, tmax, m)
+        alpha = torch.where(up, torch.exp2(m - m_new), torch.ones_like(m))
+        p = torch.exp2(ct - m_new[..., None])
+        pb = bf16(p)
+        acc = acc * alpha[..., None] + pb @ v[..., k0:k0 + tile, :]
+        l = l * alpha + (pb if lsum_bf16 else p).sum(-1)
+        m = m_new
+        moves += up
+        last_move = torch.where(up, torch.full_like(last_move, t), last_move)
+    return bf16(acc / l[..., None]), moves, last_move, m + torch.log2(l)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# attention regimes: operands whose softmax rows are peaked, so that the forward's lazy reference point moves in later tiles and the
+# backward kernels see probabilities near 1 (tests/test_attn_regimes_cpu.py checks what each regime promises)
+# ----------------------------------------------------------------------------------------------------------------------------------
+REGIMES = ("gaussian", "rising", "falling", "spike_tail", "spike_mid", "near_threshold", "one_key")
+BACKGROUND = 0.3            # standard deviation of c S over the background keys, in log2 units
+RAMP = 5.0                  # rising / falling: what a chosen row's tile maximum gains / loses per 64-key tile
+SPIKE = 14.0                # spike_tail / spike_mid: the spike key's c S in a chosen row, 12 above the rest (the background's maximum stays below 2)
+NEAR = (7.5, 8.5)           # near_threshold: the spike's gap over the row's reference point, below and above the kernel's 8
+NEAR_CLEAR = 0.05           # ... and how far from 8 every realised gap has to stay
+ONE_KEY = 20.0              # one_key: 2^-20 x ~1000 background keys leaves the dominant key more than 0.99
+SPIKE_POS = (1, 38, 29, 58)   # spike keys inside their 64-key tile: both 32-key blocks, key % 8 in 0..3 (1, 58) and in 4..7 (38, 29)
+
+
+def regime_fits(regime, Lq, Lkv):
+    """whether the regime can be built at these lengths"""
+    full, part = Lkv // 64, Lkv % 64
+    if regime in ("rising", "falling"):
+        return full >= 4
+    if regime == "spike_tail":
+        return part != 0 and full >= 1
+    if regime == "spike_mid":
+        return full >= (2 if part else 3) and Lq > 32
+    if regime == "near_threshold":
+        return full >= 2
+    return True
+
+
+def attention_regime(g, regime, dh, B, H, Lq, Lkv, scale):
+    """-> dict: q, do [B, H, Lq, dh] and k, v [B, H, Lkv, dh] in bf16; `rows`: the query rows the regime acts on; `keys`: the key rows it
+    spikes (None: all or none); `row_key` [len(rows)]: each chosen row's spike key; `row_gap`: its target. Amplitudes are in log2 units of
+    c S, c = scale log2(e): background q is drawn with standard deviation BACKGROUND / (c sqrt(dh)) against unit k, and both lose their
+    components along four orthonormal directions u_j. A chosen row of class j = (row // 4) % 4 gains w u_j / c and a key b u_j, so exactly that
+    pair's c S gains w b and every other score keeps its background value (up to the bf16 rounding of q and k).
+      gaussian        N(0, 1) operands, q times dh^-0.5 / scale: today's sweeps' scores at every scale
+      rising/falling  even rows; every key gains RAMP x (its tile's index, centred) along all four directions: the ramp is centred so that
+                      |scale S| stays below 40 at 17 tiles
+      spike_tail      rows 0, 4, 8, ...; one key per class in the partial last tile at SPIKE
+      spike_mid       the same in a full tile that is neither first nor last, in the even 32-row groups only: the odd groups have no spiking
+                      row (their waves skip the rescale), the even ones are mixed
+      near_threshold  rows 0, 4, 8, ...; spikes in the last full tile but one (the last full one if no other is left) whose gap over the
+                      row's first-tile maximum is NEAR[0] for the even classes, NEAR[1] for the odd ones: fitted on the float64 scores of
+                      the rounded operands, rows within NEAR_CLEAR of 8 are drawn again
+      one_key         rows 0, 4, 8, ...; the dominant key at ONE_KEY, in the first tile for classes 0 and 1, in the last tile for classes 2
+                      and 3 (the last but one where the tail is too short to hold the class's position)"""
+    assert regime in REGIMES and regime_fits(regime, Lq, Lkv), (regime, Lq, Lkv)
+    c = scale * LOG2E
+    rn = lambda *shape: torch.randn(*shape, generator=g, dtype=F64)
+    if regime == "gaussian":
+        q, k, v, do = rn(B, H, Lq, dh) * (dh ** -0.5 / scale), rn(B, H, Lkv, dh), rn(B, H, Lkv, dh), rn(B, H, Lq, dh)
+        none = torch.arange(0)
+        return dict(q=q.to(torch.bfloat16), k=k.to(torch.bfloat16), v=v.to(torch.bfloat16), do=do.to(torch.bfloat16), rows=none, keys=None,
+                    row_key=none, row_gap=none.to(F64))
+    U = torch.linalg.qr(rn(dh, 4))[0]                                  # [dh, 4] orthonormal columns
+    off = lambda t: t - (t @ U) @ U.T
+    sq = BACKGROUND / (c * math.sqrt(dh))
+    q, k, v, do = off(rn(B, H, Lq, dh) * sq), off(rn(B, H, Lkv, dh)), rn(B, H, Lkv, dh), rn(B, H, Lq, dh)
+    ntiles, part = (Lkv + 63) // 64, Lkv % 64
+    if regime in ("rising", "falling"):
+        rows = torch.arange(0, Lq, 2)
+        tile = (torch.arange(Lkv) // 64).to(F64) - (ntiles - 1) / 2
+        k = k + (RAMP * (tile if regime == "rising" else -tile))[:, None] * U.sum(1) / 2        # |sum of the four u_j| = 2
+        q[:, :, rows] += U.sum(1) / (2 * c)
+        return dict(q=q.to(torch.bfloat16), k=k.to(torch.bfloat16), v=v.to(torch.bfloat16), do=do.to(torch.bfloat16), rows=rows, keys=None,
+                    row_key=torch.arange(0), row_gap=torch.arange(0).to(F64))
+    rows = torch.arange(0, Lq, 4)
+    if regime == "spike_mid":
+        rows = rows[(rows // 32) % 2 == 0]
+    cls = (rows // 4) % 4
+    last = ntiles - 1
+    width = lambda t: min(64, Lkv - 64 * t)
+    at = lambda t, j: 64 * t + SPIKE_POS[j] % width(t)
+    if regime == "spike_tail":
+        key_of, gap_of = [at(last, j) for j in range(4)], [SPIKE] * 4
+    elif regime == "spike_mid":
+        mid = min(max(1, (last + 1) // 2), last - 1)
+        key_of, gap_of = [at(mid, j) for j in range(4)], [SPIKE] * 4
+    elif regime == "near_threshold":
+        full_last = last - 1 if part else last
+        late = full_last - 1 if full_last >= 2 else full_last
+        key_of, gap_of = [at(late, j) for j in range(4)], [NEAR[j % 2] for j in range(4)]
+    else:
+        later = [last if width(last) > SPIKE_POS[j] or last <= 1 else last - 1 for j in range(4)]      # at 65 keys: the one key of the tail
+        key_of, gap_of = [at(0, 0), at(0, 1), at(later[2], 2), at(later[3], 3)], [ONE_KEY] * 4
+    keys = torch.tensor(sorted(set(key_of)))
+    row_key = torch.tensor(key_of)[cls]
+    row_gap = torch.tensor(gap_of, dtype=F64)[cls]
+    amp = 4.0                                                           # key amplitude b; the row's weight is gap / b
+    for j in range(4):
+        k[:, :, key_of[j]] += amp * U[:, j]
+    k = bf16(k)
+    if regime != "near_threshold":
+        q[:, :, rows] += (row_gap / (amp * c))[:, None] * U[:, cls].T
+        return dict(q=q.to(torch.bfloat16), k=k.to(torch.bfloat16), v=v.to(torch.bfloat16), do=do.to(torch.bfloat16), rows=rows, keys=keys,
+                    row_key=row_key, row_gap=row_gap)
+    # near_threshold: the gap is what the kernel compares - the spike's c S minus the maximum of the row's first tile - on the ROUNDED operands.
+    # Fit every chosen row's weight to it (the gap is linear in the weight up to the rounding of q), then draw again what still sits near 8.
+    ks = k[:, :, row_key]                                               # [B, H, rows, dh] each chosen row's spike key
+    dirs = U[:, cls].T
+    w = (row_gap / amp).expand(B, H, -1).clone()
+    base = q[:, :, rows].clone()
+    for attempt in range(8):
+        for _ in range(4):
+            qr = bf16(base + (w / c)[..., None] * dirs)
+            gap = c * ((qr * ks).sum(-1) - (qr @ k[:, :, :64].transpose(-1, -2)).amax(-1))
+            w = w + (row_gap - gap) / amp
+        qr = bf16(base + (w / c)[..., None] * dirs)
+        gap = c * ((qr * ks).sum(-1) - (qr @ k[:, :, :64].transpose(-1, -2)).amax(-1))
+        bad = ((gap - 8.0).abs() <= NEAR_CLEAR) | ((gap - row_gap).abs() > 0.25)
+        if not bool(bad.any()):
+            break
+        base = torch.where(bad[..., None], off(rn(B, H, len(rows), dh) * sq), base)
+    assert not bool(bad.any()), "near_threshold: rows left within NEAR_CLEAR of the threshold"
+    q[:, :, rows] = qr
+    return dict(q=q.to(torch.bfloat16), k=k.to(torch.bfloat16), v=v.to(torch.bfloat16), do=do.to(torch.bfloat16), rows=rows, keys=keys,
+                row_key=row_key, row_gap=row_gap)
 
 
 def row_lse(S, scale, valid_cols=None):

@@ -79,15 +79,22 @@ def _attn_case(rng, dh, B, H, Lq, Lkv, joint=None):
                 pads=[8 * rng.choice([0, 1, 2, 3, 8]) for _ in range(8)], rpads=[rng.choice([0, 1, 5]) for _ in range(8)])
 
 
-def _run_attention(gpu, c, seed):
+def _run_attention(gpu, c, seed, data=None):
+    """Forward with LSE, then the backward with that LSE and with lse = NULL, on the layout c, against bwd_ref.attention. data None: N(0, 1)
+    operands drawn from `seed`, scale dh^-0.5, the forward bounded by the rounding-point variant O_r; returns whether the two backward runs
+    agree bit for bit. data (bwd_ref.attention_regime's dict: q, k, v, do as [B, H, L, dh] bf16): those operands with c["scale"], every other
+    element of the operand buffers - spare rows, pad columns, the key buffer's unused query columns - NaN, the forward bounded by the
+    lazy-reference-point variant O_l; returns what the regimes sweep checks further (tests/test_fuzz_attention_gpu.py)."""
     from unigen_amd import lib as L, ops
     B, H, dh, Lq, Lkv = c["B"], c["H"], c["dh"], c["Lq"], c["Lkv"]
-    D, scale = H * dh, dh ** -0.5
+    D, scale = H * dh, c.get("scale", dh ** -0.5)
     g = torch.Generator().manual_seed(seed)
     P, R = c["pads"], c["rpads"]
 
     def new(rows, width, i, fill=None):       # [B, rows + spare rows, width + spare columns]: batch stride padded by whole rows
         shape = (B, rows + R[i], width + P[i])
+        if fill is None and data is not None:
+            fill = float("nan")
         return torch.randn(*shape, generator=g).to(BF) if fill is None else torch.full(shape, fill, dtype=BF)
 
     spec = {}
@@ -104,6 +111,10 @@ def _run_attention(gpu, c, seed):
             spec["k"], spec["v"] = (new(Lkv, D, 1), 0, 0), (new(Lkv, D, 2), 0, 0)
     spec["o"] = (new(Lq, D, 3, SENT_O), 0, 0)
     spec["do"] = (new(Lq, D, 4), 0, 0)
+    if data is not None:
+        for n, rows in (("q", Lq), ("k", Lkv), ("v", Lkv), ("do", Lq)):
+            t, r0, c0 = spec[n]
+            t[:, r0:r0 + rows, c0:c0 + D] = data[n].transpose(1, 2).reshape(B, rows, D)
     on_gpu = {}
     for t, _, _ in spec.values():
         if id(t) not in on_gpu:
@@ -121,7 +132,7 @@ def _run_attention(gpu, c, seed):
     lse = torch.full((B, H, _pad64(Lq)), SENT_LSE, device=gpu, dtype=F32)
     (qv, q_rs, q_bs), (kv, k_rs, k_bs), (vv, v_rs, v_bs), (ov, o_rs, o_bs) = abi("q"), abi("k"), abi("v"), abi("o")
     ops.flash_attn(qv, kv, vv, ov, batches=B, heads=H, dh=dh, Lq=Lq, Lkv=Lkv, q_strides=(q_rs, q_bs), k_strides=(k_rs, k_bs), v_strides=(v_rs, v_bs),
-                   o_strides=(o_rs, o_bs), lse=lse)
+                   o_strides=(o_rs, o_bs), scale=scale, lse=lse)
     torch.cuda.synchronize()
     o_buf = on_gpu[id(spec["o"][0])]
     assert _sentinel_ok(o_buf, Lq, D, SENT_O), ("forward wrote outside its output", c)
@@ -147,8 +158,8 @@ def _run_attention(gpu, c, seed):
     # fp64 truth on the kernel's own operands; delta from the bf16 O the forward produced
     t = lambda n, rows: heads(spec[n][0], spec[n][1], spec[n][2], rows)
     o_k = heads(o_buf.cpu(), 0, 0, Lq)
-    ref = BR.attention(t("q", Lq), t("k", Lkv), t("v", Lkv), t("do", Lq), scale, o=o_k, lsum_bf16=dh == 64)
-    _check("forward O", o_k, ref["O"], c, var=ref["O_r"], rows_from=_tail(Lq))
+    ref = BR.attention(t("q", Lq), t("k", Lkv), t("v", Lkv), t("do", Lq), scale, o=o_k, lsum_bf16=dh == 64, fwd_tile=None if data is None else 64)
+    _check("forward O", o_k, ref["O"], c, var=ref["O_r" if data is None else "O_l"], rows_from=_tail(Lq))
     # base-2 LSE: fp32 scores and sums (2^-16 (1 + |lse2|) covers 256 fp32 ulps of the row sum); at head width 64 the row sum adds the bf16-rounded
     # probabilities P.V multiplies (each within 2^-9 of its value: |d log2 l| <= 2^-9 / ln 2)
     lse_k = lse[..., :Lq].double().cpu()
@@ -156,11 +167,34 @@ def _run_attention(gpu, c, seed):
     _check_elem("forward lse2", lse_k, ref["lse2"], tol, c)
     for mode, got in runs.items():
         for n, rows in (("dq", Lq), ("dk", Lkv), ("dv", Lkv)):
-            _check(f"bwd[{mode}] {n}", heads(got[n], 0, 0, rows), ref[n], dict(c, mode=mode), var=ref[n + "_r"], mag=ref.get(n + "_m"),
-                   rows_from=_tail(rows))
+            # regimes sweep: with the forward's LSE the kernels recompute P from it, so the variant does too (bwd_ref `*_rl`; at head width 64 that
+            # LSE is the log of a sum of bf16-rounded probabilities, which a peaked row does not average out)
+            var = ref[n + ("_rl" if data is not None and mode == "lse" else "_r")]
+            if var is not ref[n + "_r"]:
+                other = BR.err(ref[n + "_r"], ref[n], ref.get(n + "_m"), _tail(rows))
+                print(f"bwd[{mode}] {n}: 1.5 x the *_r variant (not asserted): rel-L2 {1.5 * other[0]:.3e}, worst row {1.5 * other[1]:.3e}, tail {1.5 * other[2]:.3e}")
+            _check(f"bwd[{mode}] {n}", heads(got[n], 0, 0, rows), ref[n], dict(c, mode=mode), var=var, mag=ref.get(n + "_m"), rows_from=_tail(rows))
     same = all(torch.equal(runs["lse"][n], runs["none"][n]) for n in ("dq", "dk", "dv"))
     print(f"attention {c}: backward with the forward's LSE and with lse=NULL bit-identical: {same}")
-    return same
+    if data is None:
+        return same
+
+    def forward_again(dtype):
+        """the forward without the LSE on the same operands widened to `dtype`, into a fresh sentinel-filled output -> that buffer (on the host)"""
+        cast = {i: t.to(dtype) for i, t in on_gpu.items()}
+        out = torch.full_like(cast[id(spec["o"][0])], SENT_O)
+
+        def view(name):
+            t, r0, c0 = spec[name]
+            return (out if name == "o" else cast[id(t)]).view(-1)[r0 * t.shape[2] + c0:]
+        ops.flash_attn(view("q"), view("k"), view("v"), view("o"), batches=B, heads=H, dh=dh, Lq=Lq, Lkv=Lkv, q_strides=(q_rs, q_bs),
+                       k_strides=(k_rs, k_bs), v_strides=(v_rs, v_bs), o_strides=(o_rs, o_bs), scale=scale)
+        torch.cuda.synchronize()
+        assert _sentinel_ok(out, Lq, D, SENT_O), ("forward wrote outside its output", str(dtype), c)
+        return out.cpu()
+
+    return dict(ref=ref, o=o_k, o_buf=o_buf.cpu(), runs={m: {n: heads(t, 0, 0, Lq if n == "dq" else Lkv) for n, t in r.items()} for m, r in runs.items()},
+                same=same, heads=heads, forward_again=forward_again, lse2=lse_k, k_rs=k_rs, v_rs=v_rs)
 
 
 @pytest.mark.parametrize("seed", range(40))

@@ -204,8 +204,10 @@ __global__ __launch_bounds__(512, DH == 128 ? 2 : 4) void flash_attn_kernel(
             for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, sacc[kb][i]);
         tmax = ug_max_halves(tmax);
         // Lazy reference point: a row's running max moves only when the tile maximum exceeds it by more than 2^8 in the exponent
-        // (softmax is shift-invariant; P and l stay below 2^8 per element: exact in fp32, same relative precision in bf16). With the
-        // exact max some row of the wave moves in most tiles and the 64-register rescale below ran nearly every iteration.
+        // (softmax is shift-invariant; P and l stay below 2^8 per element: exact in fp32, same relative precision in bf16 - a dominant
+        // probability then carries a bf16 rounding of its own, up to 2x the worst-row error of the exact maximum on such rows: measured in
+        // docs/PARITY_TOLERANCES.md, "Attention regimes sweep"). With the exact max some row of the wave moves in most tiles and the
+        // 64-register rescale below ran nearly every iteration.
         const bool up = (tmax - m_run) * c > 8.0f;
         const float m_new = up ? tmax : m_run;
         if (!__all(!up)) {
