@@ -588,6 +588,10 @@ int ug_gated_gelu_f32(const void* ab, int64_t ld, void* out, int64_t ldo, int64_
 /* y = x * sigmoid(1.702 x): CLIP-L's hidden_act "quick_gelu". n contiguous elements, a multiple of 8; y may alias x. */
 int ug_quick_gelu(const void* x, void* y, int64_t n, ug_stream_t stream);
 int ug_quick_gelu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
+/* y = 0.5 x (1 + erf(x / sqrt 2)): the exact GELU, hidden_act "gelu" (OpenCLIP bigG, SD3's second CLIP). Evaluated in fp32, the bf16 entry rounds once
+ * at the store. Same contract as ug_quick_gelu: n contiguous elements, a multiple of 8; y may alias x. */
+int ug_gelu_erf(const void* x, void* y, int64_t n, ug_stream_t stream);
+int ug_gelu_erf_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
 
 /* ---- image front end (csrc/image.hip; unigen_amd/image.py: VaeImageProcessor, canny; unigen_amd/condition.py - the reference builds its canny
  * condition with cv2.Canny(img, 100, 200) in src/condition.py:63-67 and sends every image through diffusers' VaeImageProcessor). Integer or exactly

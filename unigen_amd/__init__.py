@@ -6,7 +6,8 @@ __version__ = "0.1.0"
 
 # the training surface and the text encoders, imported on first use (importing the package itself needs neither torch nor the HIP library)
 _LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training_sigmas": "objective", "sample_density": "objective",
-         "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text"}
+         "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text", "CLIPTextModelWithProjection": "text",
+         "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text"}
 __all__ = sorted(_LAZY)
 
 

@@ -34,4 +34,4 @@ int ug_env_int(const char* name, int dflt) {
 }
 
 extern "C" const char* ug_last_error(void) { return g_err; }
-extern "C" int ug_version(void) { return 210; /* 0.2.1: text-encoder kernels (csrc/text.hip) */ }
+extern "C" int ug_version(void) { return 220; /* 0.2.2: ug_gelu_erf, the projected CLIP of SD3 (csrc/text.hip) */ }

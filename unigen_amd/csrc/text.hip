@@ -4,6 +4,7 @@
 //   ug_t5_rel_table          the [heads][2L - 1] table of that bias from block 0's relative_attention_bias.weight
 //   ug_rmsnorm_rows          T5LayerNorm;   ug_layernorm_rows   nn.LayerNorm with weight and bias
 //   ug_gated_gelu            gelu_new(a) * b over the two halves of the stacked [wi_0; wi_1] projection;   ug_quick_gelu   x sigmoid(1.702 x)
+//   ug_gelu_erf              0.5 x (1 + erf(x / sqrt 2)), the activation of SD3's second CLIP (OpenCLIP bigG)
 // and the `_f32` verification twin of each (fp32 storage, no intermediate rounding).
 //
 // The attention kernel is deliberately plain next to attention.hip's: at T5-XXL (512 tokens, 64 heads) attention is about 2 % of the encoder's
@@ -338,16 +339,30 @@ __global__ __launch_bounds__(256) void gated_gelu_kernel(const T* __restrict__ a
     E::store8(out + mrow * ldo + 8 * ch, y);
 }
 
-// y = x sigmoid(1.702 x) (CLIP-L's quick_gelu), contiguous, n a multiple of 8
-template <typename T>
-__global__ __launch_bounds__(256) void quick_gelu_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8) {
+// Contiguous activations between CLIP's fc1 and fc2, n a multiple of 8, one thread per 16-byte (bf16) / 2 x 16-byte (fp32) chunk; y may alias x.
+struct QuickGelu {             // y = x sigmoid(1.702 x): CLIP-L's "quick_gelu"
+    static __device__ __forceinline__ float f(float a) { return a / (1.0f + expf(-1.702f * a)); }
+};
+// y = 0.5 x (1 + erf(x / sqrt 2)): "gelu", OpenCLIP bigG's. Evaluated in fp32 as 0.5 x erfc(-x / sqrt 2) for x < 0 and 0.5 x (1 + erf(x / sqrt 2))
+// otherwise: the two are the same function, but 1 + erf cancels in the negative tail (absolute error 2^-24 |x|, the whole value from x = -5 on),
+// where erfc keeps its relative accuracy. Both forms stay at 0.09 of the test's bound (|err| <= 2^-20 |x|) with a correctly rounded erf; the
+// erfc tail is taken because it leaves the bf16 entry's single rounding as the only error of a small negative output.
+struct GeluErf {
+    static __device__ __forceinline__ float f(float a) {
+        const float u = a * 0.70710678118654752f;
+        return a < 0.0f ? 0.5f * a * erfcf(-u) : 0.5f * a * (1.0f + erff(u));
+    }
+};
+
+template <typename T, typename Act>
+__global__ __launch_bounds__(256) void act8_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8) {
     using E = ElemT<T>;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
     float a[8], r[8];
     E::load8(x + 8 * i, a);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = a[e] / (1.0f + expf(-1.702f * a[e]));
+    for (int e = 0; e < 8; ++e) r[e] = Act::f(a[e]);
     E::store8(y + 8 * i, r);
 }
 
@@ -405,15 +420,15 @@ static int gated_gelu_launch(const char* who, const void* ab, int64_t ld, void* 
     return UG_OK;
 }
 
-template <typename T>
-static int quick_gelu_launch(const char* who, const void* x, void* y, int64_t n, ug_stream_t stream) {
+template <typename T, typename Act>
+static int act8_launch(const char* who, const void* x, void* y, int64_t n, ug_stream_t stream) {
     if (n == 0) return UG_OK;
     UG_REQUIRE(x && y && n > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
     UG_REQUIRE(n % 8 == 0, UG_ERR_UNSUPPORTED, "%s: n = %lld must be a multiple of 8", who, (long long)n);
     UG_REQUIRE(ug_aligned(x, 16) && ug_aligned(y, 16), UG_ERR_BAD_ALIGN, "%s: tensors must be 16-byte aligned", who);
     const int64_t nblk = (n / 8 + 255) / 256;
     UG_REQUIRE(nblk < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: too many elements", who);
-    hipLaunchKernelGGL((quick_gelu_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n / 8);
+    hipLaunchKernelGGL((act8_kernel<T, Act>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n / 8);
     UG_CHECK_LAUNCH(who);
     return UG_OK;
 }
@@ -519,5 +534,7 @@ extern "C" int ug_gated_gelu(const void* ab, int64_t ld, void* out, int64_t ldo,
 extern "C" int ug_gated_gelu_f32(const void* ab, int64_t ld, void* out, int64_t ldo, int64_t M, int64_t F, ug_stream_t stream) {
     return gated_gelu_launch<float>("ug_gated_gelu_f32", ab, ld, out, ldo, M, F, stream);
 }
-extern "C" int ug_quick_gelu(const void* x, void* y, int64_t n, ug_stream_t stream) { return quick_gelu_launch<bf16_t>("ug_quick_gelu", x, y, n, stream); }
-extern "C" int ug_quick_gelu_f32(const void* x, void* y, int64_t n, ug_stream_t stream) { return quick_gelu_launch<float>("ug_quick_gelu_f32", x, y, n, stream); }
+extern "C" int ug_quick_gelu(const void* x, void* y, int64_t n, ug_stream_t stream) { return act8_launch<bf16_t, QuickGelu>("ug_quick_gelu", x, y, n, stream); }
+extern "C" int ug_quick_gelu_f32(const void* x, void* y, int64_t n, ug_stream_t stream) { return act8_launch<float, QuickGelu>("ug_quick_gelu_f32", x, y, n, stream); }
+extern "C" int ug_gelu_erf(const void* x, void* y, int64_t n, ug_stream_t stream) { return act8_launch<bf16_t, GeluErf>("ug_gelu_erf", x, y, n, stream); }
+extern "C" int ug_gelu_erf_f32(const void* x, void* y, int64_t n, ug_stream_t stream) { return act8_launch<float, GeluErf>("ug_gelu_erf_f32", x, y, n, stream); }

@@ -161,6 +161,7 @@ SIGNATURES.update({
     "ug_layernorm_rows": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, f32, vp]),
     "ug_gated_gelu": (i32, [vp, i64, vp, i64, i64, i64, vp]),
     "ug_quick_gelu": (i32, [vp, vp, i64, vp]),
+    "ug_gelu_erf": (i32, [vp, vp, i64, vp]),
 })
 # image front end (csrc/image.hip): integer / exactly specified fp32 arithmetic, no fp32 twins
 SIGNATURES.update({
@@ -176,7 +177,7 @@ SIGNATURES.update({
     "ug_img_chw_to_u8": (i32, [vp, i32, i64, i32, i64, i64, vp, i64, i64, i32, vp]),
 })
 _F32_TWINS = {"ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
-              "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu",
+              "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu", "ug_gelu_erf_f32": "ug_gelu_erf",
               "ug_flow_noise_f32": "ug_flow_noise", "ug_flow_loss_f32": "ug_flow_loss", "ug_flow_loss_bwd_f32": "ug_flow_loss_bwd",
               "ug_lora_wgrad_f32": "ug_lora_wgrad_bf16","ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",
               "ug_adaln_modulate_bwd_f32": "ug_adaln_modulate_bwd", "ug_qk_rmsnorm_rope_bwd_f32": "ug_qk_rmsnorm_rope_bwd",

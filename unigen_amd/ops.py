@@ -931,6 +931,16 @@ def quick_gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     return out
 
 
+def gelu_erf(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """0.5 x (1 + erf(x / sqrt 2)), contiguous; out may be x itself."""
+    dt = _act(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "out", dt)
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
+    L.check(_fn("ug_gelu_erf", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_gelu_erf")
+    return out
+
+
 # ---- image front end (csrc/image.hip): uint8 NHWC [B, H, W, C] tensors, byte strides per sample and per row -------------------------------------------
 u8 = torch.uint8
 

@@ -408,11 +408,16 @@ def sd3_denoise_loop(transformer, *, latents: torch.Tensor, control_latents: tor
 
 
 class UniGenSD3Pipeline:
-    """Call-surface twin of the reference `UniGenSD3Pipeline` for the transformer side (encoders / VAE out of scope, as above)."""
+    """Call-surface twin of the reference `UniGenSD3Pipeline`: the denoise loop runs here, prompts are encoded by the attached native text
+    encoders (unigen_amd.text) or by an attached `encode_prompt` callable; the VAE is delegated as in UniGenFLUXPipeline."""
 
     def __init__(self, transformer=None, scheduler_config: Optional[dict] = None, vae_scale_factor: int = 8, encode_prompt=None, vae=None,
-                 image_processor=None):
+                 image_processor=None, text_encoder=None, text_encoder_2=None, text_encoder_3=None, tokenizer=None, tokenizer_2=None, tokenizer_3=None):
         self.transformer = transformer
+        # native text encoders (unigen_amd.text: two CLIPTextModelWithProjection, T5EncoderModel or None), used when no `encode_prompt` callable is
+        # attached; without tokenizers a prompt is the triple (CLIP-L token ids [B, 77], CLIP-G token ids [B, 77], T5 token ids [B, L])
+        self.text_encoder, self.text_encoder_2, self.text_encoder_3 = text_encoder, text_encoder_2, text_encoder_3
+        self.tokenizer, self.tokenizer_2, self.tokenizer_3 = tokenizer, tokenizer_2, tokenizer_3
         self.vae_scale_factor = vae_scale_factor
         self.default_sample_size = 128
         sc = dict(shift=3.0, use_dynamic_shifting=False, base_image_seq_len=256, max_image_seq_len=4096, base_shift=0.5, max_shift=1.15)
@@ -424,12 +429,24 @@ class UniGenSD3Pipeline:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, transformer=None, **kwargs) -> "UniGenSD3Pipeline":
-        return cls(transformer=transformer)
+        names = ("encode_prompt", "vae", "image_processor", "text_encoder", "text_encoder_2", "text_encoder_3", "tokenizer", "tokenizer_2", "tokenizer_3")
+        return cls(transformer=transformer, **{k: kwargs.get(k) for k in names})
 
     def to(self, device=None, dtype=None):
         if self.transformer is not None:
             self.transformer.to(device=device, dtype=dtype)
         return self
+
+    def _native_prompt(self, what: str, prompt):
+        """-> (tokenizers, prompt, text_input_ids_list) for unigen_amd.text's SD3 functions: text goes through the attached tokenizers; without them
+        `prompt` must be the triple of token-id tensors (the T5 entry may be None when there is no third encoder)."""
+        tokenizers = [self.tokenizer, self.tokenizer_2, self.tokenizer_3]
+        if all(t is not None for t, e in zip(tokenizers, (self.text_encoder, self.text_encoder_2, self.text_encoder_3)) if e is not None):
+            return tokenizers, prompt, None
+        if not (isinstance(prompt, (list, tuple)) and len(prompt) == 3 and all(isinstance(t, torch.Tensor) for t in prompt[:2])
+                and (isinstance(prompt[2], torch.Tensor) or (prompt[2] is None and self.text_encoder_3 is None))):
+            raise TypeError(f"`{what}`: no tokenizers are attached, so it must be the triple of token ids (CLIP-L [B, 77], CLIP-G [B, 77], T5 [B, L])")
+        return [None, None, None], None, list(prompt)
 
     def prepare_image(self, image, width, height, batch_size, num_images_per_prompt, device, dtype, do_classifier_free_guidance=False, guess_mode=False):
         """The reference's method of the same name (src/UniGenPipeline.py:107-141): as UniGenFLUXPipeline.prepare_image, then the batch doubled for
@@ -454,15 +471,40 @@ class UniGenSD3Pipeline:
                  condition_pooled_prompt_embeds=None, output_type: str = "latent", return_dict: bool = True, gate_uniforms=None,
                  num_images_per_prompt: int = 1, control_use_vae_shift_factor: bool = True, sigmas=None, mu: Optional[float] = None,
                  control_guidance_start=0.0, control_guidance_end=1.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",), **kwargs):
+                 callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",), prompt_2=None, prompt_3=None, negative_prompt=None,
+                 negative_prompt_2=None, negative_prompt_3=None, clip_skip: Optional[int] = None, max_sequence_length: int = 256, **kwargs):
         tr = self.transformer
         dev = tr.device
         cast = lambda t: t.to(device=dev, dtype=tr.dtype)
         cfg_on = guidance_scale > 1.0
-        if prompt is not None or condition_prompt is not None:
+        native = self.encode_prompt is None and self.text_encoder is not None and self.text_encoder_2 is not None
+        if native:
+            # passed embeds win; otherwise unigen_amd.text's restatement of StableDiffusion3Pipeline.encode_prompt / encode_condition_prompt (:246-284)
+            from .text import encode_condition_prompt_sd3, encode_prompt_sd3
+            encoders = [self.text_encoder, self.text_encoder_2, self.text_encoder_3]
+            common = dict(num_images_per_prompt=num_images_per_prompt, clip_skip=clip_skip, max_sequence_length=max_sequence_length, device=dev,
+                          joint_attention_dim=tr.config.joint_attention_dim)
+            if prompt is not None and prompt_embeds is None:
+                tokenizers, text, ids = self._native_prompt("prompt", prompt)
+                need_neg = cfg_on and negative_prompt_embeds is None
+                if ids is None:                                                  # text: the negatives default to "" inside
+                    texts = dict(prompt_2=prompt_2, prompt_3=prompt_3, negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2,
+                                 negative_prompt_3=negative_prompt_3)
+                else:                                                            # token ids: the negatives come as a triple through `negative_prompt`
+                    neg_ids = self._native_prompt("negative_prompt", negative_prompt)[2] if need_neg and negative_prompt is not None else None
+                    texts = dict(text_input_ids_list=ids, negative_text_input_ids_list=neg_ids)
+                prompt_embeds, neg_embeds, pooled_prompt_embeds, neg_pooled = encode_prompt_sd3(encoders, tokenizers, text, do_classifier_free_guidance=need_neg,
+                                                                                                **texts, **common)
+                if need_neg:
+                    negative_prompt_embeds, negative_pooled_prompt_embeds = neg_embeds, neg_pooled
+            if condition_prompt is not None and condition_pooled_prompt_embeds is None:
+                tokenizers, text, ids = self._native_prompt("condition_prompt", condition_prompt)
+                condition_pooled_prompt_embeds = encode_condition_prompt_sd3(encoders, tokenizers, text, text_input_ids_list=ids, **common)[1]
+        elif prompt is not None or condition_prompt is not None:
             if self.encode_prompt is None:
                 raise NotImplementedError("prompts given as text but no text encoder is attached: set `pipe.encode_prompt` (StableDiffusion3Pipeline.encode_prompt "
-                                          "signature; CLIP/T5 are outside this package), or pass the embeds")
+                                          "signature), attach `pipe.text_encoder`, `pipe.text_encoder_2` (CLIPTextModelWithProjection) and `pipe.text_encoder_3` "
+                                          "(T5EncoderModel or None) of unigen_amd.text, or pass the embeds")
             if prompt is not None:
                 prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
                     prompt=prompt, prompt_2=None, prompt_3=None, do_classifier_free_guidance=cfg_on, device=dev, num_images_per_prompt=num_images_per_prompt)[:4]

@@ -1,10 +1,12 @@
 """Text encoders on the HIP library: the T5 encoder and the CLIP text model that the reference calls through src/text_encoder.py
-(train.py:381-395, :523-569; the top of every pipeline call), and `encode_prompt` itself.
+(train.py:381-395, :523-569; the top of every pipeline call), and `encode_prompt` itself; for the SD3 pipeline the projected CLIP
+(`CLIPTextModelWithProjection`: CLIP-L and OpenCLIP bigG, src/utils.py:16-19) and `encode_prompt_sd3` / `encode_condition_prompt_sd3`
+(src/UniGenPipeline.py:34-105, :246-290).
 
 Both classes take token ids and run entirely on libunigen_hip.so: the embedding is ug_gather_rows, every projection ug_gemm_bf16 (q | k | v and
 wi_0 | wi_1 packed into one weight each, the residual sums in the GEMM epilogue), attention ug_flash_attn_fwd_bias (T5: relative-position
 bias table, no 1/sqrt(dh) scale; CLIP: causal mask), the norms ug_rmsnorm_rows / ug_layernorm_rows, the activations ug_gated_gelu /
-ug_quick_gelu (csrc/text.hip). Parameters in fp32 run the same orchestration through the `_f32` verification twins. No attention mask is applied
+ug_quick_gelu / ug_gelu_erf (csrc/text.hip). Parameters in fp32 run the same orchestration through the `_f32` verification twins. No attention mask is applied
 (the reference passes none: padding tokens are attended to). There is no tokenizer here: callers pass token ids (the reference's
 `text_input_ids` path) or attach a tokenizer callable of their own. There is no backward: the reference freezes both encoders.
 """
@@ -30,6 +32,16 @@ class TextEncoderOutput:
 
     def __getitem__(self, i):
         return tuple(t for t in (self.last_hidden_state, self.pooler_output, self.hidden_states) if t is not None)[i]
+
+
+class CLIPTextModelOutput:
+    """`out[0]` / `out.text_embeds`, `out.last_hidden_state`, `out.hidden_states` (transformers' CLIPTextModelOutput surface)."""
+
+    def __init__(self, text_embeds, last_hidden_state, hidden_states=None):
+        self.text_embeds, self.last_hidden_state, self.hidden_states = text_embeds, last_hidden_state, hidden_states
+
+    def __getitem__(self, i):
+        return tuple(t for t in (self.text_embeds, self.last_hidden_state, self.hidden_states) if t is not None)[i]
 
 
 def _read_config_and_weights(path: str, subfolder: Optional[str]):
@@ -218,13 +230,16 @@ class CLIPTextModel(_PackedModel):
 
     KEYS = ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings", "hidden_act", "layer_norm_eps",
             "eos_token_id", "vocab_size")
+    ACTS = _CLIP_ACTS                                   # the hidden_act values this class takes
+    DROPPED = ("vision_model.", "visual_projection.", "text_projection.", "logit_scale")    # checkpoint entries from_pretrained leaves out
 
     def __init__(self, config: dict, device=None, dtype=BF):
         super().__init__(device, dtype)
         c = dict(hidden_act="quick_gelu", layer_norm_eps=1e-5, eos_token_id=2, max_position_embeddings=77)
         c.update({k: config[k] for k in self.KEYS if k in config})
-        if c["hidden_act"] not in _CLIP_ACTS:
-            raise NotImplementedError(f"CLIPTextModel: hidden_act = {c['hidden_act']!r} is not implemented (one of {_CLIP_ACTS}; erf-GELU, CLIP-G's, is a follow-up)")
+        if c["hidden_act"] not in self.ACTS:
+            raise NotImplementedError(f"{type(self).__name__}: hidden_act = {c['hidden_act']!r} is not implemented (one of {self.ACTS}; erf-GELU, "
+                                      "'gelu', is CLIPTextModelWithProjection's)")
         if c["hidden_size"] // c["num_attention_heads"] != 64:
             raise NotImplementedError("CLIPTextModel: the causal attention kernel has head width 64")
         self.config = c
@@ -267,7 +282,7 @@ class CLIPTextModel(_PackedModel):
         cfg, sd = _read_config_and_weights(path, subfolder)
         cfg = cfg.get("text_config", cfg) if "hidden_size" not in cfg else cfg
         m = cls(cfg, device=device, dtype=dtype)
-        m.load_state_dict({k: v for k, v in sd.items() if not k.startswith(("vision_model.", "visual_projection.", "text_projection.", "logit_scale"))})
+        m.load_state_dict({k: v for k, v in sd.items() if not k.startswith(cls.DROPPED)})
         return m
 
     def layer(self, x: torch.Tensor, i: int, B: int, Lq: int) -> torch.Tensor:
@@ -285,6 +300,9 @@ class CLIPTextModel(_PackedModel):
         if c["hidden_act"] == "quick_gelu":
             f = ops.gemm(h, p["fc1"], p["fc1_b"], new(c["intermediate_size"]), M=M)
             ops.quick_gelu(f, f)
+        elif c["hidden_act"] == "gelu":                 # the erf form (CLIPTextModelWithProjection only): a pass of its own, like quick_gelu
+            f = ops.gemm(h, p["fc1"], p["fc1_b"], new(c["intermediate_size"]), M=M)
+            ops.gelu_erf(f, f)
         else:                                           # the tanh form: the GEMM's own GELU epilogue
             f = ops.gemm(h, p["fc1"], p["fc1_b"], new(c["intermediate_size"]), M=M, epilogue=L.EPI_BIAS_GELU)
         return ops.gemm(f, p["fc2"], p["fc2_b"], new(D), M=M, epilogue=L.EPI_RES_SCALE, residual=x, alpha=1.0)
@@ -311,6 +329,37 @@ class CLIPTextModel(_PackedModel):
         rows = (torch.arange(B, device=self._device) * Lq + where).to(torch.int32)
         pooled = ops.gather_rows(last, rows, torch.empty(B, D, dtype=self._dtype, device=self._device))
         return TextEncoderOutput(last.view(B, Lq, D), pooled, tuple(t.view(B, Lq, D) for t in hidden) if output_hidden_states else None)
+
+    forward = __call__
+
+
+class CLIPTextModelWithProjection(CLIPTextModel):
+    """transformers' CLIPTextModelWithProjection on token ids: CLIPTextModel plus `text_projection` (no bias) on the pooled row. SD3's two CLIPs:
+    CLIP-L (quick_gelu) and OpenCLIP bigG (hidden_act "gelu", the erf form; width 1280 = 20 heads of 64)."""
+
+    KEYS = CLIPTextModel.KEYS + ("projection_dim",)
+    ACTS = _CLIP_ACTS + ("gelu",)
+    DROPPED = ("vision_model.", "visual_projection.", "logit_scale")
+
+    def __init__(self, config: dict, device=None, dtype=BF):
+        super().__init__(config, device=device, dtype=dtype)
+        self.config.setdefault("projection_dim", 512)   # transformers' default
+        self.proj = self._pack([("text_projection.weight", self.config["projection_dim"])], self.config["hidden_size"])
+
+    def _canon(self, key):
+        if key.endswith("text_projection.weight"):      # beside text_model.* on disk, not under it
+            return key if key == "text_projection.weight" else None
+        return super()._canon(key)
+
+    def state_dict(self, prefix: str = "text_model.") -> Dict[str, torch.Tensor]:
+        return {(k if k == "text_projection.weight" else prefix + k): v for k, v in self._views.items()}
+
+    @torch.no_grad()
+    def __call__(self, input_ids: torch.Tensor, output_hidden_states: bool = False, **_ignored) -> CLIPTextModelOutput:
+        out = super().__call__(input_ids, output_hidden_states=output_hidden_states)
+        pooled = out.pooler_output
+        embeds = ops.small_linear(pooled, self.proj, None, torch.empty(pooled.shape[0], self.proj.shape[0], dtype=self._dtype, device=self._device))
+        return CLIPTextModelOutput(embeds, out.last_hidden_state, out.hidden_states)
 
     forward = __call__
 
@@ -359,3 +408,84 @@ def encode_prompt(text_encoders, tokenizers, prompt, max_sequence_length, device
     embeds = embeds.repeat(1, n, 1).view(B * n, Lq, -1)
     text_ids = torch.zeros(Lq, 3, device=dev5, dtype=dtype)
     return embeds, pooled, text_ids
+
+
+# ---- SD3: three encoders (diffusers' StableDiffusion3Pipeline.encode_prompt; the reference's encode_condition_prompt) ------------------------------
+def _sd3_clip(clip, tokenizer, prompt, ids, n: int, clip_skip: Optional[int], device):
+    """One projected CLIP -> (hidden_states[-2] or [-(clip_skip + 2)] as [B n, 77, hidden], text_embeds [B n, projection_dim]). The sequence repeats
+    with the copies of a prompt adjacent, the pooled vector as a block: diffusers' `repeat(1, n, 1)` on a 3-D and on a 2-D tensor."""
+    ids = _input_ids(tokenizer, prompt, ids, 77)
+    B = ids.shape[0]
+    dev = device if device is not None else clip.device
+    out = clip(ids.to(dev), output_hidden_states=True)
+    pooled = out[0].to(dtype=clip.dtype, device=dev)
+    seq = out.hidden_states[-2 if clip_skip is None else -(clip_skip + 2)].to(dtype=clip.dtype, device=dev)
+    return seq.repeat(1, n, 1).view(B * n, seq.shape[1], -1), pooled.repeat(1, n, 1).view(B * n, -1)
+
+
+def _sd3_embeds(text_encoders, tokenizers, prompts, ids, n: int, clip_skip, max_sequence_length: int, device, joint_attention_dim):
+    """-> (prompt_embeds [B n, 77 + L3, joint_attention_dim], pooled [B n, projection_dim_l + projection_dim_g]) of one prompt triple."""
+    seq_l, pooled_l = _sd3_clip(text_encoders[0], tokenizers[0], prompts[0], ids[0], n, clip_skip, device)
+    seq_g, pooled_g = _sd3_clip(text_encoders[1], tokenizers[1], prompts[1], ids[1], n, clip_skip, device)
+    clip_seq = torch.cat([seq_l, seq_g], dim=-1)
+    t5 = text_encoders[2] if len(text_encoders) > 2 else None
+    if t5 is None:
+        if joint_attention_dim is None:
+            raise ValueError("joint_attention_dim must be given when there is no third text encoder (its rows are zeros of that width)")
+        t5_seq = torch.zeros(clip_seq.shape[0], max_sequence_length, joint_attention_dim, device=clip_seq.device, dtype=clip_seq.dtype)
+    else:
+        dev = device if device is not None else t5.device
+        t5_ids = _input_ids(tokenizers[2], prompts[2], ids[2], max_sequence_length)
+        t5_seq = t5(t5_ids.to(dev))[0].to(dtype=t5.dtype, device=dev)
+        t5_seq = t5_seq.repeat(1, n, 1).view(t5_seq.shape[0] * n, t5_seq.shape[1], -1)
+    if clip_seq.shape[-1] > t5_seq.shape[-1]:
+        raise ValueError(f"the two CLIP widths ({clip_seq.shape[-1]} together) exceed the T5 width {t5_seq.shape[-1]}")
+    clip_seq = torch.nn.functional.pad(clip_seq, (0, t5_seq.shape[-1] - clip_seq.shape[-1]))
+    return torch.cat([clip_seq, t5_seq], dim=-2), torch.cat([pooled_l, pooled_g], dim=-1)
+
+
+def _triple(x, what: str):
+    x = [None, None, None] if x is None else list(x)
+    if len(x) != 3:
+        raise ValueError(f"{what}: expected three entries (CLIP-L, CLIP-G, T5), got {len(x)}")
+    return x
+
+
+def encode_prompt_sd3(text_encoders, tokenizers, prompt, prompt_2=None, prompt_3=None, negative_prompt=None, negative_prompt_2=None,
+                      negative_prompt_3=None, do_classifier_free_guidance: bool = True, num_images_per_prompt: int = 1, clip_skip: Optional[int] = None,
+                      max_sequence_length: int = 256, device=None, text_input_ids_list=None, negative_text_input_ids_list=None,
+                      joint_attention_dim: Optional[int] = None):
+    """diffusers' StableDiffusion3Pipeline.encode_prompt on text_encoders = [clip_l, clip_g, t5 or None] (the CLIPs are CLIPTextModelWithProjection),
+    tokenizers likewise (entries may be None: then text_input_ids_list = [ids_l [B, 77], ids_g [B, 77], ids_t5 [B, L]] carries the token ids, and
+    negative_text_input_ids_list the negatives'). Returns (prompt_embeds [B n, 77 + L3, joint_attention_dim], negative_prompt_embeds, pooled_prompt_embeds
+    [B n, projection_dim_l + projection_dim_g], negative_pooled_prompt_embeds); the negatives are None without classifier-free guidance.
+
+    Each CLIP gives hidden_states[-2] (or [-(clip_skip + 2)]) and its projected pooled vector; the two sequences, side by side and zero-padded to the T5
+    width, come in front of the T5 rows of prompt_3 (zeros [B n, max_sequence_length, joint_attention_dim] without a T5)."""
+    n = num_images_per_prompt
+    text_encoders, tokenizers = _triple(text_encoders, "text_encoders"), _triple(tokenizers, "tokenizers")
+    ids, neg_ids = _triple(text_input_ids_list, "text_input_ids_list"), _triple(negative_text_input_ids_list, "negative_text_input_ids_list")
+    prompts = [prompt, prompt_2 if prompt_2 is not None else prompt, prompt_3 if prompt_3 is not None else prompt]
+    if do_classifier_free_guidance and any(text_encoders[i] is not None and tokenizers[i] is None and neg_ids[i] is None for i in range(3)):
+        raise ValueError("negative_text_input_ids_list must be provided for classifier-free guidance when the tokenizers are not specified")
+    embeds, pooled = _sd3_embeds(text_encoders, tokenizers, prompts, ids, n, clip_skip, max_sequence_length, device, joint_attention_dim)
+    if not do_classifier_free_guidance:
+        return embeds, None, pooled, None
+    B = embeds.shape[0] // n
+    neg = negative_prompt if negative_prompt is not None else ""
+    negs = [neg, negative_prompt_2 if negative_prompt_2 is not None else neg, negative_prompt_3 if negative_prompt_3 is not None else neg]
+    negs = [B * [p] if isinstance(p, str) else list(p) for p in negs]
+    if any(len(p) != B for p in negs):
+        raise ValueError(f"negative prompts: batch sizes {[len(p) for p in negs]} do not match the prompt's {B}")
+    # the negatives never take clip_skip (diffusers passes clip_skip=None for them)
+    neg_embeds, neg_pooled = _sd3_embeds(text_encoders, tokenizers, negs, neg_ids, n, None, max_sequence_length, device, joint_attention_dim)
+    return embeds, neg_embeds, pooled, neg_pooled
+
+
+def encode_condition_prompt_sd3(text_encoders, tokenizers, prompt, num_images_per_prompt: int = 1, clip_skip: Optional[int] = None,
+                                max_sequence_length: int = 256, device=None, text_input_ids_list=None, joint_attention_dim: Optional[int] = None):
+    """The reference's UniGenSD3Pipeline.encode_condition_prompt (src/UniGenPipeline.py:34-105): the same assembly for the condition prompt (one text
+    for all three encoders), no negatives. Returns (prompt_embeds, pooled_prompt_embeds)."""
+    text_encoders, tokenizers = _triple(text_encoders, "text_encoders"), _triple(tokenizers, "tokenizers")
+    return _sd3_embeds(text_encoders, tokenizers, [prompt] * 3, _triple(text_input_ids_list, "text_input_ids_list"), num_images_per_prompt, clip_skip,
+                       max_sequence_length, device, joint_attention_dim)
