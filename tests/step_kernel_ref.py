@@ -476,7 +476,22 @@ TS_CASES = [dict(B=B, dim=dim, slack=s, id=f"B{B}-dim{dim}-ld+{s}") for B, dim, 
             [(1, 2, 0), (5, 64, 0), (64, 256, 0), (1, 320, 8), (5, 1024, 3), (64, 2, 1), (5, 256, 64), (64, 320, 0), (1, 1024, 0), (64, 64, 5)]]
 
 
+# The guidance embedders feed the same kernel with `guidance.to(bf16) * 1000` (in bf16): 1000, 3504, 7008, 29952 for scales 1, 3.5, 7, 30 - arguments up
+# to 30 x the largest timestep. dim = 256 (the embedders' width), B in {1, 5}. torch's own fp32 constant on these cases is 9.06 (re-measured by
+# tests/test_step_kernel_ref_cpu.py), within TS_C_TORCH: the bound of TS_CASES holds here unchanged, scaled by the larger |t f|.
+TS_GUIDANCE = [1.0, 3.5, 7.0, 30.0]
+TS_GUIDANCE_CASES = [dict(B=B, dim=256, slack=s, guidance=True, id=f"guidance-B{B}-dim256-ld+{s}") for B, s in [(1, 0), (5, 0), (5, 8)]]
+
+
+def ts_guidance_times(B: int):
+    """float(bf16(g) * 1000 in bf16) for g in TS_GUIDANCE, cycled to B entries and starting at the largest for B = 1"""
+    t = (torch.tensor(TS_GUIDANCE, dtype=BF) * 1000).to(F32)
+    return t.flip(0).repeat(-(-B // len(TS_GUIDANCE)))[:B].contiguous()
+
+
 def ts_times(c):
+    if c.get("guidance"):
+        return ts_guidance_times(c["B"])
     g = torch.Generator().manual_seed(c["B"] * 7 + c["dim"])
     t = torch.tensor((TS_T * 11)[:c["B"]], dtype=F32)
     if c["B"] > len(TS_T):

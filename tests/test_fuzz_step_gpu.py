@@ -297,7 +297,7 @@ def test_transpose(gpu, c, dt):
 # timestep embedding, small linear
 # ----------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("c", SR.TS_CASES, ids=_ids(SR.TS_CASES))
+@pytest.mark.parametrize("c", SR.TS_CASES + SR.TS_GUIDANCE_CASES, ids=_ids(SR.TS_CASES + SR.TS_GUIDANCE_CASES))
 def test_timestep_embed(gpu, c, dt):
     B, dim, ldo = c["B"], c["dim"], c["dim"] + c["slack"]
     t = SR.ts_times(c)

@@ -146,6 +146,13 @@ def test_recorded_torch_figures():
         truth, a = SR.timestep_embed64(t, c["dim"])
         c_ts = max(c_ts, float(((SR.timestep_embed_torch32(t, c["dim"]).double() - truth).abs() / (SR.EPS32 * a.clamp_min(1.0))).max()))
     _recorded("timestep_embed c", c_ts, SR.TS_C_TORCH)
+    # the guidance-sized arguments (up to 29952): torch's constant there is within the recorded one, so TS_GUIDANCE_CASES use the same bound
+    c_gd = 0.0
+    for c in SR.TS_GUIDANCE_CASES:
+        t = SR.ts_times(c)
+        truth, a = SR.timestep_embed64(t, c["dim"])
+        c_gd = max(c_gd, float(((SR.timestep_embed_torch32(t, c["dim"]).double() - truth).abs() / (SR.EPS32 * a.clamp_min(1.0))).max()))
+    _recorded("timestep_embed c at guidance arguments", c_gd, SR.TS_C_TORCH)
     c_g = 0.0
     for c in SR.flat_cases("gelu"):
         x, _ = SR.flat_data(c, F32, big=True)
@@ -213,6 +220,10 @@ def test_cases_meet_the_documented_preconditions():
     assert {p - r for _, r, _, p, *_ in SR.TRANSPOSE_CASES} >= {0, 1, 7, 8, 63} and {c for _, _, c, *_ in SR.TRANSPOSE_CASES} >= {8, 72, 130}
     assert all(c["B"] > 0 and c["dim"] % 2 == 0 and c["dim"] > 0 for c in SR.TS_CASES) and {c["dim"] for c in SR.TS_CASES} == {2, 64, 256, 320, 1024}
     assert all(set(SR.ts_times(c).tolist()[:6]) <= {SR.f32(v) for v in SR.TS_T} for c in SR.TS_CASES)
+    assert {(c["B"], c["dim"]) for c in SR.TS_GUIDANCE_CASES} == {(1, 256), (5, 256)} and any(c["slack"] for c in SR.TS_GUIDANCE_CASES)
+    want = [float(torch.tensor(g, dtype=SR.BF) * 1000) for g in SR.TS_GUIDANCE]
+    assert want == [1000.0, 3504.0, 7008.0, 29952.0] and SR.ts_times(SR.TS_GUIDANCE_CASES[0]).tolist() == want[-1:]
+    assert all(set(SR.ts_times(c).tolist()) == set(want) for c in SR.TS_GUIDANCE_CASES if c["B"] >= 4)
     assert all(0 < c[0] <= 64 and c[1] > 0 and c[2] > 0 for c in SR.LINEAR_CASES)
     hs = set()
     for mode in SR.OPT_MODES:
@@ -336,6 +347,17 @@ def test_mutations_pack_transpose_timestep_linear():
         _rejects(lambda: SR.judge_bounded("timestep: freq shift 1", _image(torch.cat([a1.cos(), a1.sin()], 1), m, dt), truth, bound, m))
         for k, img in _image_slips(torch.full(m.shape, SR.SENT, dtype=dt), good, m).items():
             _rejects(lambda: SR.judge_bounded(f"timestep: {k}", img, truth, bound, m))
+        # guidance-sized arguments: the same bound accepts torch's fp32 evaluation and still separates the slips below at |t f| up to 29952
+        c = SR.TS_GUIDANCE_CASES[2]
+        t = SR.ts_times(c)
+        truth, a = SR.timestep_embed64(t, c["dim"])
+        _, _, m = SR.guarded(c["B"], c["dim"], c["dim"] + c["slack"], dt)
+        bound = SR.timestep_bound(a, truth, dt)
+        SR.judge_bounded("timestep, guidance", _image(SR.timestep_embed_torch32(t, c["dim"]), m, dt), truth, bound, m)
+        shifted, _ = SR.timestep_embed64(t * (1 + 2.0 ** -17), c["dim"])
+        _rejects(lambda: SR.judge_bounded("timestep, guidance: argument rounded to 18 bits", _image(shifted, m, dt), truth, bound, m))
+        plain, _ = SR.timestep_embed64(torch.tensor([1000.0 * g_ for g_ in (SR.TS_GUIDANCE[::-1] * 2)[:c["B"]]], dtype=F32), c["dim"])
+        _rejects(lambda: SR.judge_bounded("timestep, guidance: the scale not rounded to bf16 (3500, 7000, 30000)", _image(plain, m, dt), truth, bound, m))
     c = SR.LINEAR_CASES[1]
     x, W, b, Rr = SR.linear_data(c)
     truth = SR.small_linear64(x, W, b, Rr, True)

@@ -14,6 +14,10 @@ BF = torch.bfloat16
 TINY = dict(num_layers=2, num_single_layers=2, attention_head_dim=128, num_attention_heads=2, joint_attention_dim=64, pooled_projection_dim=64)
 CONTROL = dict(use_rope=True, use_shared_expert=True, use_single_trans_blocks=True, single_control_dev=2, single_block_control_method="overall_add",
                top_num=1, expert_num_each_condition=3)
+# test_control_module_gradients_match_oracle_autograd's tolerances (shared with tests/test_guidance_gpu.py). fp32 twins vs the fp32 oracle's autograd:
+# the forward, the loss, all gradients together, the worst single parameter. bf16: e_hip <= GRAD_BF16[0] * e_ref + GRAD_BF16[1], and the loss.
+F32_FORWARD, F32_LOSS, F32_GRADS, F32_WORST_PARAM = 1e-4, 1e-5, 1e-3, 5e-3
+GRAD_BF16, BF16_LOSS = (1.5, 5e-3), 3e-2
 
 
 def _dev(v, gpu, dt=None):
@@ -32,14 +36,17 @@ def _step(fwd, target, dtype):
     return out.detach(), float(loss), extra
 
 
-@pytest.mark.parametrize("n_cond,cls_name,top_num", [(1, "UniGenFlux", 1), (2, "MultiCondtionUniGenFlux", 1), (1, "UniGenFlux", 2), (1, "UniGenFlux", 3)])
-def test_control_module_gradients_match_oracle_autograd(gpu, n_cond, cls_name, top_num):
-    """top_num = 2: deepspeed top2gating - the gradient reaches the gate through BOTH kept probabilities and their normalising sum. top_num = 3:
-    topkgating (no random draw) - through all kept probabilities of a token and their sum."""
+def check_control_module_gradients(gpu, n_cond, cls_name, top_num, guidance=None, **cfg_over):
+    """The body of test_control_module_gradients_match_oracle_autograd, shared with tests/test_guidance_gpu.py (`cfg_over`: config entries on top
+    of TINY, `guidance`: a [B] tensor handed to both forwards) so that both state one set of tolerances. Asserts the fp32-twin and the bf16 parity
+    and returns what it measured: the trainable names, the dead ones, and the gradients {name: tensor or None} of the fp32 oracle, the fp32 twins,
+    the bf16 oracle and the bf16 product path, with `z(d, k)` (a gradient as an fp32 CPU tensor, zeros for None) and the per-parameter `floor`."""
     import importlib
     cls = getattr(importlib.import_module("src.UniGenTransformer"), cls_name)
     B, grid, T = 2, 8, 64                     # N = 64 image tokens, every joint length a multiple of 64 (attention backward contraction lengths)
     CONTROL = dict(globals()["CONTROL"], top_num=top_num)
+    TINY = dict(globals()["TINY"], **cfg_over)
+    tag = f"train_{cls_name}_k{top_num}" + ("_guidance" if guidance is not None else "")
     rcfg = R.FluxConfig(condition_nums=n_cond, top_num=top_num, **TINY)
     base = cls.from_config(dict(TINY), device=gpu, dtype=BF)
     base.init_condition_block(condition_nums=n_cond, condition_types=["canny", "depth"][:n_cond], control_params=dict(CONTROL))
@@ -56,10 +63,12 @@ def test_control_module_gradients_match_oracle_autograd(gpu, n_cond, cls_name, t
     base.init_trainable_param()
     names = [n for n, p in base.named_parameters() if p.requires_grad]
     assert any(n.startswith("control_joint_trans_blocks.") for n in names) and not any(n.startswith("transformer_blocks.") for n in names)
+    gkw = {} if guidance is None else dict(guidance=guidance)
+    gkw_dev = {} if guidance is None else dict(guidance=guidance.to(gpu))
 
     def oracle_grads(dtype):
         st = {k: (v.to(dtype).clone().requires_grad_(True) if k in names else v.to(dtype)) for k, v in state.items()}
-        out, loss, _ = _step(lambda: R.unigen_flux_forward(st, rcfg, timestep=t, dtype=dtype, **inp), target, dtype)
+        out, loss, _ = _step(lambda: R.unigen_flux_forward(st, rcfg, timestep=t, dtype=dtype, **gkw, **inp), target, dtype)
         return out, loss, {k: st[k].grad for k in names}
 
     def hip_grads(dtype):
@@ -68,7 +77,9 @@ def test_control_module_gradients_match_oracle_autograd(gpu, n_cond, cls_name, t
         model.load_state_dict({k: v.to(dtype) for k, v in state.items()})
         model.init_trainable_param()
         kw = {k: _dev(v, gpu, dtype if k != "gate_uniform" and not k.endswith("_ids") else None) for k, v in inp.items()}
-        out, loss, extra = _step(lambda: model(timestep=t.to(gpu), **kw), target, dtype)
+        out, loss, extra = _step(lambda: model(timestep=t.to(gpu), **gkw_dev, **kw), target, dtype)
+        frozen = [k for k, p in model.named_parameters() if not p.requires_grad and p.grad is not None]
+        assert not frozen, f"frozen parameters received a gradient: {frozen[:4]}"
         return out, loss, {k: model.get_parameter(k).grad for k in names}, extra
 
     truth_out, truth_loss, truth = oracle_grads(torch.float32)
@@ -82,21 +93,29 @@ def test_control_module_gradients_match_oracle_autograd(gpu, n_cond, cls_name, t
     rel = lambda a, b: float((a - b).norm() / b.norm())
     # fp32 verification path
     out32, loss32, g32, _ = hip_grads(torch.float32)
-    m = report(f"train_{cls_name}_k{top_num}_f32_forward", out32, truth_out)
+    m = report(f"{tag}_f32_forward", out32, truth_out)
     e_all = rel(cat(g32), cat(truth))
     floor = 1e-3 * float(cat(truth).norm()) / len(names) ** 0.5          # gradients that are themselves rounding noise (e.g. a key bias) do not count
     worst = max((float((z(g32, k) - truth[k]).norm() / max(float(truth[k].norm()), floor)), k) for k in live)
     assert all(float(z(g32, k).abs().max()) == 0.0 for k in dead), "a parameter behind a discarded output received a gradient"
     print(f"training fp32: loss {loss32:.6f} vs {truth_loss:.6f}; all gradients rel_l2 {e_all:.3e}; worst parameter {worst[1]} {worst[0]:.3e}")
-    assert m["rel_l2"] <= 1e-4 and abs(loss32 - truth_loss) <= 1e-5 * abs(truth_loss) + 1e-7 and e_all <= 1e-3 and worst[0] <= 5e-3, (m, e_all, worst)
+    assert m["rel_l2"] <= F32_FORWARD and abs(loss32 - truth_loss) <= F32_LOSS * abs(truth_loss) + 1e-7 and e_all <= F32_GRADS and worst[0] <= F32_WORST_PARAM, (m, e_all, worst)
     # bf16 product path vs the oracle's own bf16 autograd
     ref_out, ref_loss, gref = oracle_grads(BF)
     out16, loss16, g16, extra = hip_grads(BF)
     e_hip, e_ref = rel(cat(g16), cat(truth)), rel(cat(gref), cat(truth))
     print(f"training bf16: loss {loss16:.5f} (oracle bf16 {ref_loss:.5f}, fp32 {truth_loss:.5f}); gradients vs fp32: hip {e_hip:.3e}, oracle bf16 {e_ref:.3e}")
-    report(f"train_{cls_name}_k{top_num}_bf16_grads", cat(g16), cat(truth), err_hip_vs_fp32=e_hip, err_oraclebf16_vs_fp32=e_ref)
-    assert e_hip <= 1.5 * e_ref + 5e-3 and abs(loss16 - truth_loss) <= 3e-2 * abs(truth_loss), (e_hip, e_ref, loss16, truth_loss)
+    report(f"{tag}_bf16_grads", cat(g16), cat(truth), err_hip_vs_fp32=e_hip, err_oraclebf16_vs_fp32=e_ref)
+    assert e_hip <= GRAD_BF16[0] * e_ref + GRAD_BF16[1] and abs(loss16 - truth_loss) <= BF16_LOSS * abs(truth_loss), (e_hip, e_ref, loss16, truth_loss)
     assert int(extra["expert_counts"].sum()) == top_num * B * grid * grid
+    return dict(model=base, names=names, dead=dead, live=live, truth=truth, g32=g32, gref=gref, g16=g16, z=z, floor=floor, e_hip=e_hip, e_ref=e_ref)
+
+
+@pytest.mark.parametrize("n_cond,cls_name,top_num", [(1, "UniGenFlux", 1), (2, "MultiCondtionUniGenFlux", 1), (1, "UniGenFlux", 2), (1, "UniGenFlux", 3)])
+def test_control_module_gradients_match_oracle_autograd(gpu, n_cond, cls_name, top_num):
+    """top_num = 2: deepspeed top2gating - the gradient reaches the gate through BOTH kept probabilities and their normalising sum. top_num = 3:
+    topkgating (no random draw) - through all kept probabilities of a token and their sum."""
+    check_control_module_gradients(gpu, n_cond, cls_name, top_num)
 
 
 SD3_TINY = dict(sample_size=16, num_layers=3, attention_head_dim=64, num_attention_heads=2, joint_attention_dim=64, caption_projection_dim=128,

@@ -315,6 +315,8 @@ def flux_forward(model, hidden_states, condition_hidden_states=None, conditionin
     BF = torch.bfloat16
     t_f32 = (timestep.to(BF) * 1000).float().contiguous()
     g_f32 = (guidance.to(BF) * 1000).float().contiguous() if (guidance is not None and cfg.guidance_embeds) else None
+    if cfg.guidance_embeds and g_f32 is None:                               # as the inference forward (flux.py): never a silently guidance-free step
+        raise ValueError("guidance is required when config.guidance_embeds is True")
     pooled = pooled_projections.to(dt).contiguous()
     x = _lin(model, "x_embedder", hidden_states.to(dt))
     temb = _time_text_embed(model, "time_text_embed", t_f32, pooled, g_f32)
