@@ -636,6 +636,19 @@ int ug_img_u8_to_chw(const uint8_t* src, int64_t src_bstride, int64_t src_rstrid
  * C from 1 to 4. */
 int ug_img_chw_to_u8(const void* src, int32_t src_dtype, int64_t B, int32_t C, int64_t H, int64_t W, uint8_t* dst, int64_t dst_bstride, int64_t dst_rstride,
                      int32_t denormalize, ug_stream_t stream);
+/* PIL's BoxBlur / GaussianBlur of 8-bit images (BoxBlur.c): `passes` passes along rows with (rx, wwx, fwx), then `passes` along columns with
+ * (ry, wwy, fwy), uint8 after every pass. One pass along a line of `size` pixels, per channel, in uint32:
+ *   out[x] = (ww * sum_{i=-r..r} in[clamp(x+i)] + fw * (in[clamp(x-r-1)] + in[clamp(x+r+1)]) + 2^23) >> 24,  clamp(p) = min(max(p, 0), size - 1).
+ * The constants come from the host (unigen_amd/image.py box_blur_constants, gaussian_box_radius): 0 <= r < 2^24, weights >= 0 with
+ * (2 r + 1) ww + 2 fw <= 2^24. (0, 2^24, 0), the constants of radius 0, skips the axis as PIL does; both axes skipped is a copy. BoxBlur(R) is
+ * passes = 1, GaussianBlur(radius) is passes = 3 with the box radius of _gaussian_blur_radius. C is 1 or 3; dst must not alias src.
+ * fuse = 1: an axis whose halo of passes * (r + 1) pixels fits in LDS (up to 128 along rows, 48 along columns) runs all its passes in ONE launch;
+ * fuse = 0, or a larger halo: one launch per pass, any radius (r + 1 >= size included). The launches alternate between the two images of the
+ * caller-owned, 16-byte aligned workspace of the size the query returns. */
+int64_t ug_img_blur_workspace_bytes(int64_t B, int64_t H, int64_t W, int32_t C);
+int ug_img_box_blur_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t H, int64_t W, int32_t C, uint8_t* dst,
+                       int64_t dst_bstride, int64_t dst_rstride, int32_t rx, int32_t wwx, int32_t fwx, int32_t ry, int32_t wwy, int32_t fwy, int32_t passes,
+                       int32_t fuse, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 
 int ug_version(void);
 const char* ug_last_error(void);

@@ -1,7 +1,8 @@
 """Image front end at 1024 x 1024 x 3, B = 1 and B = 8: time (HIP events after warm-up) and bytes moved per second of ug_canny_u8 (with its sweep count
-and the three stages apart), ug_img_resize_u8 from 1536^2 to 1024^2 and the two converters.
+and the three stages apart), ug_img_resize_u8 from 1536^2 to 1024^2, the two converters and ug_img_box_blur_u8 as PIL's GaussianBlur(10) (the "deblurring" condition), fused
+(all three passes of an axis in one launch) against fuse=0 (one launch per pass), the two interleaved in one process.
 
-    python tools/image_bench.py [--size 1024] [--batches 1 8] [--out profiles/NAME.log]
+    python tools/image_bench.py [--size 1024] [--batches 1 8] [--steps blur] [--out profiles/NAME.log]
 
 Each step runs in a fresh child process under its own time limit (`--step NAME` is what a child runs); a step that fails or runs out of time ends the
 run - nothing more is started on the GPU after it. The yardstick to read the numbers against is one `vae.encode` of the same image
@@ -15,7 +16,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-STEPS = ["canny", "canny_stages", "resize", "u8_to_chw", "chw_to_u8"]
+STEPS = ["canny", "canny_stages", "resize", "u8_to_chw", "chw_to_u8", "blur"]
 STEP_SECONDS = 120
 
 
@@ -69,7 +70,18 @@ def run_step(step, size, B):
         xb = x.to(torch.bfloat16)
         rec.update(fp32_ms=timed(lambda: ops.img_chw_to_u8(x)), fp32_bytes=n * 3 * 4 + n * 3, bf16_ms=timed(lambda: ops.img_chw_to_u8(xb)),
                    bf16_bytes=n * 3 * 2 + n * 3)
-    for k in [k for k in rec if k.endswith("bytes")]:
+    elif step == "blur":
+        from unigen_amd.image import box_blur_constants, gaussian_box_radius
+        c = box_blur_constants(gaussian_box_radius(10))
+        fused, generic = lambda: ops.img_box_blur_u8(img, c, c, 3, fuse=True), lambda: ops.img_box_blur_u8(img, c, c, 3, fuse=False)
+        same = bool(torch.equal(fused(), generic()))
+        rounds = [(timed(fused), timed(generic)) for _ in range(7)]                 # interleaved: a drift of the machine hits both alike
+        med = lambda v: sorted(v)[len(v) // 2]
+        rec.update(fused_ms=med([r[0] for r in rounds]), generic_ms=med([r[1] for r in rounds]), fused_min_ms=min(r[0] for r in rounds),
+                   generic_min_ms=min(r[1] for r in rounds), fused_max_ms=max(r[0] for r in rounds), generic_max_ms=max(r[1] for r in rounds), same_bytes=same,
+                   constants=list(c), fused_bytes=n * 3 * 4, generic_bytes=n * 3 * 12, note="medians of 7 interleaved rounds of 20 calls; a launch reads and "
+                   "writes the image once: 2 launches fused, 6 with fuse=0; each call also allocates its output and workspace")
+    for k in [k for k in rec if k.endswith("bytes") and k != "same_bytes"]:
         ms = rec[k[:-5] + "ms"]
         rec[k[:-5] + "GBps"] = round(rec[k] / ms / 1e6, 1)
     print("IMAGE_BENCH", json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
@@ -79,6 +91,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--steps", nargs="+", choices=STEPS, default=STEPS)
     ap.add_argument("--step", choices=STEPS)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--out")
@@ -87,7 +100,7 @@ def main():
         return run_step(a.step, a.size, a.batch)
     lines = []
     for B in a.batches:
-        for step in STEPS:
+        for step in a.steps:
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step, "--size", str(a.size), "--batch", str(B)], cwd=ROOT,
                                    capture_output=True, text=True, timeout=STEP_SECONDS)

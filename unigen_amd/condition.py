@@ -2,6 +2,7 @@
 (unigen_amd/image.py) and encoded by the native VAE.
 
     Condition("canny", raw_img=img).encode(pipe) -> (tokens [B, N, 4C], ids [N, 3], type_id [N, 1])
+    Condition("deblurring", raw_img=deblurring_image(img), no_process=True).encode(pipe)
 
 `pipe` needs `image_processor` (unigen_amd.image.VaeImageProcessor) and `vae` (unigen_amd.vae.AutoencoderKL). Images are PIL images, uint8 ndarrays
 or uint8 tensors [H, W, C]; a condition image comes back in the kind it went in as (PIL in, PIL out).
@@ -47,6 +48,13 @@ def _rgb(img):
     return img
 
 
+def deblurring_image(raw_img):
+    """The reference's "deblurring" condition image (src/condition.py:72-78), `raw_img.convert("RGB").filter(ImageFilter.GaussianBlur(10)).convert("RGB")`,
+    in the kind of `raw_img` (PIL image, uint8 ndarray or tensor [H, W] / [H, W, C]); the blur runs in csrc/image.hip, bit for bit PIL's."""
+    rgb = _rgb(raw_img)
+    return I.gaussian_blur(rgb.contiguous() if isinstance(rgb, torch.Tensor) else rgb, 10)      # a replicated gray tensor is a stride-0 view
+
+
 class Condition(object):
     def __init__(self, condition_type: str, raw_img=None, no_process: bool = False, condition=None, condition_ids=None, mask=None) -> None:
         self.condition_type = condition_type
@@ -77,8 +85,9 @@ class Condition(object):
             gray = ops.img_rgb_to_l(x)[0].cpu().numpy()                      # .convert("L").convert("RGB")
             return _like(raw_img, np.repeat(gray, 3, axis=-1))
         if condition_type == "deblurring":
-            raise NotImplementedError("condition type 'deblurring' is PIL's GaussianBlur(10) (an extended box blur), which has no kernel here yet - the "
-                                      "follow-up is listed in docs/NEXT_ROWS.md; blur the image yourself and pass it with `no_process=True`")
+            raise NotImplementedError("condition type 'deblurring' is PIL's GaussianBlur(10); `deblurring_image` of this module computes it on the GPU, "
+                                      "bit for bit - pass Condition(\"deblurring\", raw_img=deblurring_image(img), no_process=True) "
+                                      "(docs/NEXT_ROWS.md: why this branch still refuses)")
         if condition_type == "fill":
             return _rgb(raw_img)
         return self.condition

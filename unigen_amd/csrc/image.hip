@@ -4,6 +4,7 @@
 //   ug_canny_grad / ug_canny_nms / ug_canny_hysteresis / ug_canny_u8    cv2.Canny(img, low, high) (L2gradient = false), in its three stages
 //   ug_img_resize_u8      PIL Image.resize(..., LANCZOS) of 8-bit images from host-built fixed-point tables (ImagingResample, 8bpc)
 //   ug_img_rgb_to_l       PIL convert("L")
+//   ug_img_box_blur_u8    PIL ImageFilter.BoxBlur / GaussianBlur of 8-bit images from host-built fixed-point constants (BoxBlur.c)
 //   ug_img_u8_to_chw      VaeImageProcessor.preprocess' pil_to_numpy + numpy_to_pt + normalize
 //   ug_img_chw_to_u8      VaeImageProcessor.postprocess' denormalize + pt_to_numpy + numpy_to_pil
 // Images are uint8 NHWC [B, H, W, C] with a byte stride per sample and per row (pixels of a row are contiguous). Byte kernels: memory- or latency-bound;
@@ -412,6 +413,136 @@ __global__ __launch_bounds__(256) void chw_to_u8_kernel(const T* __restrict__ sr
     }
 }
 
+// ---- PIL BoxBlur / GaussianBlur (BoxBlur.c, 8-bit): passes of an extended box filter along rows, then along columns ------------------------------
+// One pass along a line of `size` pixels, per channel, in uint32 (the weights sum to at most 2^24, so nothing overflows):
+//   out[x] = (ww * sum_{i=-r..r} in[clamp(x+i)] + fw * (in[clamp(x-r-1)] + in[clamp(x+r+1)]) + 2^23) >> 24,   clamp(p) = min(max(p, 0), size-1)
+// r, ww, fw come from the host (unigen_amd/image.py box_blur_constants). PIL slides one accumulator along the line; integer sums are associative, so
+// the direct window gives the same bytes. The tile kernels hold a tile plus a halo of passes * (r + 1) pixels per side in LDS and run all `passes`
+// of their axis there, ping-pong between two buffers; every pass clamps to the IMAGE, and pass p is computed on the tile widened by the
+// (passes - 1 - p) * (r + 1) pixels the later passes still read. Four bytes are summed at a time as two pairs of 16-bit lanes (r <= 127).
+constexpr int BL_BUF = 24576;                        // bytes per LDS buffer
+constexpr int BL_HALF = 1 << 23;
+constexpr int BH_TW = 256, BH_ROWS = 8;              // horizontal tile: 256 pixels of up to 8 rows
+constexpr int BH_HALO_MAX = 128;
+constexpr int BH_NDS_MAX = ((BH_TW + 2 * BH_HALO_MAX) * 3 + 12) / 4;      // staged dwords of a tile row at the largest halo, C = 3
+constexpr int BV_WB = 128;                           // vertical tile: 128 bytes (32 dwords) of a row ...
+constexpr int BV_ROWS = BL_BUF / BV_WB;              // ... times 192 rows, halo included
+constexpr int BV_HALO_MAX = 48, BV_TH_MAX = 96;
+
+__device__ __forceinline__ void blur_add4(unsigned& lo, unsigned& hi, unsigned v) { lo += v & 0x00ff00ffu; hi += (v >> 8) & 0x00ff00ffu; }
+__device__ __forceinline__ unsigned blur_byte(unsigned sum, unsigned edge, unsigned ww, unsigned fw) { return (ww * sum + fw * edge + (unsigned)BL_HALF) >> 24; }
+__device__ __forceinline__ unsigned blur_pack4(unsigned lo, unsigned hi, unsigned elo, unsigned ehi, unsigned ww, unsigned fw) {
+    return blur_byte(lo & 0xffffu, elo & 0xffffu, ww, fw) | (blur_byte(hi & 0xffffu, ehi & 0xffffu, ww, fw) << 8) | (blur_byte(lo >> 16, elo >> 16, ww, fw) << 16) |
+           (blur_byte(hi >> 16, ehi >> 16, ww, fw) << 24);
+}
+// 4 bytes of an LDS line at any byte offset q >= 0, from the two dwords around it (the line is padded by one dword)
+__device__ __forceinline__ unsigned lds_u32_at(const uint8_t* line, int q) {
+    const unsigned* p = (const unsigned*)(line + (q & ~3));
+    return (unsigned)(((((uint64_t)p[1]) << 32) | p[0]) >> (8 * (q & 3)));
+}
+__device__ __forceinline__ void store4_guarded(uint8_t* row, int g, int row_bytes, bool vec, unsigned v) {
+    if (vec && g + 4 <= row_bytes) *(unsigned*)(row + g) = v;
+    else
+        for (int k = 0; k < 4; ++k)
+            if (g + k < row_bytes) row[g + k] = (uint8_t)(v >> (8 * k));
+}
+
+// along rows: LDS offset o of a tile row holds byte a0 + o of the image row, a0 a multiple of 4 at least 3 bytes before the halo; a thread makes one
+// dword of a row per step. A dword whose whole window lies inside the image reads unaligned dwords C bytes apart; at the image's ends every byte
+// clamps its own pixel index.
+template <int C>
+__global__ __launch_bounds__(256) void blur_h_kernel(const uint8_t* __restrict__ src, int64_t sb, int64_t sr, int H, int W, uint8_t* __restrict__ dst, int64_t db,
+                                                     int64_t dr, int r, unsigned ww, unsigned fw, int passes, int nds, int vec_in, int vec_out) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2][BH_ROWS * 4 * (BH_NDS_MAX + 1)];
+    const int pitch = 4 * (nds + 1);
+    const int x0 = blockIdx.x * BH_TW, y0 = blockIdx.y * BH_ROWS, halo = passes * (r + 1), reach = (r + 1) * C;
+    const int row_bytes = W * C, nrow = min(BH_ROWS, H - y0);
+    const int a0 = ((x0 - halo) * C - 3) & ~3;
+    const uint8_t* base = src + (int64_t)blockIdx.z * sb + (int64_t)y0 * sr;
+    for (int idx = threadIdx.x; idx < nrow * nds; idx += 256) {
+        const int row = idx / nds, d = idx - row * nds;
+        *(unsigned*)(lds[0] + row * pitch + 4 * d) = load4_guarded(base + (int64_t)row * sr, (int64_t)a0 + 4 * d, row_bytes, vec_in != 0, 0u);
+    }
+    for (int p = 0; p < passes; ++p) {
+        __syncthreads();
+        const uint8_t* in = lds[p & 1];
+        uint8_t* out = lds[(p & 1) ^ 1];
+        const int hp = (passes - 1 - p) * (r + 1);
+        const int o_lo = (max(x0 - hp, 0) * C - a0) & ~3, o_hi = (min(x0 + BH_TW + hp, W) * C - a0 + 3) & ~3;      // this pass' pixels, widened to dwords
+        const int ndw = (o_hi - o_lo) >> 2;
+        for (int idx = threadIdx.x; idx < nrow * ndw; idx += 256) {
+            const int row = idx / ndw, o = o_lo + 4 * (idx - row * ndw), g = a0 + o;
+            const uint8_t* line = in + row * pitch;
+            unsigned res = 0;
+            if (g - reach >= 0 && g + 3 + reach < row_bytes) {
+                unsigned lo = 0, hi = 0, elo = 0, ehi = 0;
+                for (int i = -r; i <= r; ++i) blur_add4(lo, hi, lds_u32_at(line, o + i * C));
+                blur_add4(elo, ehi, lds_u32_at(line, o - reach));
+                blur_add4(elo, ehi, lds_u32_at(line, o + reach));
+                res = blur_pack4(lo, hi, elo, ehi, ww, fw);
+            } else {
+                for (int k = 0; k < 4; ++k) {
+                    if (g + k < 0 || g + k >= row_bytes) continue;
+                    const int x = (g + k) / C, ch = g + k - x * C - a0;
+                    unsigned sum = 0;
+                    for (int i = -r; i <= r; ++i) sum += line[clampi(x + i, 0, W - 1) * C + ch];
+                    const unsigned edge = (unsigned)line[clampi(x - r - 1, 0, W - 1) * C + ch] + line[clampi(x + r + 1, 0, W - 1) * C + ch];
+                    res |= blur_byte(sum, edge, ww, fw) << (8 * k);
+                }
+            }
+            if (p + 1 < passes) *(unsigned*)(out + row * pitch + o) = res;
+            else if (g < row_bytes) store4_guarded(dst + (int64_t)blockIdx.z * db + (int64_t)(y0 + row) * dr, g, row_bytes, vec_out != 0, res);
+        }
+    }
+}
+
+// along columns: a row of W * C bytes is a byte vector, the window is the same rows for every lane. LDS row j holds image row y0 - halo + j.
+__global__ __launch_bounds__(256) void blur_v_kernel(const uint8_t* __restrict__ src, int64_t sb, int64_t sr, int H, int row_bytes, uint8_t* __restrict__ dst,
+                                                     int64_t db, int64_t dr, int r, unsigned ww, unsigned fw, int passes, int th, int vec_in, int vec_out) {
+    __shared__ __attribute__((aligned(16))) unsigned lds[2][BL_BUF / 4];
+    constexpr int ND = BV_WB / 4;
+    const int gx = blockIdx.x * BV_WB, y0 = blockIdx.y * th, halo = passes * (r + 1), ybase = y0 - halo;
+    const int d = threadIdx.x & (ND - 1), g = gx + 4 * d;
+    const bool live = g < row_bytes;                                               // a column past the row's end only keeps the barriers company
+    const uint8_t* base = src + (int64_t)blockIdx.z * sb;
+    const int ya = max(ybase, 0), yb = min(y0 + th + halo, H);
+    for (int y = ya + (threadIdx.x >> 5); live && y < yb; y += 256 / ND) lds[0][(y - ybase) * ND + d] = load4_guarded(base + (int64_t)y * sr, g, row_bytes, vec_in != 0, 0u);
+    for (int p = 0; p < passes; ++p) {
+        __syncthreads();
+        const unsigned* in = lds[p & 1];
+        unsigned* out = lds[(p & 1) ^ 1];
+        const int hp = (passes - 1 - p) * (r + 1);
+        const int y_lo = max(y0 - hp, 0), y_hi = min(y0 + th + hp, H);
+        for (int y = y_lo + (threadIdx.x >> 5); live && y < y_hi; y += 256 / ND) {
+            unsigned lo = 0, hi = 0, elo = 0, ehi = 0;
+            for (int i = -r; i <= r; ++i) blur_add4(lo, hi, in[(clampi(y + i, 0, H - 1) - ybase) * ND + d]);
+            blur_add4(elo, ehi, in[(clampi(y - r - 1, 0, H - 1) - ybase) * ND + d]);
+            blur_add4(elo, ehi, in[(clampi(y + r + 1, 0, H - 1) - ybase) * ND + d]);
+            const unsigned res = blur_pack4(lo, hi, elo, ehi, ww, fw);
+            if (p + 1 < passes) out[(y - ybase) * ND + d] = res;
+            else store4_guarded(dst + (int64_t)blockIdx.z * db + (int64_t)y * dr, g, row_bytes, vec_out != 0, res);
+        }
+    }
+}
+
+// any radius, one pass, one output byte per thread straight from memory: the window is clipped to the line and its clamped ends are counted, so a
+// byte costs at most `size` reads however large r is (r + 1 >= size included)
+__global__ __launch_bounds__(256) void blur_direct_kernel(const uint8_t* __restrict__ src, int64_t sb, int64_t sr, int H, int W, int C, uint8_t* __restrict__ dst,
+                                                          int64_t db, int64_t dr, int vertical, int r, unsigned ww, unsigned fw) {
+    const int g = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (g >= W * C) return;
+    const uint8_t* line = src + (int64_t)blockIdx.z * sb;
+    int64_t step;
+    int n, pos;
+    if (vertical) { line += g; step = sr; n = H; pos = y; }
+    else { pos = g / C; line += (int64_t)y * sr + (g - pos * C); step = C; n = W; }
+    const int lo = pos - r, hi = pos + r;                                          // r, pos < 2^24
+    unsigned sum = (unsigned)max(-lo, 0) * line[0] + (unsigned)max(hi - (n - 1), 0) * line[(n - 1) * step];
+    for (int i = max(lo, 0); i <= min(hi, n - 1); ++i) sum += line[i * step];
+    const unsigned edge = (unsigned)line[clampi(lo - 1, 0, n - 1) * step] + line[clampi(hi + 1, 0, n - 1) * step];
+    dst[(int64_t)blockIdx.z * db + (int64_t)y * dr + g] = (uint8_t)blur_byte(sum, edge, ww, fw);
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------
 static bool img_args_ok(const void* p, int64_t sb, int64_t sr, int64_t B, int64_t H, int64_t W, int64_t C) {
     return p && B >= 1 && H >= 1 && W >= 1 && B < 65536 && H < 65536 && W < (1 << 24) && sr >= W * C && (B == 1 || sb >= H * sr || sb >= (H - 1) * sr + W * C);
@@ -585,5 +716,84 @@ extern "C" int ug_img_chw_to_u8(const void* src, int32_t src_dtype, int64_t B, i
         hipLaunchKernelGGL(chw_to_u8_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, C, (int)H, (int)W, dst, dst_bstride, dst_rstride,
                            (int)denormalize, (int)(W % 8 == 0 && ug_aligned(src, 16)), vout);
     UG_CHECK_LAUNCH("ug_img_chw_to_u8");
+    return UG_OK;
+}
+
+// workspace of ug_img_box_blur_u8: two contiguous images [B, H, W, C], each 256-byte aligned, that the launches alternate between
+extern "C" int64_t ug_img_blur_workspace_bytes(int64_t B, int64_t H, int64_t W, int32_t C) {
+    if (B < 1 || H < 1 || W < 1 || C < 1) return 0;
+    return 2 * up256(B * H * W * C);
+}
+
+static bool blur_consts_ok(int64_t r, int64_t ww, int64_t fw) {                     // weights that sum to at most 2^24: no pass overflows uint32
+    return r >= 0 && r < (1 << 24) && ww >= 0 && fw >= 0 && (2 * r + 1) * ww + 2 * fw <= (1 << 24);
+}
+static bool blur_identity(int64_t r, int64_t ww, int64_t fw) { return r == 0 && fw == 0 && ww == (1 << 24); }      // the constants of radius 0: PIL skips the axis
+
+extern "C" int ug_img_box_blur_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t H, int64_t W, int32_t C, uint8_t* dst,
+                                  int64_t dst_bstride, int64_t dst_rstride, int32_t rx, int32_t wwx, int32_t fwx, int32_t ry, int32_t wwy, int32_t fwy,
+                                  int32_t passes, int32_t fuse, void* workspace, int64_t workspace_bytes, ug_stream_t stream) {
+    UG_REQUIRE((C == 1 || C == 3) && img_args_ok(src, src_bstride, src_rstride, B, H, W, C) && img_args_ok(dst, dst_bstride, dst_rstride, B, H, W, C),
+               UG_ERR_BAD_SHAPE, "ug_img_box_blur_u8: bad arguments (B=%lld H=%lld W=%lld C=%d; C is 1 or 3, strides cover a row / a sample)", (long long)B,
+               (long long)H, (long long)W, C);
+    UG_REQUIRE(passes >= 1 && (fuse == 0 || fuse == 1), UG_ERR_BAD_SHAPE, "ug_img_box_blur_u8: passes = %d (at least 1), fuse = %d (0 generic, 1 auto)", passes, fuse);
+    UG_REQUIRE(blur_consts_ok(rx, wwx, fwx) && blur_consts_ok(ry, wwy, fwy), UG_ERR_BAD_SHAPE,
+               "ug_img_box_blur_u8: bad constants (r, ww, fw) = (%d, %d, %d), (%d, %d, %d): 0 <= r < 2^24, weights >= 0 with (2 r + 1) ww + 2 fw <= 2^24", rx, wwx,
+               fwx, ry, wwy, fwy);
+    const int64_t img_bytes = up256(B * H * W * C);
+    UG_REQUIRE(workspace && workspace_bytes >= 2 * img_bytes && ug_aligned(workspace, 16), UG_ERR_BAD_SHAPE,
+               "ug_img_box_blur_u8: a 16-byte aligned workspace of ug_img_blur_workspace_bytes = %lld bytes is needed (got %lld)", (long long)(2 * img_bytes),
+               (long long)workspace_bytes);
+    const uint8_t* src_end = src + (B - 1) * src_bstride + (H - 1) * src_rstride + W * C;
+    const uint8_t* dst_end = dst + (B - 1) * dst_bstride + (H - 1) * dst_rstride + W * C;
+    UG_REQUIRE(dst_end <= src || src_end <= dst, UG_ERR_BAD_SHAPE, "ug_img_box_blur_u8: dst must not alias src");
+    hipStream_t s = (hipStream_t)stream;
+    struct Axis { int r, ww, fw, vertical, launches, per; bool tile; } axes[2] = {{rx, wwx, fwx, 0, 0, 0, false}, {ry, wwy, fwy, 1, 0, 0, false}};
+    int total = 0;
+    for (Axis& a : axes) {
+        if (blur_identity(a.r, a.ww, a.fw)) continue;
+        const int64_t halo_max = a.vertical ? BV_HALO_MAX : BH_HALO_MAX;
+        const bool fused = fuse && (int64_t)passes * (a.r + 1) <= halo_max;        // all passes of the axis in one launch when their halo fits in LDS
+        a.tile = a.r + 1 <= halo_max;
+        a.per = fused ? passes : 1;
+        a.launches = fused ? 1 : passes;
+        total += a.launches;
+    }
+    if (total == 0) {                      // radius 0 on both axes: a copy, row by row
+        hipError_t e = hipSuccess;
+        for (int64_t b = 0; b < B && e == hipSuccess; ++b)
+            e = hipMemcpy2DAsync(dst + b * dst_bstride, (size_t)dst_rstride, src + b * src_bstride, (size_t)src_rstride, (size_t)(W * C), (size_t)H,
+                                 hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) UG_FAIL(UG_ERR_HIP, "ug_img_box_blur_u8: copy failed: %s", hipGetErrorString(e));
+        return UG_OK;
+    }
+    uint8_t* ws[2] = {(uint8_t*)workspace, (uint8_t*)workspace + img_bytes};
+    const int64_t wsb = H * W * C, wsr = W * C;
+    int k = 0;
+    for (const Axis& a : axes)
+        for (int l = 0; l < a.launches; ++l, ++k) {
+            const uint8_t* in = k == 0 ? src : ws[(k - 1) & 1];
+            const int64_t ib = k == 0 ? src_bstride : wsb, ir = k == 0 ? src_rstride : wsr;
+            uint8_t* out = k == total - 1 ? dst : ws[k & 1];
+            const int64_t ob = k == total - 1 ? dst_bstride : wsb, orow = k == total - 1 ? dst_rstride : wsr;
+            const int vin = strided_aligned(in, ib, ir, 4), vout = strided_aligned(out, ob, orow, 4);
+            const int halo = a.per * (a.r + 1);
+            if (!a.tile) {
+                const dim3 grid((unsigned)cdiv64(W * C, 256), (unsigned)H, (unsigned)B);
+                hipLaunchKernelGGL(blur_direct_kernel, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, (int)C, out, ob, orow, a.vertical, a.r, (unsigned)a.ww,
+                                   (unsigned)a.fw);
+            } else if (a.vertical) {
+                const int th = BV_ROWS - 2 * halo < BV_TH_MAX ? BV_ROWS - 2 * halo : BV_TH_MAX;
+                const dim3 grid((unsigned)cdiv64(W * C, BV_WB), (unsigned)cdiv64(H, th), (unsigned)B);
+                hipLaunchKernelGGL(blur_v_kernel, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)(W * C), out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, th,
+                                   vin, vout);
+            } else {
+                const int nds = ((BH_TW + 2 * halo) * C + 12) / 4;
+                const dim3 grid((unsigned)cdiv64(W, BH_TW), (unsigned)cdiv64(H, BH_ROWS), (unsigned)B);
+                if (C == 1) hipLaunchKernelGGL(blur_h_kernel<1>, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, nds, vin, vout);
+                else hipLaunchKernelGGL(blur_h_kernel<3>, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, nds, vin, vout);
+            }
+            UG_CHECK_LAUNCH("ug_img_box_blur_u8");
+        }
     return UG_OK;
 }

@@ -2,8 +2,9 @@
 
 The reference passes PIL images to `pipe(control_image=...)`, saves `pipe(...).images` as PIL images (infer.py) and builds its canny condition with
 `cv2.Canny(img, 100, 200)` (src/condition.py:63-67); every image goes through `VaeImageProcessor.preprocess` / `.postprocess`. Here an image is
-uploaded once as uint8 and everything after that runs in csrc/image.hip: PIL's Lanczos resampler, convert("L"), the uint8 <-> [-1, 1] converters and
-the three stages of Canny. All of it is integer or exactly specified fp32 arithmetic (docs/PARITY_TOLERANCES.md, "Image front end: exact").
+uploaded once as uint8 and everything after that runs in csrc/image.hip: PIL's Lanczos resampler, convert("L"), the uint8 <-> [-1, 1] converters, the
+three stages of Canny and PIL's BoxBlur / GaussianBlur (the reference's "deblurring" condition, src/condition.py:72-78). All of it is integer or
+exactly specified fp32 arithmetic (docs/PARITY_TOLERANCES.md, "Image front end: exact").
 
 PIL is imported lazily: only PIL-typed inputs and `output_type="pil"` need it.
 """
@@ -138,6 +139,69 @@ def canny(image, low: int = 100, high: int = 200, return_sweeps: bool = False):
     return (out, sweeps) if return_sweeps else out
 
 
+# ---- PIL's BoxBlur / GaussianBlur (BoxBlur.c): the constants of a pass, on the host with C's float roundings ---------------------------------------
+_f32 = np.float32
+
+
+def box_blur_constants(R) -> Tuple[int, int, int]:
+    """(r, ww, fw) of one box-blur pass of float radius R: r = (int)R, ww = (uint32)(2^24 / (R * 2 + 1)) divided in float32, fw the weight of the
+    two pixels just outside the window. A pass is (ww * window + fw * (in[x-r-1] + in[x+r+1]) + 2^23) >> 24."""
+    R = _f32(R)
+    if not 0 <= R < (1 << 24):                       # also refuses a NaN
+        raise ValueError(f"blur radius must be in [0, 2^24), got {R}")
+    r = int(R)
+    ww = int(_f32(1 << 24) / (R * _f32(2) + _f32(1)))
+    return r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2
+
+
+def gaussian_box_radius(radius, passes: int = 3) -> np.float32:
+    """BoxBlur.c _gaussian_blur_radius: the float box radius whose `passes` repetitions approximate a Gaussian of standard deviation `radius`.
+    Every variable is a C float, so every product, sum and quotient rounds to float32; only sqrt and floor see doubles (their literals are doubles)."""
+    radius, one = _f32(radius), _f32(1)
+    sigma2 = radius * radius / _f32(passes)
+    L = _f32(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = _f32(math.floor((float(L) - 1.0) / 2.0))
+    a = (_f32(2) * l + one) * (l * (l + one) - _f32(3) * sigma2)
+    a = a / (_f32(6) * (sigma2 - (l + one) * (l + one)))
+    return l + a
+
+
+def _xy(radius) -> Tuple[float, float]:
+    rx, ry = radius if isinstance(radius, (tuple, list)) else (radius, radius)
+    if not (rx >= 0 and ry >= 0):
+        raise ValueError(f"blur radius must be non-negative, got {radius!r}")
+    return rx, ry
+
+
+def _blur(image, Rx, Ry, passes: int):
+    """`passes` box passes of float radius Rx along rows, then of Ry along columns; the result in the kind of `image`."""
+    from . import ops
+    pil, as_numpy = _is_pil(image), not isinstance(image, torch.Tensor)
+    ndim = 3 if pil else image.ndim
+    dev = image.device if isinstance(image, torch.Tensor) and image.is_cuda else _default_device()
+    x = to_device_u8(image, dev)
+    out = ops.img_box_blur_u8(x, box_blur_constants(Rx), box_blur_constants(Ry), passes)
+    out = out if ndim == 4 else (out[0, :, :, 0] if ndim == 2 or (pil and x.shape[-1] == 1) else out[0])
+    if pil:
+        from PIL import Image
+        return Image.fromarray(out.cpu().numpy())
+    return out.cpu().numpy() if as_numpy else (out if image.is_cuda else out.cpu())
+
+
+def box_blur(image, radius):
+    """PIL's `image.filter(ImageFilter.BoxBlur(radius))`, bit for bit: uint8 [H, W], [H, W, C] or [B, H, W, C] (C = 1 or 3), a PIL image, ndarray or
+    tensor, returned in the kind it came in (a GPU tensor stays on the GPU). `radius` is a number or an (x, y) pair."""
+    rx, ry = _xy(radius)
+    return _blur(image, rx, ry, 1)
+
+
+def gaussian_blur(image, radius=2):
+    """PIL's `image.filter(ImageFilter.GaussianBlur(radius))`, bit for bit: three box passes per axis of radius `gaussian_box_radius(radius)`.
+    Image kinds and `radius` as for `box_blur`."""
+    rx, ry = _xy(radius)
+    return _blur(image, gaussian_box_radius(rx, 3), gaussian_box_radius(ry, 3), 3)
+
+
 class VaeImageProcessor:
     """diffusers.image_processor.VaeImageProcessor for the pipelines of this package: same constructor names and defaults, `preprocess` and
     `postprocess`; the arithmetic runs in csrc/image.hip. Attach it like the text encoders:
@@ -158,6 +222,11 @@ class VaeImageProcessor:
         self.do_resize, self.vae_scale_factor, self.do_normalize = do_resize, int(vae_scale_factor), do_normalize
         self.do_convert_rgb, self.do_convert_grayscale = do_convert_rgb, do_convert_grayscale
         self.device = None if device is None else torch.device(device)
+
+    @staticmethod
+    def blur(image, blur_factor: int = 4):
+        """diffusers' `image.filter(ImageFilter.GaussianBlur(blur_factor))`."""
+        return gaussian_blur(image, blur_factor)
 
     # ---------------------------------------------------------------- sizes --------------------------------------------------------------------
     def get_default_height_width(self, image, height: Optional[int] = None, width: Optional[int] = None) -> Tuple[int, int]:

@@ -175,6 +175,8 @@ SIGNATURES.update({
     "ug_img_rgb_to_l": (i32, [vp, i64, i64, i64, i64, i64, vp, i64, i64, vp]),
     "ug_img_u8_to_chw": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i32, i32, i32, vp]),
     "ug_img_chw_to_u8": (i32, [vp, i32, i64, i32, i64, i64, vp, i64, i64, i32, vp]),
+    "ug_img_blur_workspace_bytes": (i64, [i64, i64, i64, i32]),
+    "ug_img_box_blur_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
 })
 _F32_TWINS = {"ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
               "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu", "ug_gelu_erf_f32": "ug_gelu_erf",

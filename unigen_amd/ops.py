@@ -1061,3 +1061,16 @@ def img_chw_to_u8(x: torch.Tensor, denormalize: bool = True) -> torch.Tensor:
     out = torch.empty(B, H, W, Cc, dtype=u8, device=x.device)
     L.check(L.load().ug_img_chw_to_u8(x.data_ptr(), dt, B, Cc, H, W, out.data_ptr(), H * W * Cc, W * Cc, int(bool(denormalize)), _stream()), "ug_img_chw_to_u8")
     return out
+
+
+def img_box_blur_u8(x: torch.Tensor, cx, cy, passes: int = 1, fuse: bool = True) -> torch.Tensor:
+    """PIL's box blur of a uint8 [B, H, W, C] batch: `passes` passes along rows with the constants cx = (r, ww, fw), then along columns with cy
+    (unigen_amd.image.box_blur_constants; those of radius 0 skip the axis). passes = 3 with the box radius of `gaussian_box_radius` is PIL's
+    GaussianBlur. `fuse=False` forces one launch per pass."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    lib = L.load()
+    ws = torch.empty(int(lib.ug_img_blur_workspace_bytes(B, H, W, Cc)), dtype=u8, device=x.device)
+    out = torch.empty(B, H, W, Cc, dtype=u8, device=x.device)
+    L.check(lib.ug_img_box_blur_u8(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), H * W * Cc, W * Cc, *(int(v) for v in cx), *(int(v) for v in cy), int(passes),
+                                   int(bool(fuse)), ws.data_ptr(), ws.numel(), _stream()), "ug_img_box_blur_u8")
+    return out
