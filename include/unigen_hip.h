@@ -82,7 +82,9 @@ typedef struct ug_gemm_desc {
     int64_t r_gstride, gate_gstride;
     /* optional caller-owned scratch (>= ug_gemm_workspace_bytes(), 16-byte aligned) for the split-K treatment of the last, partially
      * filled round of tiles; NULL = plain tiles only. Its first 4096 bytes (arrival tickets) must be ZERO before the first call;
-     * every call leaves them zero again. The rest needs no initialisation. One workspace per stream. */
+     * every call leaves them zero again. The rest needs no initialisation. One workspace per stream. A launch writes only the slabs of its
+     * own K-slices (bytes [4096, 4096 + padded tail tiles x K-slices x 256 KiB)); a workspace too small for them is not an error: that launch
+     * runs unsplit, with the result of workspace = NULL, and does not touch it (tests/test_workspace_gpu.py). */
     void* workspace; int64_t workspace_bytes;
     /* Column split, for one launch over the concatenated weights of two Linear layers that read the same input (the single block's
      * [to_q; to_k; to_v; proj_mlp], diffusers FluxSingleTransformerBlock, called at src/UniGenTransformer.py:1151):
@@ -420,7 +422,9 @@ int ug_rowdot(const void* a, int64_t lda, const void* b, int64_t ldb, float* out
  * The fp32 verification path keeps the GEMM-based formulation of unigen_amd/autograd.py. */
 int64_t ug_flash_attn_bwd_workspace_bytes(int64_t batches, int32_t heads, int64_t Lq);
 /* ug_flash_attn_fwd that also writes lse2[b][h][q] = log2 sum_k 2^(scale log2(e) s_qk) (fp32, row length lse_ld >= Lq, typically Lq rounded up to 64
- * with the padding zeroed by the caller): the forward of a training step; hand the buffer to ug_flash_attn_bwd as lse_in. */
+ * with the padding zeroed by the caller): the forward of a training step; hand the buffer to ug_flash_attn_bwd as lse_in. The padding must be
+ * there (the backward loads whole 64-row tiles of statistics), but no kernel multiplies by it - a query row >= Lq is selected to 0 - so its values
+ * reach no result (tests/test_workspace_gpu.py fills it with NaN). */
 int ug_flash_attn_fwd_lse(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
                           const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
                           int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale, float* lse2, int64_t lse_ld,

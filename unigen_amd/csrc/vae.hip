@@ -464,7 +464,7 @@ int groupnorm_impl(const void* x, const void* gamma, const void* beta, void* out
                "ug_groupnorm_nhwc: 16-byte alignment required");
     int64_t nchunks = (HW + GN_ROWS - 1) / GN_ROWS;
     const int64_t part_bytes = B * nchunks * G * 2 * (int64_t)sizeof(double);
-    UG_REQUIRE(workspace_bytes >= part_bytes + B * G * 2 * (int64_t)sizeof(float), UG_ERR_BAD_SHAPE, "ug_groupnorm_nhwc: workspace too small (ug_groupnorm_workspace_bytes)");
+    UG_REQUIRE(workspace_bytes >= ug_groupnorm_workspace_bytes(B, HW, G), UG_ERR_BAD_SHAPE, "ug_groupnorm_nhwc: workspace too small (ug_groupnorm_workspace_bytes)");
     UG_REQUIRE(nchunks < (1 << 30) && B < 65536, UG_ERR_UNSUPPORTED, "ug_groupnorm_nhwc: too large");
     hipStream_t s = (hipStream_t)stream;
     double* part = (double*)workspace;
