@@ -654,6 +654,54 @@ int ug_img_box_blur_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstr
                        int64_t dst_bstride, int64_t dst_rstride, int32_t rx, int32_t wwx, int32_t fwx, int32_t ry, int32_t wwy, int32_t fwy, int32_t passes,
                        int32_t fuse, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 
+/* ---- depth condition (csrc/depth.hip; unigen_amd/depth.py: transformers' DepthAnythingForDepthEstimation, DPTImageProcessor and the
+ * depth-estimation pipeline's post-processing - the reference builds its depth condition with them in src/condition.py:52-62). The glue that is
+ * neither a GEMM nor a convolution; activations are NHWC. Every bf16 entry has an `_f32` twin (fp32 storage, no intermediate rounding) declared
+ * beside it. Outputs are fully written, pad channels included; 16-byte aligned bases take the 8-channel paths, anything else single elements. ---- */
+/* uint8 NHWC [B, H, W, C] (byte strides as for the image front end; C = 3, or 1: gray replicated) -> rows [B (H/P) (W/P)][ld_out] of the
+ * patch-embedding GEMM: column c P^2 + ky P + kx (the flattening of the conv weight [D][3][P][P]) of the row of patch (py, px) is
+ *   ((float)((double)v * rescale) - mean[c]) / std[c]          v = img[b][py P + ky][px P + kx][c]
+ * with DPTImageProcessor's rounding points (rescale: a float64 product cast to float32; normalize: float32 subtraction and IEEE division);
+ * columns [3 P^2, Kp) are zero. Kp a multiple of 64; H, W multiples of P <= 64. mean, std: 3 floats each on the HOST. bf16 rounds once, at the store. */
+int ug_img_u8_to_patches(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
+                         const float* mean, const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
+int ug_img_u8_to_patches_f32(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
+                             const float* mean, const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
+/* y = max(x, 0) over n contiguous elements, n a multiple of 8; y may be x. */
+int ug_relu(const void* x, void* y, int64_t n, ug_stream_t stream);
+int ug_relu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
+/* Second half of nn.ConvTranspose2d(C, C, kernel = stride = f): `prod` is the fp32 product (UG_EPI_F32) of the input rows [B h w][Cin] with the
+ * weight re-laid as [(ky, kx, co)][Cin], rows of f f Cout floats with leading dimension ld_prod.
+ *   out[b][y f + ky][x f + kx][co] = rnd(prod[(b, y, x)][(ky f + kx) Cout + co] + bias[co]),  zeros in channels [Cout, Cp)
+ * out NHWC [B][h f][w f][Cp], Cp a multiple of 8: accumulate, add the bias, round once, as the module does in bf16. */
+int ug_deconv_scatter_nhwc(const float* prod, int64_t ld_prod, const void* bias, void* out, int64_t B, int64_t h, int64_t w, int32_t f, int64_t Cout,
+                           int64_t Cp, ug_stream_t stream);
+int ug_deconv_scatter_nhwc_f32(const float* prod, int64_t ld_prod, const void* bias, void* out, int64_t B, int64_t h, int64_t w, int32_t f, int64_t Cout,
+                               int64_t Cp, ug_stream_t stream);
+/* F.interpolate(mode="bilinear", align_corners) of NHWC [B][H][W][C] to [B][Ho][Wo][C], C a multiple of 8, any Ho, Wo >= 1. Source index and
+ * weights in fp32 as torch's area_pixel_compute_source_index: align_corners: scale = (in - 1) / (out - 1) (0 when out == 1), src = o scale;
+ * otherwise scale = in / out, src = max(0, (o + 0.5) scale - 0.5), the upper index clamped. One rounding, at the store. */
+int ug_bilinear_nhwc(const void* x, int64_t B, int64_t H, int64_t W, int64_t C, void* out, int64_t Ho, int64_t Wo, int32_t align_corners,
+                     ug_stream_t stream);
+int ug_bilinear_nhwc_f32(const void* x, int64_t B, int64_t H, int64_t W, int64_t C, void* out, int64_t Ho, int64_t Wo, int32_t align_corners,
+                         ug_stream_t stream);
+/* DepthAnythingDepthEstimationHead's activation1 + conv3 (1x1 to one channel) + activation2 + max_depth on x [pixels][Cp] (channels [0, C) used):
+ *   out[p] = act(rnd(bias[0] + sum_c w[c] relu(x[p][c]))) * max_depth,  act = ReLU, or sigmoid with metric != 0
+ * out fp32 [pixels]; w [C], bias [1] in the activation dtype. The bf16 entry rounds conv3's output, the sigmoid and the product to bf16. */
+int ug_depth_head_out(const void* x, int64_t pixels, int64_t C, int64_t Cp, const void* w, const void* bias, float max_depth, int32_t metric, float* out,
+                      ug_stream_t stream);
+int ug_depth_head_out_f32(const void* x, int64_t pixels, int64_t C, int64_t Cp, const void* w, const void* bias, float max_depth, int32_t metric,
+                          float* out, ug_stream_t stream);
+/* F.interpolate(mode="bicubic", align_corners=False) of fp32 [B][H][W] to [B][Ho][Wo] (the pipeline's post_process_depth_estimation): A = -0.75, the
+ * four taps per axis index-clamped as upsample_bicubic2d does. fp32 only. B, Ho < 65536. */
+int ug_bicubic_f32(const float* x, int64_t B, int64_t H, int64_t W, float* out, int64_t Ho, int64_t Wo, ug_stream_t stream);
+/* The pipeline's depth image: per image of d fp32 [B][HW], uint8(trunc(((d - min) / (max - min)) * 255.0f)) with numpy's float32 order of operations,
+ * written to uint8 [B][HW][channels], channels 1 or 3 (replicated). One right answer per element. max == min writes 0 (numpy yields NaN there and
+ * its cast is unspecified). Min and max are reduced in two deterministic stages, no float atomics; the caller-owned, 8-byte aligned workspace of the
+ * size the query returns needs no initialisation. B < 65536. */
+int64_t ug_minmax_workspace_bytes(int64_t B, int64_t HW);
+int ug_minmax_to_u8(const float* d, int64_t B, int64_t HW, uint8_t* out, int32_t channels, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

@@ -1,0 +1,339 @@
+"""Depth Anything (DINOv2 backbone + DPT neck and head), its image processor and the depth pipeline's post-processing restated in plain torch on the
+CPU, from transformers' modules (models/depth_anything, models/dinov2, models/dpt/image_processing_pil_dpt.py, pipelines/depth_estimation.py) - not
+from the kernels. It takes transformers' state dict. `forward(..., dtype=torch.float64)` is the truth the GPU tests compare against;
+`round_bf16=True` rounds every tensor a bf16 module run materialises (the rounding points of the HIP path) while computing in `dtype`.
+tests/test_depth_ref_cpu.py pins it to transformers and to tests/golden/depth_tiny.safetensors (tests/golden/make_depth_golden.py).
+
+No GPU and no transformers are needed to import or run this file.
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+TINY = dict(patch_size=14, reassemble_hidden_size=128, reassemble_factors=[4, 2, 1, 0.5], neck_hidden_sizes=[24, 48, 96, 128], fusion_hidden_size=64,
+            head_in_index=-1, head_hidden_size=32, depth_estimation_type="relative", max_depth=1,
+            backbone_config=dict(model_type="dinov2", hidden_size=128, num_hidden_layers=4, num_attention_heads=2, mlp_ratio=2, hidden_act="gelu",
+                                 layer_norm_eps=1e-6, image_size=70, patch_size=14, num_channels=3, qkv_bias=True, use_swiglu_ffn=False,
+                                 apply_layernorm=True, reshape_hidden_states=False, out_indices=[1, 2, 3, 4]))
+SMALL = dict(patch_size=14, reassemble_hidden_size=384, reassemble_factors=[4, 2, 1, 0.5], neck_hidden_sizes=[48, 96, 192, 384], fusion_hidden_size=64,
+             head_in_index=-1, head_hidden_size=32, depth_estimation_type="relative", max_depth=1,
+             backbone_config=dict(model_type="dinov2", hidden_size=384, num_hidden_layers=12, num_attention_heads=6, mlp_ratio=4, hidden_act="gelu",
+                                  layer_norm_eps=1e-6, image_size=518, patch_size=14, num_channels=3, qkv_bias=True, use_swiglu_ffn=False,
+                                  apply_layernorm=True, reshape_hidden_states=False, out_indices=[9, 10, 11, 12]))
+CASES = {"g2x2": (28, 28), "g4x3": (56, 42), "g5x7": (70, 98)}        # name -> model input (H, W), B = 2
+SEED = 23          # picked so that every case passes the generator's positive-share condition with room (0.49 - 0.77 positive)
+
+
+def keys_and_shapes(cfg):
+    """transformers' state-dict keys of DepthAnythingForDepthEstimation(cfg) with their shapes (mask_token included)."""
+    b = cfg["backbone_config"]
+    D, P, F_, Hh, nl = b["hidden_size"], b["patch_size"], cfg["fusion_hidden_size"], cfg["head_hidden_size"], b["num_hidden_layers"]
+    n0 = b["image_size"] // P
+    e = {"backbone.embeddings.cls_token": (1, 1, D), "backbone.embeddings.mask_token": (1, D), "backbone.embeddings.position_embeddings": (1, 1 + n0 * n0, D),
+         "backbone.embeddings.patch_embeddings.projection.weight": (D, 3, P, P), "backbone.embeddings.patch_embeddings.projection.bias": (D,)}
+    for i in range(nl):
+        p = f"backbone.encoder.layer.{i}."
+        for n in ("norm1", "norm2"):
+            e[p + n + ".weight"], e[p + n + ".bias"] = (D,), (D,)
+        for n in ("attention.attention.query", "attention.attention.key", "attention.attention.value", "attention.output.dense"):
+            e[p + n + ".weight"], e[p + n + ".bias"] = (D, D), (D,)
+        e[p + "mlp.fc1.weight"], e[p + "mlp.fc1.bias"] = (D * b["mlp_ratio"], D), (D * b["mlp_ratio"],)
+        e[p + "mlp.fc2.weight"], e[p + "mlp.fc2.bias"] = (D, D * b["mlp_ratio"]), (D,)
+        e[p + "layer_scale1.lambda1"], e[p + "layer_scale2.lambda1"] = (D,), (D,)
+    e["backbone.layernorm.weight"], e["backbone.layernorm.bias"] = (D,), (D,)
+    for i, (ch, f) in enumerate(zip(cfg["neck_hidden_sizes"], cfg["reassemble_factors"])):
+        p = f"neck.reassemble_stage.layers.{i}."
+        e[p + "projection.weight"], e[p + "projection.bias"] = (ch, D, 1, 1), (ch,)
+        if f != 1:
+            k = int(f) if f > 1 else 3
+            e[p + "resize.weight"], e[p + "resize.bias"] = (ch, ch, k, k), (ch,)
+        e[f"neck.convs.{i}.weight"] = (F_, ch, 3, 3)
+        p = f"neck.fusion_stage.layers.{i}."
+        e[p + "projection.weight"], e[p + "projection.bias"] = (F_, F_, 1, 1), (F_,)
+        for r in ("residual_layer1", "residual_layer2"):
+            for q in ("convolution1", "convolution2"):
+                e[p + f"{r}.{q}.weight"], e[p + f"{r}.{q}.bias"] = (F_, F_, 3, 3), (F_,)
+    e["head.conv1.weight"], e["head.conv1.bias"] = (F_ // 2, F_, 3, 3), (F_ // 2,)
+    e["head.conv2.weight"], e["head.conv2.bias"] = (Hh, F_ // 2, 3, 3), (Hh,)
+    e["head.conv3.weight"], e["head.conv3.bias"] = (1, Hh, 1, 1), (1,)
+    return e
+
+
+def random_state(cfg, seed=SEED, device="cpu"):
+    """Seeded weights, bf16-representable (returned as bf16), with a spread that keeps the head alive - transformers' default init gives an output
+    of about 3e-5 that is half zero, which tests nothing: weights N(0, (1.4 / sqrt(fan_in))^2), biases N(0, 0.1^2), norm weights 1 + 0.2 N,
+    lambda U(0.5, 1.5), class token and positions 0.5 N, head.conv3.bias 0.5. One generator, keys in sorted order."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    rn = lambda shape: torch.randn(shape, generator=g, device=device, dtype=torch.float32)
+    sd = {}
+    shapes = keys_and_shapes(cfg)
+    for k in sorted(shapes):
+        shape = shapes[k]
+        if k.endswith("lambda1"):
+            t = 0.5 + torch.rand(shape, generator=g, device=device, dtype=torch.float32)
+        elif "cls_token" in k or "position_embeddings" in k or "mask_token" in k:
+            t = 0.5 * rn(shape)
+        elif k == "head.conv3.bias":
+            t = torch.full(shape, 0.5, device=device)
+        elif k.endswith(".bias"):
+            t = 0.1 * rn(shape)
+        elif "norm" in k:
+            t = 1.0 + 0.2 * rn(shape)
+        else:
+            fan_in = shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1)
+            if ".resize." in k and cfg["reassemble_factors"][int(k.split(".")[3])] > 1:      # ConvTranspose2d [Cin][Cout][f][f], stride f: one tap per output
+                fan_in = shape[0]
+            t = (1.4 / math.sqrt(fan_in)) * rn(shape)
+        sd[k] = t.to(torch.bfloat16)
+    return sd
+
+
+def fingerprint(sd):
+    """float64 [keys, 3]: sum, sum of squares and first element of every tensor, keys sorted - what the fixture keeps of the weights."""
+    return torch.tensor([[float(sd[k].double().sum()), float((sd[k].double() ** 2).sum()), float(sd[k].reshape(-1)[0])] for k in sorted(sd)], dtype=torch.float64)
+
+
+def case_images(name, B=2):
+    """The uint8 model inputs [B, H, W, 3] of a fixture case: smooth ramps plus seeded noise, so that neighbouring patches differ."""
+    H, W = CASES[name]
+    g = torch.Generator().manual_seed(1000 + H * 7 + W)
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    imgs = []
+    for b in range(B):
+        base = torch.stack([128 + 100 * torch.sin(0.11 * (b + 1) * yy + 0.07 * xx + c) for c in range(3)], -1)
+        imgs.append((base + 40 * torch.randn(H, W, 3, generator=g)).clamp(0, 255).to(torch.uint8))
+    return torch.stack(imgs)
+
+
+# ---- image processor -----------------------------------------------------------------------------------------------------------------------------
+def output_size(H, W, size=518, keep_aspect_ratio=True, multiple=14):
+    sh, sw = size / H, size / W
+    if keep_aspect_ratio:
+        if abs(1 - sw) < abs(1 - sh):
+            sh = sw
+        else:
+            sw = sh
+    return round(sh * H / multiple) * multiple, round(sw * W / multiple) * multiple
+
+
+def pixel_values(u8, mean=IMAGENET_MEAN, std=IMAGENET_STD, rescale=1 / 255):
+    """uint8 [B, H, W, 3] (numpy or torch) -> float32 [B, 3, H, W] with the processor's rounding points: float64 product cast to float32, then a
+    float32 subtraction and a float32 division."""
+    a = np.asarray(u8)
+    r = (a.astype(np.float64) * rescale).astype(np.float32)
+    r = (r - np.array(mean, np.float32)) / np.array(std, np.float32)
+    return torch.from_numpy(np.ascontiguousarray(r.transpose(0, 3, 1, 2)))
+
+
+def patch_rows(pv, P, Kp=None):
+    """[B, 3, H, W] -> the rows [B * ph * pw, Kp] of the patch-embedding GEMM: column c P^2 + ky P + kx, zeros in the pad."""
+    B, C, H, W = pv.shape
+    ph, pw = H // P, W // P
+    rows = pv.reshape(B, C, ph, P, pw, P).permute(0, 2, 4, 1, 3, 5).reshape(B * ph * pw, C * P * P)
+    Kp = (C * P * P + 63) // 64 * 64 if Kp is None else Kp
+    return F.pad(rows, (0, Kp - C * P * P))
+
+
+def resize_pil_tables(u8, h, w, filt="bicubic"):
+    """PIL's two-pass 8-bit resampler driven by unigen_amd.image.resample_tables, in numpy: [H, W, C] uint8 -> [h, w, C]."""
+    from unigen_amd.image import resample_tables
+
+    def one_pass(a, out):
+        b, c, _ = resample_tables(a.shape[1], out, filt)
+        r = np.zeros((a.shape[0], out, a.shape[2]), np.uint8)
+        for o in range(out):
+            x0, n = int(b[o, 0]), int(b[o, 1])
+            acc = (a[:, x0:x0 + n].astype(np.int64) * c[o, :n, None].astype(np.int64)).sum(1) + (1 << 21)
+            r[:, o] = np.clip(acc >> 22, 0, 255)
+        return r
+
+    a = np.asarray(u8)
+    if a.shape[1] != w:
+        a = one_pass(a, w)
+    if a.shape[0] != h:
+        a = one_pass(a.transpose(1, 0, 2), h).transpose(1, 0, 2)
+    return a
+
+
+def postprocess(depth, H, W):
+    """post_process_depth_estimation + the pipeline's formatting: fp32 [h, w] -> (fp32 [H, W], uint8 [H, W])."""
+    d = F.interpolate(depth[None, None], size=(H, W), mode="bicubic", align_corners=False).squeeze(0).squeeze(0)
+    a = d.numpy()
+    a = (a - a.min()) / (a.max() - a.min())
+    return d, torch.from_numpy((a * 255).astype("uint8"))
+
+
+def minmax_u8(d):
+    """numpy's float32 arithmetic of the pipeline on fp32 [H, W]; a constant image gives 0 (the kernel's documented choice)."""
+    a = np.asarray(d, dtype=np.float32)
+    lo, hi = a.min(), a.max()
+    if hi == lo:
+        return np.zeros(a.shape, np.uint8)
+    return (((a - lo) / (hi - lo)) * np.float32(255)).astype("uint8")
+
+
+# ---- kernel restatements (float64 unless stated) -------------------------------------------------------------------------------------------------
+def deconv_scatter(prod, bias, B, h, w, f, Cout, Cp):
+    """prod [B h w, f f Cout] -> NHWC [B, h f, w f, Cp], bias added, zeros in the pad channels."""
+    y = prod.reshape(B, h, w, f, f, Cout).permute(0, 1, 3, 2, 4, 5).reshape(B, h * f, w * f, Cout) + bias
+    return F.pad(y, (0, Cp - Cout))
+
+
+def bilinear_nhwc(x, Ho, Wo, align):
+    return F.interpolate(x.permute(0, 3, 1, 2), size=(Ho, Wo), mode="bilinear", align_corners=align).permute(0, 2, 3, 1).contiguous()
+
+
+def bicubic(x, Ho, Wo):
+    return F.interpolate(x[:, None], size=(Ho, Wo), mode="bicubic", align_corners=False)[:, 0]
+
+
+def head_out(x, C, w, bias, max_depth=1.0, metric=False):
+    v = (torch.relu(x[..., :C]) * w).sum(-1) + bias
+    return (torch.sigmoid(v) if metric else torch.relu(v)) * max_depth
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------------------------------------
+def forward(sd, cfg, pv, dtype=torch.float64, round_bf16=False):
+    """pixel_values [B, 3, H, W] -> dict(embeddings [B, T, D], feature_maps 4 x [B, T, D], reassembled / fused 4 x NCHW, predicted_depth [B, H, W])."""
+    r = (lambda t: t.to(torch.bfloat16).to(dtype)) if round_bf16 else (lambda t: t)
+    w = {k: v.to(dtype) for k, v in sd.items()}
+    b = cfg["backbone_config"]
+    D, P, nh, eps = b["hidden_size"], b["patch_size"], b["num_attention_heads"], b["layer_norm_eps"]
+    B, _, H, W = pv.shape
+    ph, pw = H // P, W // P
+    x = r(pv.to(dtype))
+    e = "backbone.embeddings."
+    x = r(F.conv2d(x, w[e + "patch_embeddings.projection.weight"], w[e + "patch_embeddings.projection.bias"], stride=P)).flatten(2).transpose(1, 2)
+    x = torch.cat([w[e + "cls_token"].expand(B, -1, -1), x], 1)
+    pos = w[e + "position_embeddings"]
+    n0 = int(round((pos.shape[1] - 1) ** 0.5))
+    if (ph, pw) != (n0, n0):
+        grid = pos[:, 1:].reshape(1, n0, n0, D).permute(0, 3, 1, 2)
+        grid = r(F.interpolate(grid.to(torch.float32), size=(ph, pw), mode="bicubic", align_corners=False).to(dtype))
+        pos = torch.cat([pos[:, :1], grid.permute(0, 2, 3, 1).reshape(1, -1, D)], 1)
+    x = r(x + pos)
+    out = dict(embeddings=x)
+    lin = lambda t, k: r(F.linear(t, w[k + ".weight"], w[k + ".bias"]))
+    ln = lambda t, k: r(F.layer_norm(t, (D,), w[k + ".weight"], w[k + ".bias"], eps))
+    hs = [x]
+    for i in range(b["num_hidden_layers"]):
+        k = f"backbone.encoder.layer.{i}."
+        h = ln(x, k + "norm1")
+        q, kk, v = (lin(h, k + "attention.attention." + n).view(B, -1, nh, D // nh).transpose(1, 2) for n in ("query", "key", "value"))
+        p = torch.softmax(q @ kk.transpose(-1, -2) * (D // nh) ** -0.5, -1)
+        a = r((p @ v).transpose(1, 2).reshape(B, -1, D))
+        x = r(x + r(lin(a, k + "attention.output.dense") * w[k + "layer_scale1.lambda1"]))
+        h = ln(x, k + "norm2")
+        h = r(F.gelu(lin(h, k + "mlp.fc1")))
+        x = r(x + r(lin(h, k + "mlp.fc2") * w[k + "layer_scale2.lambda1"]))
+        hs.append(x)
+    fms = [ln(hs[i], "backbone.layernorm") if b.get("apply_layernorm", True) else hs[i] for i in b["out_indices"]]
+    out["feature_maps"] = fms
+    conv = lambda t, k, **kw: r(F.conv2d(t, w[k + ".weight"], w.get(k + ".bias"), **kw))
+    reasm, maps = [], []
+    for i, (fm, f) in enumerate(zip(fms, cfg["reassemble_factors"])):
+        k = f"neck.reassemble_stage.layers.{i}."
+        y = fm[:, 1:].reshape(B, ph, pw, D).permute(0, 3, 1, 2)
+        y = conv(y, k + "projection")
+        if f > 1:
+            y = r(F.conv_transpose2d(y, w[k + "resize.weight"], w[k + "resize.bias"], stride=int(f)))
+        elif f < 1:
+            y = conv(y, k + "resize", stride=int(1 / f), padding=1)
+        reasm.append(y)
+        maps.append(conv(y, f"neck.convs.{i}", padding=1))
+    out["reassembled"] = reasm
+
+    def rcu(t, k):
+        y = conv(torch.relu(t), k + ".convolution1", padding=1)
+        y = conv(torch.relu(y), k + ".convolution2", padding=1)
+        return r(y + t)
+
+    fused, h = [], None
+    maps = maps[::-1]
+    for i, m in enumerate(maps):
+        k = f"neck.fusion_stage.layers.{i}."
+        if h is None:
+            h = m
+        else:
+            if h.shape != m.shape:
+                m = r(F.interpolate(m, size=h.shape[2:], mode="bilinear", align_corners=False))
+            h = r(h + rcu(m, k + "residual_layer1"))
+        h = rcu(h, k + "residual_layer2")
+        size = dict(size=maps[i + 1].shape[2:]) if i + 1 < len(maps) else dict(scale_factor=2)
+        h = r(F.interpolate(h, **size, mode="bilinear", align_corners=True))
+        h = conv(h, k + "projection")
+        fused.append(h)
+    out["fused"] = fused
+    h = conv(fused[cfg["head_in_index"]], "head.conv1", padding=1)
+    h = r(F.interpolate(h, (ph * P, pw * P), mode="bilinear", align_corners=True))
+    h = torch.relu(conv(h, "head.conv2", padding=1))
+    h = conv(h, "head.conv3")
+    h = r(torch.sigmoid(h)) if cfg["depth_estimation_type"] == "metric" else torch.relu(h)
+    out["predicted_depth"] = r(h * (cfg.get("max_depth") or 1)).squeeze(1)
+    return out
+
+
+def stage_list(out):
+    """(name, tensor) pairs of a forward's dict, NCHW maps as NHWC."""
+    items = [("embeddings", out["embeddings"])]
+    items += [(f"feature_maps.{i}", t) for i, t in enumerate(out["feature_maps"])]
+    items += [(f"reassembled.{i}", t.permute(0, 2, 3, 1)) for i, t in enumerate(out["reassembled"])]
+    items += [(f"fused.{i}", t.permute(0, 2, 3, 1)) for i, t in enumerate(out["fused"])]
+    return items + [("predicted_depth", out["predicted_depth"])]
+
+
+def rel_l2(a, b):
+    a, b = a.double(), b.double()
+    return float((a - b).norm() / b.norm().clamp_min(1e-300))
+
+
+# ---- the rounding kernels' cases: shared by tests/test_depth_gpu.py and tests/golden/make_depth_golden.py (which measures c on them) ----------------
+BILINEAR_SIZES = [((1, 1), (2, 2)), ((2, 2), (3, 4)), ((3, 4), (6, 8)), ((4, 3), (56, 42)), ((5, 7), (5, 7)), ((5, 7), (3, 4))]
+
+
+def kernel_cases():
+    return {
+        "deconv_scatter": [dict(f=f, Cout=co, Cp=cp, h=h, w=w) for f in (2, 4) for co, cp in ((24, 64), (128, 128)) for h, w in ((1, 1), (3, 5))],
+        "bilinear": [dict(src=s, dst=d, C=C, align=a) for s, d in BILINEAR_SIZES for C in (8, 64) for a in (True, False)],
+        "head_out": [dict(H=H, W=W, metric=m) for H, W in ((1, 1), (28, 28)) for m in (False, True)],
+        "bicubic": [dict(src=s, dst=d) for s, d in (((2, 2), (5, 3)), ((28, 42), (45, 33)), ((56, 98), (60, 100)))],
+    }
+
+
+def _bf(t):
+    return t.to(torch.bfloat16).float()
+
+
+def kernel_inputs(name, case, B=2):
+    """Seeded fp32 inputs, bf16-representable wherever the bf16 entry stores bf16 (so both entries share one truth)."""
+    g = torch.Generator().manual_seed(sum(ord(ch) for ch in name + repr(sorted(case.items()))))
+    rn = lambda *s: torch.randn(*s, generator=g)
+    if name == "deconv_scatter":
+        return dict(prod=3 * rn(B * case["h"] * case["w"], case["f"] ** 2 * case["Cout"]), bias=_bf(rn(case["Cout"])))
+    if name == "bilinear":
+        return dict(x=_bf(2 * rn(B, *case["src"], case["C"])))
+    if name == "head_out":
+        x = _bf(2 * rn(B, case["H"], case["W"], 64))
+        return dict(x=x, w=_bf(0.3 * rn(32)), bias=_bf(torch.tensor([0.5])), max_depth=20.0 if case["metric"] else 1.0)
+    if name == "bicubic":
+        return dict(x=5 * rn(B, *case["src"]))
+    raise KeyError(name)
+
+
+def kernel_truth(name, case, dtype=torch.float64, B=2):
+    """-> (the result computed by torch on the CPU in `dtype`, the magnitude the bound c * 2^-24 * scale refers to)."""
+    i = {k: (v.to(dtype) if isinstance(v, torch.Tensor) else v) for k, v in kernel_inputs(name, case, B).items()}
+    if name == "deconv_scatter":
+        return deconv_scatter(i["prod"], i["bias"], B, case["h"], case["w"], case["f"], case["Cout"], case["Cp"]), float(max(i["prod"].abs().max(), i["bias"].abs().max()))
+    if name == "bilinear":
+        return bilinear_nhwc(i["x"], *case["dst"], case["align"]), float(i["x"].abs().max())
+    if name == "head_out":
+        scale = ((torch.relu(i["x"][..., :32]) * i["w"].abs()).sum(-1) + i["bias"].abs()).double() * i["max_depth"]
+        return head_out(i["x"], 32, i["w"], i["bias"], i["max_depth"], case["metric"]), scale
+    if name == "bicubic":
+        return bicubic(i["x"], *case["dst"]), float(i["x"].abs().max())
+    raise KeyError(name)

@@ -3,6 +3,7 @@
 
     Condition("canny", raw_img=img).encode(pipe) -> (tokens [B, N, 4C], ids [N, 3], type_id [N, 1])
     Condition("deblurring", raw_img=deblurring_image(img), no_process=True).encode(pipe)
+    Condition("depth", raw_img=depth_image(img, model), no_process=True).encode(pipe)        model: unigen_amd.depth.DepthAnythingForDepthEstimation
 
 `pipe` needs `image_processor` (unigen_amd.image.VaeImageProcessor) and `vae` (unigen_amd.vae.AutoencoderKL). Images are PIL images, uint8 ndarrays
 or uint8 tensors [H, W, C]; a condition image comes back in the kind it went in as (PIL in, PIL out).
@@ -55,6 +56,23 @@ def deblurring_image(raw_img):
     return I.gaussian_blur(rgb.contiguous() if isinstance(rgb, torch.Tensor) else rgb, 10)      # a replicated gray tensor is a stride-0 view
 
 
+def depth_image(raw_img, model, processor=None):
+    """The reference's "depth" condition image (src/condition.py:52-62), `depth_pipe(raw_img.convert("RGB"))["depth"].convert("RGB")`, in the kind of
+    `raw_img`; `model` is a unigen_amd.depth.DepthAnythingForDepthEstimation, `processor` a DepthImageProcessor (default: depth-anything's settings).
+    A GPU tensor stays on the GPU and nothing synchronises with the host."""
+    from .depth import _estimate
+    if not I._is_pil(raw_img) and raw_img.ndim not in (2, 3):
+        raise ValueError(f"depth_image takes one image [H, W] or [H, W, C], got {tuple(raw_img.shape)}")
+    _, u8 = _estimate(model, raw_img, processor, 3)                       # a gray image is replicated by the patch kernel: convert("RGB")
+    out = u8[0]
+    if I._is_pil(raw_img):
+        from PIL import Image
+        return Image.fromarray(out.cpu().numpy())
+    if isinstance(raw_img, torch.Tensor):
+        return out if raw_img.is_cuda else out.to(raw_img.device)
+    return out.cpu().numpy()
+
+
 class Condition(object):
     def __init__(self, condition_type: str, raw_img=None, no_process: bool = False, condition=None, condition_ids=None, mask=None) -> None:
         self.condition_type = condition_type
@@ -70,8 +88,9 @@ class Condition(object):
     def get_condition(self, condition_type: str, raw_img):
         """Returns the condition image (src/condition.py:46-81)."""
         if condition_type == "depth":
-            raise NotImplementedError("condition type 'depth' needs a depth-estimation model (the reference runs transformers' depth-anything pipeline), "
-                                      "which this package does not have: pass the depth map as `condition=` / `no_process=True` (docs/NEXT_ROWS.md)")
+            raise NotImplementedError("condition type 'depth' needs a depth-estimation model (the reference runs transformers' depth-anything pipeline); "
+                                      "`depth_image` of this module runs one on the GPU (unigen_amd.depth) - pass Condition(\"depth\", "
+                                      "raw_img=depth_image(img, model), no_process=True) (docs/NEXT_ROWS.md: why this branch still refuses)")
         if condition_type == "canny":
             src = np.array(raw_img) if I._is_pil(raw_img) else raw_img
             edges = I.canny(src, 100, 200)                                   # cv2.Canny(img, 100, 200)

@@ -36,13 +36,30 @@ def _lanczos(x: float) -> float:
     return _sinc(x) * _sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
 
 
+def _bicubic(x: float) -> float:
+    a = -0.5                                         # PIL's BICUBIC (torch's bicubic interpolation has a = -0.75)
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+_FILTERS = {"lanczos": (_lanczos, 3.0), "bicubic": (_bicubic, 2.0)}      # name -> (kernel, support) of Resample.c
+
+
 @lru_cache(maxsize=64)
-def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, int]:
-    """-> (bounds int32 [out, 2] = (first input coordinate, taps), coef int32 [out, ksize] 22-bit fixed point, ksize) of one Lanczos (a = 3) pass."""
+def resample_tables(in_size: int, out_size: int, filter: str = "lanczos") -> Tuple[np.ndarray, np.ndarray, int]:
+    """-> (bounds int32 [out, 2] = (first input coordinate, taps), coef int32 [out, ksize] 22-bit fixed point, ksize) of one pass of PIL's
+    "lanczos" (a = 3) or "bicubic" (a = -0.5) filter."""
+    if filter not in _FILTERS:
+        raise NotImplementedError(f"filter={filter!r}: one of {sorted(_FILTERS)}")
+    kernel, support = _FILTERS[filter]
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 3.0 * filterscale
+    support = support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     coef = np.zeros((out_size, ksize), np.int32)
@@ -52,7 +69,7 @@ def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
@@ -67,12 +84,12 @@ def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray
 _device_tables = {}
 
 
-def _tables_on(device: torch.device, in_size: int, out_size: int):
-    key = (str(device), in_size, out_size)
+def _tables_on(device: torch.device, in_size: int, out_size: int, filter: str = "lanczos"):
+    key = (str(device), in_size, out_size, filter)
     if key not in _device_tables:
         if len(_device_tables) >= 64:
             _device_tables.clear()
-        b, c, k = resample_tables(in_size, out_size)
+        b, c, k = resample_tables(in_size, out_size, filter)
         _device_tables[key] = (torch.from_numpy(b).to(device), torch.from_numpy(c).to(device), k)
     return _device_tables[key]
 
@@ -294,12 +311,12 @@ class VaeImageProcessor:
         return [Image.fromarray(a[..., 0], mode="L") if a.shape[-1] == 1 else Image.fromarray(a) for a in arr]
 
 
-def resize_u8(x: torch.Tensor, height: int, width: int) -> torch.Tensor:
-    """PIL's `Image.resize((width, height), LANCZOS)` of a uint8 [B, H, W, C] GPU tensor, bit for bit."""
+def resize_u8(x: torch.Tensor, height: int, width: int, filter: str = "lanczos") -> torch.Tensor:
+    """PIL's `Image.resize((width, height), LANCZOS)` (or BICUBIC with filter="bicubic") of a uint8 [B, H, W, C] GPU tensor, bit for bit."""
     from . import ops
     B, H, W, Cc = x.shape
     if (H, W) == (height, width):
         return x
-    xt = _tables_on(x.device, W, width) if W != width else None
-    yt = _tables_on(x.device, H, height) if H != height else None
+    xt = _tables_on(x.device, W, width, filter) if W != width else None
+    yt = _tables_on(x.device, H, height, filter) if H != height else None
     return ops.img_resize_u8(x, height, width, xt, yt)

@@ -178,7 +178,20 @@ SIGNATURES.update({
     "ug_img_blur_workspace_bytes": (i64, [i64, i64, i64, i32]),
     "ug_img_box_blur_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
 })
-_F32_TWINS = {"ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
+# depth condition (csrc/depth.hip); mean / std of ug_img_u8_to_patches are host arrays of 3 floats
+SIGNATURES.update({
+    "ug_img_u8_to_patches": (i32, [vp, i64, i64, i64, i64, i64, i32, i32, C.c_double, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, vp]),
+    "ug_relu": (i32, [vp, vp, i64, vp]),
+    "ug_deconv_scatter_nhwc": (i32, [vp, i64, vp, vp, i64, i64, i64, i32, i64, i64, vp]),
+    "ug_bilinear_nhwc": (i32, [vp, i64, i64, i64, i64, vp, i64, i64, i32, vp]),
+    "ug_depth_head_out": (i32, [vp, i64, i64, i64, vp, vp, f32, i32, vp, vp]),
+    "ug_bicubic_f32": (i32, [vp, i64, i64, i64, vp, i64, i64, vp]),
+    "ug_minmax_workspace_bytes": (i64, [i64, i64]),
+    "ug_minmax_to_u8": (i32, [vp, i64, i64, vp, i32, vp, i64, vp]),
+})
+_F32_TWINS = {"ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32": "ug_relu", "ug_deconv_scatter_nhwc_f32": "ug_deconv_scatter_nhwc",
+              "ug_bilinear_nhwc_f32": "ug_bilinear_nhwc", "ug_depth_head_out_f32": "ug_depth_head_out",
+              "ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
               "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu", "ug_gelu_erf_f32": "ug_gelu_erf",
               "ug_flow_noise_f32": "ug_flow_noise", "ug_flow_loss_f32": "ug_flow_loss", "ug_flow_loss_bwd_f32": "ug_flow_loss_bwd",
               "ug_lora_wgrad_f32": "ug_lora_wgrad_bf16","ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",

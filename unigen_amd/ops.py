@@ -1074,3 +1074,91 @@ def img_box_blur_u8(x: torch.Tensor, cx, cy, passes: int = 1, fuse: bool = True)
     L.check(lib.ug_img_box_blur_u8(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), H * W * Cc, W * Cc, *(int(v) for v in cx), *(int(v) for v in cy), int(passes),
                                    int(bool(fuse)), ws.data_ptr(), ws.numel(), _stream()), "ug_img_box_blur_u8")
     return out
+
+
+# ---- depth condition (csrc/depth.hip): the glue of Depth Anything that is neither a GEMM nor a convolution; activations NHWC ----------------------------
+def img_u8_to_patches(x: torch.Tensor, patch: int, mean, std, rescale: float = 1 / 255, dtype=bf16, Kp: Optional[int] = None) -> torch.Tensor:
+    """uint8 [B, H, W, C] (a strided view is fine) -> the rows [B * (H/P) * (W/P), Kp] of the patch-embedding GEMM in `dtype`, normalised as
+    DPTImageProcessor does; Kp defaults to 3 P^2 rounded up to a multiple of 64, the pad columns are zero."""
+    B, H, W, Cc, sb, sr = _img(x, "x")
+    if dtype not in (bf16, f32):
+        raise TypeError(f"dtype: torch.bfloat16 or torch.float32, got {dtype}")
+    Kp = (3 * patch * patch + 63) // 64 * 64 if Kp is None else Kp
+    if H % patch or W % patch:
+        raise ValueError(f"image {H}x{W} is not a multiple of the patch size {patch}")
+    out = torch.empty(B * (H // patch) * (W // patch), Kp, dtype=dtype, device=x.device)
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    L.check(_fn("ug_img_u8_to_patches", dtype)(x.data_ptr(), sb, sr, B, H, W, Cc, patch, float(rescale), m3, s3, out.data_ptr(), Kp, Kp, _stream()),
+            "ug_img_u8_to_patches")
+    return out
+
+
+def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """max(x, 0), contiguous, numel a multiple of 8; out may be x itself."""
+    dt = _act(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "out", dt)
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
+    L.check(_fn("ug_relu", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_relu")
+    return out
+
+
+def deconv_scatter_nhwc(prod: torch.Tensor, bias: torch.Tensor, *, B: int, h: int, w: int, f: int, Cout: int, Cp: int) -> torch.Tensor:
+    """Second half of ConvTranspose2d(k = s = f): prod fp32 [B*h*w, f*f*Cout] (the GEMM against the weight laid out [(ky, kx, co)][Cin]) ->
+    [B, h*f, w*f, Cp] in bias' dtype = rnd(prod + bias), zeros in the pad channels."""
+    _chk(prod, "prod", f32)
+    dt = _act(bias, "bias")
+    assert prod.dim() == 2 and prod.shape[0] == B * h * w and prod.shape[1] >= f * f * Cout and bias.numel() == Cout and bias.is_contiguous()
+    out = torch.empty(B, h * f, w * f, Cp, dtype=dt, device=prod.device)
+    L.check(_fn("ug_deconv_scatter_nhwc", dt)(prod.data_ptr(), prod.stride(0), bias.data_ptr(), out.data_ptr(), B, h, w, f, Cout, Cp, _stream()),
+            "ug_deconv_scatter_nhwc")
+    return out
+
+
+def bilinear_nhwc(x: torch.Tensor, Ho: int, Wo: int, align_corners: bool) -> torch.Tensor:
+    """F.interpolate(mode="bilinear") of NHWC [B, H, W, C] (C a multiple of 8) to [B, Ho, Wo, C]."""
+    dt = _act(x, "x")
+    assert x.dim() == 4 and x.is_contiguous(), x.shape
+    B, H, W, Cc = x.shape
+    out = torch.empty(B, Ho, Wo, Cc, dtype=dt, device=x.device)
+    L.check(_fn("ug_bilinear_nhwc", dt)(x.data_ptr(), B, H, W, Cc, out.data_ptr(), Ho, Wo, int(bool(align_corners)), _stream()), "ug_bilinear_nhwc")
+    return out
+
+
+def depth_head_out(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, C_: int, max_depth: float = 1.0, metric: bool = False) -> torch.Tensor:
+    """x [B, H, W, Cp] (channels [0, C_) used) -> fp32 [B, H, W] = act(bias + sum_c w[c] relu(x[c])) * max_depth; act is ReLU, or sigmoid if metric."""
+    dt = _act(x, "x")
+    _chk(w, "w", dt); _chk(bias, "bias", dt)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.numel() == C_ and bias.numel() == 1 and C_ <= x.shape[-1]
+    B, H, W, Cp = x.shape
+    out = torch.empty(B, H, W, dtype=f32, device=x.device)
+    L.check(_fn("ug_depth_head_out", dt)(x.data_ptr(), B * H * W, C_, Cp, w.data_ptr(), bias.data_ptr(), float(max_depth), int(bool(metric)), out.data_ptr(),
+                                       _stream()), "ug_depth_head_out")
+    return out
+
+
+def bicubic_f32(x: torch.Tensor, Ho: int, Wo: int) -> torch.Tensor:
+    """F.interpolate(mode="bicubic", align_corners=False) of fp32 [B, H, W] to [B, Ho, Wo]."""
+    _chk(x, "x", f32)
+    assert x.dim() == 3 and x.is_contiguous(), x.shape
+    B, H, W = x.shape
+    out = torch.empty(B, Ho, Wo, dtype=f32, device=x.device)
+    L.check(L.load().ug_bicubic_f32(x.data_ptr(), B, H, W, out.data_ptr(), Ho, Wo, _stream()), "ug_bicubic_f32")
+    return out
+
+
+def minmax_workspace_bytes(B: int, HW: int) -> int:
+    return int(L.load().ug_minmax_workspace_bytes(B, HW))
+
+
+def minmax_to_u8(d: torch.Tensor, channels: int = 1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [B, H, W] -> uint8 [B, H, W, channels] (1 or 3 equal channels): per image uint8(trunc((d - min) / (max - min) * 255)); a constant image
+    gives 0. `workspace`: a uint8 tensor of at least minmax_workspace_bytes(B, H * W), contents irrelevant."""
+    _chk(d, "d", f32)
+    assert d.dim() == 3 and d.is_contiguous(), d.shape
+    B, H, W = d.shape
+    ws = torch.empty(minmax_workspace_bytes(B, H * W), dtype=u8, device=d.device) if workspace is None else workspace
+    _chk(ws, "workspace", u8)
+    out = torch.empty(B, H, W, channels, dtype=u8, device=d.device)
+    L.check(L.load().ug_minmax_to_u8(d.data_ptr(), B, H * W, out.data_ptr(), channels, ws.data_ptr(), ws.numel(), _stream()), "ug_minmax_to_u8")
+    return out
