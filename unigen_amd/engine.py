@@ -140,6 +140,9 @@ class HipModule(nn.Module):
         self.trainable_control_modules: Dict[str, nn.Module] = {}
         self._lora_sites: Dict[str, _LoRAHolder] = {}     # projection prefix -> its adapter-carrying holder (add_lora)
         self._lora_fused: Dict[Tuple, Tuple] = {}         # fused adapter operands per launch (prefixes + adapter state), see _lora_operands
+        self._lora_merge_only: Dict[str, Dict[str, Tuple]] = {}   # adapter -> {module: (A, B, alpha)} outside LORA_CAPABLE (load_lora_weights): run only merged
+        self._lora_merged: Dict[str, float] = {}          # adapter -> lora_scale of the adapters fuse_lora merged into the base weights
+        self._lora_backup: Optional[Dict[str, torch.Tensor]] = None   # parameter name -> its bytes before the first fuse_lora (None: nothing fused / no backup)
 
     def _check_dtype(self, *inputs: torch.Tensor):
         """bf16 = the product path; fp32 = the verification path (every C-ABI call goes to its `_f32` twin, unigen_amd/ops.py).
@@ -328,6 +331,206 @@ class HipModule(nn.Module):
         if set(used) != set(want):
             raise KeyError(f"load_lora_state_dict: missing {sorted(set(want) - set(used))[:4]} ...")
         return used
+
+    # ------------------------------------------------------------------ LoRA files and the merge into the base weights ---------------
+    @classmethod
+    def lora_capable(cls, name: str) -> bool:
+        """Does the module `name` take a live adapter (the rule add_lora enforces)? Everything else can only be merged (fuse_lora)."""
+        return any(name == c or name.endswith("." + c) for c in cls.LORA_CAPABLE) and name != "proj_out" and ".experts." not in name
+
+    def load_lora_weights(self, src, adapter_name: str = "default", strict: bool = True):
+        """Read a LoRA file (`src`: a path - unigen_amd/lora_io.py `read_lora_file` - or a state dict in the diffusers / PEFT, kohya or BFL naming),
+        infer rank and alpha per module, and attach it as `adapter_name`: the modules in LORA_CAPABLE through `add_lora(..., A=, B=)` - live, switched by
+        `enable_lora` as before - the others (AdaLN linears, embedders, experts, proj_out ...) as merge-only entries that reach the output only through
+        `fuse_lora()`; until then the forward refuses to run (a partly applied adapter is never computed). Tensors are cast to the model's dtype.
+        Module names the model does not have raise under `strict`. Returns lora_io.LoraReport(live, merge_only, ignored)."""
+        from . import lora_io
+        sd = src if isinstance(src, dict) else lora_io.read_lora_file(src)
+        entries, report = lora_io.convert(sd, self, strict=strict)
+        if not entries:
+            raise ValueError("load_lora_weights: the file holds no adapter weight for this model")
+        taken = set(self._lora_merge_only.get(adapter_name, ())) | {n for n, m in self._lora_sites.items() if adapter_name in m.lora_A}
+        if taken & set(entries):
+            raise L.UniGenHipError(f"load_lora_weights: adapter {adapter_name!r} already covers {sorted(taken & set(entries))[:4]} ...; unload_lora_weights first")
+        if adapter_name in self._lora_merged:
+            raise L.UniGenHipError(f"load_lora_weights: adapter {adapter_name!r} is fused into the weights; unfuse_lora first")
+        groups: Dict[Tuple[int, float], list] = {}
+        for name in report.live:
+            A, B, alpha = entries[name]
+            groups.setdefault((A.shape[0], float(alpha if alpha is not None else A.shape[0])), []).append(name)
+        # add_lora matches its targets by PEFT's suffix rule: a full module name must not ALSO be the tail of a deeper module's name
+        modules = dict(self.named_modules())
+        for name in report.live:
+            extra = [n for n in modules if n.endswith("." + name) and modules[n]._parameters.get("weight") is not None]
+            if extra:
+                raise L.UniGenHipError(f"load_lora_weights: {name!r} is also the suffix of {extra[:2]}; the file's entry cannot be attached to one module alone")
+        try:
+            for (r, alpha), names in groups.items():
+                hits = self.add_lora(names, adapter_name, r, alpha, A={n: entries[n][0] for n in names}, B={n: entries[n][1] for n in names})
+                if set(hits) != set(names):
+                    raise L.UniGenHipError(f"load_lora_weights: add_lora attached {sorted(set(hits) ^ set(names))[:4]} beyond / short of the file's modules")
+        except Exception:
+            self._drop_live_adapter(adapter_name, only=set(report.live))      # nothing of a file that failed part-way stays attached
+            raise
+        dev, dt = self.device, self.dtype
+        for name in report.merge_only:
+            A, B, alpha = entries[name]
+            self._lora_merge_only.setdefault(adapter_name, {})[name] = (A.detach().to(dev, dt).contiguous(), B.detach().to(dev, dt).contiguous(),
+                                                                        float(alpha if alpha is not None else A.shape[0]))
+        return report
+
+    def _lora_guard(self) -> None:
+        """Refuse a forward while an adapter has merge-only entries that are not merged: only part of it would be applied."""
+        if self._lora_merge_only:
+            pending = [a for a in self._lora_merge_only if a not in self._lora_merged]
+            if pending:
+                raise L.UniGenHipError(f"adapter(s) {pending} carry weights for modules outside LORA_CAPABLE (e.g. {next(iter(self._lora_merge_only[pending[0]]))}) that only run "
+                                       "merged into the base weights: call fuse_lora() before the forward (or unload_lora_weights)")
+
+    def _weights_rewritten(self, params) -> None:
+        """Base weights were overwritten through raw pointers (the merge GEMM) - `_version` did not move - or restored: drop everything derived from
+        them: the backward's transposed copies of frozen weights (autograd._wt_cache) and the fused adapter operands (self._lora_fused)."""
+        if params:
+            torch.autograd.graph.increment_version(list(params))
+        self._storage_moved()
+        self._lora_fused.clear()
+
+    @staticmethod
+    def _merge_into(w: torch.Tensor, blocks) -> None:
+        """w [N_out, K_in] (a view inside its pack) <- dtype(w + Bs A_cat), Bs = dtype(scaling_a * B_a), in place, every adapter of this weight as one
+        concatenated rank - w is rounded ONCE. Two existing launches: P = Bs A_cat through ug_gemm with the fp32 epilogue (UG_EPI_F32: the accumulators
+        as they are), then w = dtype(w + P) through ug_add_rowbcast_f32. (One UG_EPI_RES_SCALE launch with the residual aliased to the output also
+        merges in place, but that epilogue rounds the product to bf16 before it adds the residual; the second rounding moved a fused bf16 forward
+        from 0.0089 to 0.0143 off the fp32 oracle: profiles/lora_merge_rounding.log, DESIGN.md section 7a addendum.) A weight the kernels' alignment rules refuse is staged through a
+        padded temporary."""
+        from .lora import _RANK_PAD
+        N, K = w.shape
+        R = sum(a.shape[0] for a, _, _ in blocks)
+        Rp = (R + _RANK_PAD - 1) // _RANK_PAD * _RANK_PAD
+        A_cat = torch.zeros(Rp, K, device=w.device, dtype=w.dtype)
+        Bs = torch.zeros(N, Rp, device=w.device, dtype=w.dtype)
+        c0 = 0
+        for a, b, sc in blocks:
+            r = a.shape[0]
+            A_cat[c0:c0 + r] = a
+            Bs[:, c0:c0 + r] = (b.float() * sc).to(w.dtype)
+            c0 += r
+        direct = K % 8 == 0 and w.stride(1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0
+        Kp = K if direct else (K + 63) // 64 * 64
+        dst = w if direct else torch.zeros(N, Kp, device=w.device, dtype=w.dtype)
+        if not direct:
+            dst[:, :K].copy_(w)
+            A_cat = torch.nn.functional.pad(A_cat, (0, Kp - K))
+        At = ops.transpose(A_cat)                                            # [K_in, Rp]: the GEMM's W operand, nn.Linear layout over the rank
+        P = torch.empty(N, Kp, device=w.device, dtype=torch.float32)
+        ops.gemm(Bs, At, None, P, M=N, epilogue=L.EPI_F32)
+        ops.add_rowbcast_f32(dst, P, N)
+        if not direct:
+            w.copy_(dst[:, :K])
+
+    @torch.no_grad()
+    def fuse_lora(self, adapter_names: Optional[Sequence[str]] = None, lora_scale: float = 1.0, backup: Optional[str] = "device") -> Sequence[str]:
+        """Merge the named adapters (None: every adapter that is not merged yet) into the base weights, live sites and merge-only entries alike:
+        W <- dtype(W + sum_a dtype(scaling_a * lora_scale * B_a) A_a), rounded once, in place: one GEMM launch + one add per weight (`_merge_into`; fp32
+        models take the fp32 twins).
+        Live sites use their CURRENT scaling. A merged adapter stops contributing at run time whatever `enable_lora` or `joint_attention_kwargs["scale"]`
+        say: `live_adapters()` skips it, so the forward's launches are those of the adapter-free model.
+        backup: "device" / "host" keep the original bytes of every touched parameter (about 24 GB for an all-linear FLUX adapter) for `unfuse_lora`;
+        None keeps none. Merging an adapter twice is an error. Returns the names of the touched parameters."""
+        if backup not in ("device", "host", None):
+            raise ValueError(f"fuse_lora: backup must be 'device', 'host' or None, got {backup!r}")
+        known = set(self._lora_merge_only) | {a for m in self._lora_sites.values() for a in m.lora_A}
+        names = [a for a in sorted(known) if a not in self._lora_merged] if adapter_names is None else \
+            [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        for a in names:
+            if a in self._lora_merged:
+                raise L.UniGenHipError(f"fuse_lora: adapter {a!r} is already fused into the weights")
+            if a not in known:
+                raise KeyError(f"fuse_lora: no adapter named {a!r} (attached: {sorted(known)})")
+        if not names:
+            raise L.UniGenHipError("fuse_lora: no adapter to fuse")
+        if self._lora_merged and (backup is None) != (self._lora_backup is None):
+            raise L.UniGenHipError("fuse_lora: adapters are already fused with another backup mode; unfuse_lora first")
+        per_weight: Dict[str, list] = {}
+        for a in names:
+            for mod, site in self._lora_sites.items():
+                if a in site.lora_A and site.scaling[a] * lora_scale != 0.0:
+                    per_weight.setdefault(mod, []).append((site.lora_A[a].weight.data, site.lora_B[a].weight.data, site.scaling[a] * lora_scale))
+            for mod, (A, B, alpha) in self._lora_merge_only.get(a, {}).items():
+                if lora_scale != 0.0:
+                    per_weight.setdefault(mod, []).append((A, B, alpha / A.shape[0] * lora_scale))
+        if backup is not None and self._lora_backup is None:
+            self._lora_backup = {}
+        touched = []
+        for mod, blocks in per_weight.items():
+            p = self.get_parameter(mod + ".weight")
+            if backup is not None and mod + ".weight" not in self._lora_backup:
+                self._lora_backup[mod + ".weight"] = p.data.detach().clone() if backup == "device" else p.data.detach().cpu()
+            self._merge_into(p.data, blocks)
+            touched.append(p)
+        for a in names:
+            self._lora_merged[a] = float(lora_scale)
+            for site in self._lora_sites.values():
+                if a in site.lora_A:
+                    site.fused_adapters.add(a)
+        self._weights_rewritten(touched)
+        return [m + ".weight" for m in per_weight]
+
+    @torch.no_grad()
+    def unfuse_lora(self) -> None:
+        """Undo every fuse_lora: copy the backed-up bytes back - bit for bit - and let the merged live adapters contribute again. Without a backup
+        (`fuse_lora(backup=None)`) this raises: subtracting the product again in bf16 is NOT an inverse of the merge (W was rounded after the
+        addition), so there is nothing exact to restore."""
+        if not self._lora_merged:
+            raise L.UniGenHipError("unfuse_lora: no adapter is fused")
+        if self._lora_backup is None:
+            raise L.UniGenHipError("unfuse_lora: fuse_lora(backup=None) kept no copy of the original weights, and subtracting the adapters in bf16 does not "
+                                   "restore them; reload the base weights instead")
+        touched = []
+        for name, saved in self._lora_backup.items():
+            p = self.get_parameter(name)
+            p.data.copy_(saved)
+            touched.append(p)
+        self._lora_backup = None
+        for site in self._lora_sites.values():
+            site.fused_adapters.difference_update(self._lora_merged)
+        self._lora_merged.clear()
+        self._weights_rewritten(touched)
+
+    def unload_lora_weights(self, adapter_name: str) -> None:
+        """Remove the adapter: unfuse first if it is merged (every merged adapter is unfused - the backup holds the weights before all of them), then
+        drop its live layers (a holder left without adapters becomes a plain one again) and its merge-only entries."""
+        known = set(self._lora_merge_only) | {a for m in self._lora_sites.values() for a in m.lora_A}
+        if adapter_name not in known:
+            raise KeyError(f"unload_lora_weights: no adapter named {adapter_name!r} (attached: {sorted(known)})")
+        if adapter_name in self._lora_merged:
+            self.unfuse_lora()
+        self._lora_merge_only.pop(adapter_name, None)
+        self._drop_live_adapter(adapter_name)
+
+    def _drop_live_adapter(self, adapter_name: str, only=None) -> None:
+        """Remove the adapter's live layers (from the sites named in `only`, or everywhere); a holder left without adapters becomes a plain one again."""
+        for name, site in list(self._lora_sites.items()):
+            if adapter_name not in site.lora_A or (only is not None and name not in only):
+                continue
+            del site.lora_A[adapter_name], site.lora_B[adapter_name]
+            for d in (site.r, site.lora_alpha, site.scaling):
+                d.pop(adapter_name, None)
+            if adapter_name in site.active_adapters:
+                site.active_adapters.remove(adapter_name)
+            site.fused_adapters.discard(adapter_name)
+            if not site.lora_A:
+                plain = _Holder()
+                for n, p_ in site._parameters.items():
+                    plain.register_parameter(n, p_)
+                for n, m in site._modules.items():
+                    if n not in ("lora_A", "lora_B"):
+                        plain.add_module(n, m)
+                parent_name, _, leaf = name.rpartition(".")
+                (self.get_submodule(parent_name) if parent_name else self)._modules[leaf] = plain
+                del self._lora_sites[name]
+        self._pname_cache = None
+        self._lora_fused.clear()
 
     # No longer called by the forwards - the differentiable forward carries live adapters (training._lora) - but kept as it was: its behaviour is
     # pinned by the host tests.

@@ -129,6 +129,7 @@ class UniGenFlux(HipModule):
     """Drop-in for the reference `UniGenFlux(FluxTransformer2DModel)`."""
 
     multi_condition = False
+    BFL_NAMES = True          # kohya / BFL-named LoRA files map onto this engine's modules (unigen_amd/lora_io.py)
 
     # ------------------------------------------------------------------ construction ---------------------------------
     def __init__(self, config: Optional[dict] = None, device=None, dtype=BF, _init: bool = True, **kwargs):
@@ -423,6 +424,7 @@ class UniGenFlux(HipModule):
     def forward(self, *args, **kwargs):
         """Inference (no autograd: the in-place HIP engine below) or, when autograd is on and some parameter requires a gradient - the reference's
         train.py:622-662 after `init_trainable_param()` - the differentiable forward of unigen_amd/training.py. Same arguments, same 3-tuple."""
+        self._lora_guard()          # an adapter with merge-only entries (load_lora_weights) runs only after fuse_lora
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from . import training
             with self._lora_scaled(kwargs.get("joint_attention_kwargs")):

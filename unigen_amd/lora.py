@@ -43,6 +43,7 @@ class LoRALayer:
         self.lora_alpha: Dict[str, float] = {}
         self.scaling: Dict[str, float] = {}
         self.active_adapters: List[str] = []
+        self.fused_adapters: set = set()          # merged into the base weight (HipModule.fuse_lora): no longer part of the forward
 
     def add_adapter(self, name: str, r: int, lora_alpha: float, A: Optional[torch.Tensor] = None, B: Optional[torch.Tensor] = None,
                     generator: Optional[torch.Generator] = None) -> None:
@@ -84,8 +85,8 @@ class LoRALayer:
                 self.scaling[a] /= scale
 
     def live_adapters(self) -> List[str]:
-        """The adapters that contribute to this layer's output right now: active, known, scaling != 0."""
-        return [a for a in self.active_adapters if a in self.scaling and self.scaling[a] != 0.0]
+        """The adapters that contribute to this layer's output right now: active, known, scaling != 0, not merged into the base weight."""
+        return [a for a in self.active_adapters if a in self.scaling and self.scaling[a] != 0.0 and a not in self.fused_adapters]
 
 
 def fuse_adapters(layers: List[Optional["LoRALayer"]], widths: List[int], dtype, device):

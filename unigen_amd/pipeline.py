@@ -151,7 +151,45 @@ def denoise_loop(transformer, *, latents: torch.Tensor, control_tokens, prompt_e
     return latents
 
 
-class UniGenFLUXPipeline:
+class _LoraLoaderMixin:
+    """diffusers' `FluxLoraLoaderMixin` / `SD3LoraLoaderMixin` call surface over the transformer's own methods (HipModule.load_lora_weights ...):
+    the same argument names; only the transformer carries adapters (text-encoder entries of a file are reported as ignored)."""
+
+    @classmethod
+    def lora_state_dict(cls, pretrained_model_name_or_path_or_dict, **kwargs):
+        """`FluxPipeline.lora_state_dict(path)` (src/hook.py:60): `transformer.<module>.lora_A.weight` / `lora_B.weight` / `alpha` keys."""
+        from . import lora_io
+        return lora_io.lora_state_dict(pretrained_model_name_or_path_or_dict)
+
+    def _lora_transformer(self, what: str):
+        if self.transformer is None:
+            raise RuntimeError(f"{what}: assign `.transformer` first")
+        return self.transformer
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, strict: bool = True, **kwargs):
+        return self._lora_transformer("load_lora_weights").load_lora_weights(pretrained_model_name_or_path_or_dict,
+                                                                             adapter_name=adapter_name or "default", strict=strict)
+
+    def fuse_lora(self, components: Sequence[str] = ("transformer",), lora_scale: float = 1.0, safe_fusing: bool = False,
+                  adapter_names: Optional[Sequence[str]] = None, backup: Optional[str] = "device", **kwargs):
+        if list(components) != ["transformer"]:
+            raise ValueError(f"fuse_lora: only the transformer carries adapters here, got components={list(components)}")
+        return self._lora_transformer("fuse_lora").fuse_lora(adapter_names=adapter_names, lora_scale=lora_scale, backup=backup)
+
+    def unfuse_lora(self, components: Sequence[str] = ("transformer",), **kwargs):
+        if list(components) != ["transformer"]:
+            raise ValueError(f"unfuse_lora: only the transformer carries adapters here, got components={list(components)}")
+        return self._lora_transformer("unfuse_lora").unfuse_lora()
+
+    def unload_lora_weights(self, adapter_name: Optional[str] = None):
+        """diffusers removes every adapter; `adapter_name` (extra) removes one."""
+        tr = self._lora_transformer("unload_lora_weights")
+        names = [adapter_name] if adapter_name is not None else sorted(set(tr._lora_merge_only) | {a for m in tr._lora_sites.values() for a in m.lora_A})
+        for a in names:
+            tr.unload_lora_weights(a)
+
+
+class UniGenFLUXPipeline(_LoraLoaderMixin):
     """Call-surface twin of the reference `UniGenFLUXPipeline(FluxPipeline)`: the denoise loop runs here; text encoding and the VAE are
     delegated to attributes the caller attaches (`encode_prompt`, `vae`, `image_processor`), with the reference's keyword arguments."""
 
@@ -407,7 +445,7 @@ def sd3_denoise_loop(transformer, *, latents: torch.Tensor, control_latents: tor
     return latents
 
 
-class UniGenSD3Pipeline:
+class UniGenSD3Pipeline(_LoraLoaderMixin):
     """Call-surface twin of the reference `UniGenSD3Pipeline`: the denoise loop runs here, prompts are encoded by the attached native text
     encoders (unigen_amd.text) or by an attached `encode_prompt` callable; the VAE is delegated as in UniGenFLUXPipeline."""
 

@@ -349,6 +349,7 @@ class UniGenSD3(HipModule):
     def forward(self, *args, **kwargs):
         """Inference (the in-place HIP engine below, no autograd) or - autograd on and some parameter requiring a gradient, train.py:622-662 after
         `init_trainable_param()` - the differentiable forward of unigen_amd/training.py. Same arguments, same 3-tuple."""
+        self._lora_guard()          # an adapter with merge-only entries (load_lora_weights) runs only after fuse_lora
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from . import training
             with self._lora_scaled(kwargs.get("joint_attention_kwargs")):

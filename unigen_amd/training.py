@@ -305,6 +305,7 @@ def flux_forward(model, hidden_states, condition_hidden_states=None, conditionin
                  pooled_projections=None, condition_pooled_projections=None, timestep=None, img_ids=None, txt_ids=None, guidance=None,
                  condition_ids=None, gate_uniform=None, **_):
     """src/UniGenTransformer.py:1182-1271 (lists of conditions: :1360-1450) under autograd. Same return as the inference forward."""
+    model._lora_guard()
     ctl, cfg = model._ctl, model.config
     multi = isinstance(condition_hidden_states, (list, tuple))
     dt = model._check_dtype(hidden_states, encoder_hidden_states)
@@ -477,6 +478,7 @@ def _sd3_comoe(model, x, c, ctrl_enc, control_temb, condition_temb, pooled, cond
 def sd3_forward(model, hidden_states, condition_hidden_states=None, conditioning_scale: float = 1.0, encoder_hidden_states=None,
                 pooled_projections=None, condition_pooled_projections=None, timestep=None, gate_uniform=None, **_):
     """UniGenSD3.forward (src/UniGenTransformer.py:625-710) under autograd: NCHW latents in, NCHW out; the timestep is used as given."""
+    model._lora_guard()
     cfg, ctl = model.config, model._ctl
     dt = model._check_dtype(hidden_states, encoder_hidden_states)
     B, _, height, width = hidden_states.shape
