@@ -566,11 +566,6 @@ def test_add_lora_makes_the_projections_peft_shaped_layers_enable_lora_switches(
     assert m.add_lora(["proj_out", "proj_mlp"], "x", 4, 4.0, prefix="single_transformer_blocks.0.") == ["single_transformer_blocks.0.proj_mlp", "single_transformer_blocks.0.proj_out"]
     with pytest.raises(ValueError, match="no module"):
         m.add_lora(["attn.to_q"], "x", 4, 4.0, prefix="nowhere.")
-    # the training forward does not carry adapters: refused loudly while any is live
-    with pytest.raises(NotImplementedError, match="LoRA"):
-        m._refuse_lora_in_training()
-    with mod.enable_lora(list(m.modules()), []):
-        m._refuse_lora_in_training()
 
 
 def test_control_checkpoint_wire_formats(tmp_path):

@@ -9,7 +9,7 @@ import torch
 
 from unigen_amd import lib as L
 from unigen_amd.flux import UniGenFlux
-from unigen_amd.lora import fuse_adapters, fuse_adapters_autograd
+from unigen_amd.lora import adapter_operands, enable_lora, fuse_adapters, fuse_adapters_autograd
 
 TINY = dict(num_layers=2, num_single_layers=4, attention_head_dim=128, num_attention_heads=2, joint_attention_dim=64, pooled_projection_dim=64)
 ATTN = ["attn.to_q", "attn.to_k", "attn.to_v"]
@@ -69,7 +69,16 @@ def test_differentiable_fuse_equals_inference_fuse_and_routes_gradients():
     p = "control_joint_trans_blocks.0.attn."
     sites = [m._lora_sites.get(p + n) for n in ("to_q", "to_k", "to_v")] + [None]
     widths = [256, 256, 256, 64]
+    sites[0].set_scale("depth", 1.5)                                # alpha != r on both adapters of to_q
     A0, B0 = fuse_adapters(sites, widths, torch.bfloat16, "cpu")
+    # the builder in its merge form (HipModule._merge_into): ONE projection, explicit (A, B, scale) blocks - ranks 4 and 8, alpha / r = 2 and 1.5
+    q = sites[0]
+    assert {a: (q.r[a], q.scaling[a]) for a in q.live_adapters()} == {"canny": (8, 2.0), "depth": (4, 1.5)}
+    blocks = [(q.lora_A[a].weight, q.lora_B[a].weight, q.scaling[a]) for a in q.live_adapters()]
+    Aq, Bq = fuse_adapters([q], [256], torch.bfloat16, "cpu")
+    Am, Bm = adapter_operands([blocks], [256], torch.bfloat16, "cpu")
+    assert torch.equal(Am, Aq) and torch.equal(Bm, Bq) and Am.shape == (64, 256) and Bm.shape == (256, 64) and Am.is_contiguous() and Bm.is_contiguous()
+    assert torch.equal(Am[:12], A0[:12]) and torch.equal(Bm[:, :12], B0[:256, :12]) and not Am[12:].any() and not Bm[:, 12:].any()   # = to_q's block of the three-way launch
     m.set_lora_trainable()
     A1, B1, has = fuse_adapters_autograd(sites, widths, torch.bfloat16, "cpu")
     assert torch.equal(A0, A1) and torch.equal(B0, B1) and has == (True, True, True, False)
@@ -85,6 +94,14 @@ def test_differentiable_fuse_equals_inference_fuse_and_routes_gradients():
         s.set_scale("canny", 0)
         s.set_scale("depth", 0)
     assert fuse_adapters_autograd(sites, widths, torch.bfloat16, "cpu") is None
+    for s in sites[:3]:
+        s.unscale_layer(None)                                       # back to alpha / r: live again
+    assert fuse_adapters(sites, widths, torch.bfloat16, "cpu")[0] is not None
+    # every adapter switched off by enable_lora: no operands in any of the three forms
+    with enable_lora(list(m.modules()), []):
+        assert fuse_adapters(sites, widths, torch.bfloat16, "cpu") == (None, None)
+        assert fuse_adapters_autograd(sites, widths, torch.bfloat16, "cpu") is None
+        assert adapter_operands([[(q.lora_A[a].weight, q.lora_B[a].weight, q.scaling[a]) for a in q.live_adapters()]], [256], torch.bfloat16, "cpu") == (None, None)
 
 
 def test_header_and_exports_agree_with_the_new_symbols():

@@ -267,7 +267,7 @@ def linear_n(x: torch.Tensor, ws, bs):
 class LoRALinearN(torch.autograd.Function):
     """LinearN (n >= 1 projections of the same rows x) with live LoRA adapters:  y_i = x w_i^T + b_i + T B_bd[rows of i]^T,  T = bf16(x A_cat^T).
     `a_cat` [Rp, K] / `b_bd` [sum N_i, Rp] are the fused operands of lora.fuse_adapters_autograd (differentiable: torch.autograd carries their
-    gradients on to every adapter's own lora_A / lora_B). The forward is the inference engine's (engine._lora_operands + the K-segment launch): the
+    gradients on to every adapter's own lora_A / lora_B). The forward is the inference engine's (HipModule._lora_gemm: T, then the K-segment launch): the
     same two launches, the same rounding points. `has` [n]: whether projection i carries a live adapter (its rows of b_bd are non-zero).
     Backward: dT = sum_i dy_i B_bd[rows of i] (the projections' rank columns are disjoint, so accumulating through the GEMM's residual epilogue adds
     exact zeros); dx = sum_i dy_i w_i + dT A_cat, the adapter term as the K-segment of the first launch; dA_cat = dT^T x and dB_bd[rows of i] =

@@ -1,6 +1,8 @@
 """Shared host-side machinery of the HIP engines (UniGenFlux, UniGenSD3): parameter containers under the reference's state-dict
 names, weight packing into fused buffers (parameters become views), a workspace cache, token-stream descriptors and the
-block routines that orchestrate calls through the C ABI (unigen_amd/ops.py). No arithmetic happens in torch here."""
+block routines that orchestrate calls through the C ABI (unigen_amd/ops.py). No arithmetic happens in torch here.
+LoRA adapters are managed by lora.LoRAHost, which HipModule inherits: the block routines launch every adapter-capable projection through its
+`_lora_gemm`, and `_weights_rewritten` is what the packing code offers it in return."""
 from __future__ import annotations
 
 import math
@@ -11,30 +13,10 @@ from torch import nn
 
 from . import lib as L
 from . import ops
-from .lora import LoRALayer, fuse_adapters
+from .lora import LoRAHost, _Holder         # _Holder: re-exported, flux.py and vae.py import it from here
 from .ops import RowMap
 
 BF = torch.bfloat16
-
-
-class _Holder(nn.Module):
-    """Parameter container; the arithmetic lives in libunigen_hip.so, so calling it is an error."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise L.UniGenHipError("parameter holder: unigen_amd modules are executed by the HIP engine, not called directly")
-
-
-class _LoRAHolder(_Holder, LoRALayer):
-    """The holder of a projection that carries LoRA adapters (HipModule.add_lora): the same `weight` / `bias` parameters plus
-    `lora_A.<adapter>.weight`, `lora_B.<adapter>.weight` and the PEFT layer attributes `enable_lora` reads."""
-
-    def __init__(self, plain: _Holder):
-        super().__init__()
-        for n, p_ in plain._parameters.items():         # the SAME Parameter objects: packed views, state-dict keys and optimiser references survive
-            self.register_parameter(n, p_)
-        for n, m in plain._modules.items():
-            self.add_module(n, m)
-        self._init_lora()
 
 
 def _register(root: nn.Module, name: str, shape: Tuple[int, ...], device, dtype) -> nn.Parameter:
@@ -125,8 +107,9 @@ class _Routing:
         self.weights, self.exp_counts, self.l_aux = weights, exp_counts, l_aux
 
 
-class HipModule(nn.Module):
-    """Base of the drop-in transformer classes: holds parameters, never computes in torch."""
+class HipModule(LoRAHost, nn.Module):
+    """Base of the drop-in transformer classes: holds parameters, never computes in torch. LoRA adapters - their state, `add_lora` ... `fuse_lora`
+    and `_lora_gemm`, the launch of a projection together with its live adapters - come from lora.LoRAHost."""
 
     inner_dim: int
     _heads: int
@@ -138,11 +121,6 @@ class HipModule(nn.Module):
         self._packed: Dict[str, torch.Tensor] = {}
         self._emb_tab: Dict[str, torch.Tensor] = {}       # AdaLN linear outputs of the current step, by module prefix (_adaln_group)
         self.trainable_control_modules: Dict[str, nn.Module] = {}
-        self._lora_sites: Dict[str, _LoRAHolder] = {}     # projection prefix -> its adapter-carrying holder (add_lora)
-        self._lora_fused: Dict[Tuple, Tuple] = {}         # fused adapter operands per launch (prefixes + adapter state), see _lora_operands
-        self._lora_merge_only: Dict[str, Dict[str, Tuple]] = {}   # adapter -> {module: (A, B, alpha)} outside LORA_CAPABLE (load_lora_weights): run only merged
-        self._lora_merged: Dict[str, float] = {}          # adapter -> lora_scale of the adapters fuse_lora merged into the base weights
-        self._lora_backup: Optional[Dict[str, torch.Tensor]] = None   # parameter name -> its bytes before the first fuse_lora (None: nothing fused / no backup)
 
     def _check_dtype(self, *inputs: torch.Tensor):
         """bf16 = the product path; fp32 = the verification path (every C-ABI call goes to its `_f32` twin, unigen_amd/ops.py).
@@ -165,6 +143,17 @@ class HipModule(nn.Module):
     @property
     def device(self):
         return self._probe().device
+
+    def forward(self, *args, **kwargs):
+        """Inference (no autograd: the subclass's in-place HIP engine, `_forward_inference`) or, when autograd is on and some parameter requires a gradient -
+        the reference's train.py:622-662 after `init_trainable_param()` - the differentiable forward of unigen_amd/training.py. Same arguments, same 3-tuple."""
+        self._lora_guard()          # an adapter with merge-only entries (load_lora_weights) runs only after fuse_lora
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            from . import training
+            with self._lora_scaled(kwargs.get("joint_attention_kwargs")):
+                return getattr(training, self._training_forward)(self, *args, **kwargs)      # named by the subclass: "flux_forward" / "sd3_forward"
+        with torch.no_grad(), self._lora_scaled(kwargs.get("joint_attention_kwargs")):
+            return self._forward_inference(*args, **kwargs)
 
     def init_trainable_param(self):
         for module in self.trainable_control_modules.values():
@@ -200,372 +189,6 @@ class HipModule(nn.Module):
                     p.copy_(torch.randn(p.shape, generator=g, device=p.device, dtype=torch.float32) * std)
         return self
 
-    # ------------------------------------------------------------------ LoRA (A12) -------------------------------------
-    # The projections whose GEMM launches take the adapter K-segment (every attention / feed-forward projection of a joint or single block, in
-    # the base, control, shared-expert and consistency blocks alike). PEFT matches `target_modules` by module-name suffix; a suffix that hits a
-    # parameter the engine runs another way (AdaLN linears, embedders, experts, zero-res projections) is refused rather than silently ignored.
-    LORA_CAPABLE = ("attn.to_q", "attn.to_k", "attn.to_v", "attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj", "attn.to_out.0", "attn.to_add_out",
-                    "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0", "ff.net.0.proj", "ff.net.2", "ff_context.net.0.proj", "ff_context.net.2",
-                    "proj_mlp", "proj_out")
-
-    def add_lora(self, target_suffixes: Sequence[str], adapter_name: str, r: int, lora_alpha: float, A=None, B=None, prefix: str = "",
-                 init_lora_weights: bool = True, seed: int = 0) -> Sequence[str]:
-        """Attach the LoRA adapter `adapter_name` (rank r, scaling lora_alpha / r) to every projection whose module name ends with one of
-        `target_suffixes` (PEFT's `target_modules` rule: name == key or name.endswith("." + key)) and starts with `prefix` (e.g.
-        "control_joint_trans_blocks." for the per-condition adapters of the control branch). The projection's holder becomes a PEFT-shaped layer
-        (`lora_A`, `lora_B`, `scaling`, `active_adapters`, `set_scale`) that `enable_lora(list(model.modules()), [...])`
-        (src/lora_switching_module.py:11-38) switches; the engines' GEMM launches for that weight take the live adapters as a K-segment of the base
-        product (`ug_gemm_desc.lora_T / lora_B`). A / B: None (PEFT's initial values: A uniform, B zero - or B random too with
-        init_lora_weights=False, PEFT's testing mode), or {module name: tensor}. Returns the module names that received the adapter.
-        No adapter attached -> nothing changes anywhere (bit-identical outputs, same launches)."""
-        hits = []
-        for name, mod in list(self.named_modules()):
-            if not name.startswith(prefix) or not any(name == t or name.endswith("." + t) for t in target_suffixes):
-                continue
-            w = mod._parameters.get("weight")
-            if w is None or w.dim() != 2:
-                continue
-            if not any(name == c or name.endswith("." + c) for c in self.LORA_CAPABLE) or name == "proj_out" or ".experts." in name:
-                raise L.UniGenHipError(f"add_lora: {name} is not a projection the HIP engine can extend with an adapter K-segment "
-                                       f"(supported suffixes: {', '.join(self.LORA_CAPABLE)} inside transformer blocks)")
-            hits.append(name)
-        if not hits:
-            raise ValueError(f"add_lora: no module under prefix {prefix!r} matches {list(target_suffixes)}")
-        g = torch.Generator().manual_seed(seed)
-        for name in hits:
-            parent_name, _, leaf = name.rpartition(".")
-            parent = self.get_submodule(parent_name) if parent_name else self
-            mod = parent._modules[leaf]
-            if not isinstance(mod, _LoRAHolder):
-                mod = _LoRAHolder(mod)
-                parent._modules[leaf] = mod
-                self._lora_sites[name] = mod
-            a = A.get(name) if isinstance(A, dict) else A
-            b = B.get(name) if isinstance(B, dict) else B
-            if b is None and not init_lora_weights:
-                b = torch.randn(mod.weight.shape[0], r, generator=g) * 0.02
-            mod.add_adapter(adapter_name, r, lora_alpha, A=a, B=b, generator=g)
-        self._pname_cache = None
-        self._lora_fused.clear()
-        return hits
-
-    def _lora_scaled(self, joint_attention_kwargs):
-        """`scale_lora_layers(self, lora_scale)` ... `unscale_lora_layers(self, lora_scale)` around a forward (src/UniGenTransformer.py:1200-1208,
-        1266-1269; diffusers 0.32.2 utils/peft_utils.py): `joint_attention_kwargs["scale"]` multiplies every adapter's scaling for the duration of
-        the forward; 1.0 (or no adapter-carrying projection) is a no-op, 0 is undone by `set_scale(adapter, 1.0)`."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def cm():
-            w = (joint_attention_kwargs or {}).get("scale", 1.0)
-            on = bool(self._lora_sites) and w is not None and w != 1.0
-            if on:
-                for m in self._lora_sites.values():
-                    m.scale_layer(w)
-            try:
-                yield
-            finally:
-                if on:
-                    for m in self._lora_sites.values():
-                        if w != 0:
-                            m.unscale_layer(w)
-                        else:
-                            for a in m.active_adapters:
-                                m.set_scale(a, 1.0)
-        return cm()
-
-    def set_lora_trainable(self, adapters: Optional[Sequence[str]] = None, freeze_rest: bool = True) -> Sequence[str]:
-        """Make the `lora_A` / `lora_B` weights of the named adapters (None: every adapter) trainable - the reference's `transformer_lora_parameters`
-        (train.py:349). With `freeze_rest` every other parameter is frozen (the base, the control modules, the adapters not named); those adapters
-        still take part in the forward while live. The differentiable forward (unigen_amd/training.py) then runs the LoRA-carrying linears of
-        unigen_amd/autograd.py. Returns the names of the trainable parameters."""
-        known = {a for m in self._lora_sites.values() for a in m.lora_A}
-        want = known if adapters is None else set(adapters)
-        if not want or want - known:
-            raise ValueError(f"set_lora_trainable: unknown adapters {sorted(want - known)} (attached: {sorted(known)})" if want else
-                             "set_lora_trainable: no adapter is attached (add_lora)")
-        if freeze_rest:
-            self.requires_grad_(False)
-        for m in self._lora_sites.values():
-            for a in want & set(m.lora_A):
-                m.lora_A[a].weight.requires_grad_(True)
-                m.lora_B[a].weight.requires_grad_(True)
-        return [n for n, p_ in self.named_parameters() if p_.requires_grad]
-
-    def lora_state_dict(self, adapter: str) -> Dict[str, torch.Tensor]:
-        """What PEFT's `get_peft_model_state_dict(model, adapter_name=adapter)` returns and the reference's save hook writes (src/hook.py:29-46):
-        `<proj>.lora_A.weight` / `<proj>.lora_B.weight` - the adapter name dropped - for every projection that carries the adapter."""
-        sd = {}
-        for name, m in self._lora_sites.items():
-            if adapter in m.lora_A:
-                sd[f"{name}.lora_A.weight"] = m.lora_A[adapter].weight.detach().clone()
-                sd[f"{name}.lora_B.weight"] = m.lora_B[adapter].weight.detach().clone()
-        if not sd:
-            raise KeyError(f"lora_state_dict: no projection carries an adapter named {adapter!r}")
-        return sd
-
-    def load_lora_state_dict(self, state_dict: Dict[str, torch.Tensor], adapter: str) -> Sequence[str]:
-        """Load the weights of `adapter` (already attached with add_lora: rank and alpha are not part of a state dict). Accepted key forms:
-        `<proj>.lora_A.weight` (lora_state_dict / PEFT), the same under a `transformer.` prefix (what `FluxPipeline.lora_state_dict` hands to the
-        reference's load hook, src/hook.py:49-70) and the in-model `<proj>.lora_A.<adapter>.weight` (the base weights of a PEFT-wrapped
-        checkpoint sit under `<proj>.base_layer.`: INTEGRATION.md). Every projection that carries the adapter must be covered, every key must be used. Returns the loaded keys."""
-        want = {f"{n}.lora_{s}": getattr(m, f"lora_{s}")[adapter].weight for n, m in self._lora_sites.items() if adapter in m.lora_A for s in "AB"}
-        if not want:
-            raise KeyError(f"load_lora_state_dict: no projection carries an adapter named {adapter!r}")
-        used = []
-        with torch.no_grad():
-            for key, val in state_dict.items():
-                k = key[len("transformer."):] if key.startswith("transformer.") else key
-                if not k.endswith(".weight"):
-                    raise KeyError(f"load_lora_state_dict: unexpected key {key!r}")
-                k = k[:-len(".weight")]
-                if k.endswith("." + adapter):
-                    k = k[:-len(adapter) - 1]
-                dst = want.get(k)
-                if dst is None or k in used:
-                    raise KeyError(f"load_lora_state_dict: {key!r} does not name a lora_A / lora_B weight of adapter {adapter!r}")
-                if tuple(val.shape) != tuple(dst.shape):
-                    raise ValueError(f"load_lora_state_dict: {key!r} is {tuple(val.shape)}, the adapter's weight is {tuple(dst.shape)}")
-                dst.copy_(val.to(dst.device, dst.dtype))
-                used.append(k)
-        if set(used) != set(want):
-            raise KeyError(f"load_lora_state_dict: missing {sorted(set(want) - set(used))[:4]} ...")
-        return used
-
-    # ------------------------------------------------------------------ LoRA files and the merge into the base weights ---------------
-    @classmethod
-    def lora_capable(cls, name: str) -> bool:
-        """Does the module `name` take a live adapter (the rule add_lora enforces)? Everything else can only be merged (fuse_lora)."""
-        return any(name == c or name.endswith("." + c) for c in cls.LORA_CAPABLE) and name != "proj_out" and ".experts." not in name
-
-    def load_lora_weights(self, src, adapter_name: str = "default", strict: bool = True):
-        """Read a LoRA file (`src`: a path - unigen_amd/lora_io.py `read_lora_file` - or a state dict in the diffusers / PEFT, kohya or BFL naming),
-        infer rank and alpha per module, and attach it as `adapter_name`: the modules in LORA_CAPABLE through `add_lora(..., A=, B=)` - live, switched by
-        `enable_lora` as before - the others (AdaLN linears, embedders, experts, proj_out ...) as merge-only entries that reach the output only through
-        `fuse_lora()`; until then the forward refuses to run (a partly applied adapter is never computed). Tensors are cast to the model's dtype.
-        Module names the model does not have raise under `strict`. Returns lora_io.LoraReport(live, merge_only, ignored)."""
-        from . import lora_io
-        sd = src if isinstance(src, dict) else lora_io.read_lora_file(src)
-        entries, report = lora_io.convert(sd, self, strict=strict)
-        if not entries:
-            raise ValueError("load_lora_weights: the file holds no adapter weight for this model")
-        taken = set(self._lora_merge_only.get(adapter_name, ())) | {n for n, m in self._lora_sites.items() if adapter_name in m.lora_A}
-        if taken & set(entries):
-            raise L.UniGenHipError(f"load_lora_weights: adapter {adapter_name!r} already covers {sorted(taken & set(entries))[:4]} ...; unload_lora_weights first")
-        if adapter_name in self._lora_merged:
-            raise L.UniGenHipError(f"load_lora_weights: adapter {adapter_name!r} is fused into the weights; unfuse_lora first")
-        groups: Dict[Tuple[int, float], list] = {}
-        for name in report.live:
-            A, B, alpha = entries[name]
-            groups.setdefault((A.shape[0], float(alpha if alpha is not None else A.shape[0])), []).append(name)
-        # add_lora matches its targets by PEFT's suffix rule: a full module name must not ALSO be the tail of a deeper module's name
-        modules = dict(self.named_modules())
-        for name in report.live:
-            extra = [n for n in modules if n.endswith("." + name) and modules[n]._parameters.get("weight") is not None]
-            if extra:
-                raise L.UniGenHipError(f"load_lora_weights: {name!r} is also the suffix of {extra[:2]}; the file's entry cannot be attached to one module alone")
-        try:
-            for (r, alpha), names in groups.items():
-                hits = self.add_lora(names, adapter_name, r, alpha, A={n: entries[n][0] for n in names}, B={n: entries[n][1] for n in names})
-                if set(hits) != set(names):
-                    raise L.UniGenHipError(f"load_lora_weights: add_lora attached {sorted(set(hits) ^ set(names))[:4]} beyond / short of the file's modules")
-        except Exception:
-            self._drop_live_adapter(adapter_name, only=set(report.live))      # nothing of a file that failed part-way stays attached
-            raise
-        dev, dt = self.device, self.dtype
-        for name in report.merge_only:
-            A, B, alpha = entries[name]
-            self._lora_merge_only.setdefault(adapter_name, {})[name] = (A.detach().to(dev, dt).contiguous(), B.detach().to(dev, dt).contiguous(),
-                                                                        float(alpha if alpha is not None else A.shape[0]))
-        return report
-
-    def _lora_guard(self) -> None:
-        """Refuse a forward while an adapter has merge-only entries that are not merged: only part of it would be applied."""
-        if self._lora_merge_only:
-            pending = [a for a in self._lora_merge_only if a not in self._lora_merged]
-            if pending:
-                raise L.UniGenHipError(f"adapter(s) {pending} carry weights for modules outside LORA_CAPABLE (e.g. {next(iter(self._lora_merge_only[pending[0]]))}) that only run "
-                                       "merged into the base weights: call fuse_lora() before the forward (or unload_lora_weights)")
-
-    def _weights_rewritten(self, params) -> None:
-        """Base weights were overwritten through raw pointers (the merge GEMM) - `_version` did not move - or restored: drop everything derived from
-        them: the backward's transposed copies of frozen weights (autograd._wt_cache) and the fused adapter operands (self._lora_fused)."""
-        if params:
-            torch.autograd.graph.increment_version(list(params))
-        self._storage_moved()
-        self._lora_fused.clear()
-
-    @staticmethod
-    def _merge_into(w: torch.Tensor, blocks) -> None:
-        """w [N_out, K_in] (a view inside its pack) <- dtype(w + Bs A_cat), Bs = dtype(scaling_a * B_a), in place, every adapter of this weight as one
-        concatenated rank - w is rounded ONCE. Two existing launches: P = Bs A_cat through ug_gemm with the fp32 epilogue (UG_EPI_F32: the accumulators
-        as they are), then w = dtype(w + P) through ug_add_rowbcast_f32. (One UG_EPI_RES_SCALE launch with the residual aliased to the output also
-        merges in place, but that epilogue rounds the product to bf16 before it adds the residual; the second rounding moved a fused bf16 forward
-        from 0.0089 to 0.0143 off the fp32 oracle: profiles/lora_merge_rounding.log, DESIGN.md section 7a addendum.) A weight the kernels' alignment rules refuse is staged through a
-        padded temporary."""
-        from .lora import _RANK_PAD
-        N, K = w.shape
-        R = sum(a.shape[0] for a, _, _ in blocks)
-        Rp = (R + _RANK_PAD - 1) // _RANK_PAD * _RANK_PAD
-        A_cat = torch.zeros(Rp, K, device=w.device, dtype=w.dtype)
-        Bs = torch.zeros(N, Rp, device=w.device, dtype=w.dtype)
-        c0 = 0
-        for a, b, sc in blocks:
-            r = a.shape[0]
-            A_cat[c0:c0 + r] = a
-            Bs[:, c0:c0 + r] = (b.float() * sc).to(w.dtype)
-            c0 += r
-        direct = K % 8 == 0 and w.stride(1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0
-        Kp = K if direct else (K + 63) // 64 * 64
-        dst = w if direct else torch.zeros(N, Kp, device=w.device, dtype=w.dtype)
-        if not direct:
-            dst[:, :K].copy_(w)
-            A_cat = torch.nn.functional.pad(A_cat, (0, Kp - K))
-        At = ops.transpose(A_cat)                                            # [K_in, Rp]: the GEMM's W operand, nn.Linear layout over the rank
-        P = torch.empty(N, Kp, device=w.device, dtype=torch.float32)
-        ops.gemm(Bs, At, None, P, M=N, epilogue=L.EPI_F32)
-        ops.add_rowbcast_f32(dst, P, N)
-        if not direct:
-            w.copy_(dst[:, :K])
-
-    @torch.no_grad()
-    def fuse_lora(self, adapter_names: Optional[Sequence[str]] = None, lora_scale: float = 1.0, backup: Optional[str] = "device") -> Sequence[str]:
-        """Merge the named adapters (None: every adapter that is not merged yet) into the base weights, live sites and merge-only entries alike:
-        W <- dtype(W + sum_a dtype(scaling_a * lora_scale * B_a) A_a), rounded once, in place: one GEMM launch + one add per weight (`_merge_into`; fp32
-        models take the fp32 twins).
-        Live sites use their CURRENT scaling. A merged adapter stops contributing at run time whatever `enable_lora` or `joint_attention_kwargs["scale"]`
-        say: `live_adapters()` skips it, so the forward's launches are those of the adapter-free model.
-        backup: "device" / "host" keep the original bytes of every touched parameter (about 24 GB for an all-linear FLUX adapter) for `unfuse_lora`;
-        None keeps none. Merging an adapter twice is an error. Returns the names of the touched parameters."""
-        if backup not in ("device", "host", None):
-            raise ValueError(f"fuse_lora: backup must be 'device', 'host' or None, got {backup!r}")
-        known = set(self._lora_merge_only) | {a for m in self._lora_sites.values() for a in m.lora_A}
-        names = [a for a in sorted(known) if a not in self._lora_merged] if adapter_names is None else \
-            [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
-        for a in names:
-            if a in self._lora_merged:
-                raise L.UniGenHipError(f"fuse_lora: adapter {a!r} is already fused into the weights")
-            if a not in known:
-                raise KeyError(f"fuse_lora: no adapter named {a!r} (attached: {sorted(known)})")
-        if not names:
-            raise L.UniGenHipError("fuse_lora: no adapter to fuse")
-        if self._lora_merged and (backup is None) != (self._lora_backup is None):
-            raise L.UniGenHipError("fuse_lora: adapters are already fused with another backup mode; unfuse_lora first")
-        per_weight: Dict[str, list] = {}
-        for a in names:
-            for mod, site in self._lora_sites.items():
-                if a in site.lora_A and site.scaling[a] * lora_scale != 0.0:
-                    per_weight.setdefault(mod, []).append((site.lora_A[a].weight.data, site.lora_B[a].weight.data, site.scaling[a] * lora_scale))
-            for mod, (A, B, alpha) in self._lora_merge_only.get(a, {}).items():
-                if lora_scale != 0.0:
-                    per_weight.setdefault(mod, []).append((A, B, alpha / A.shape[0] * lora_scale))
-        if backup is not None and self._lora_backup is None:
-            self._lora_backup = {}
-        touched = []
-        for mod, blocks in per_weight.items():
-            p = self.get_parameter(mod + ".weight")
-            if backup is not None and mod + ".weight" not in self._lora_backup:
-                self._lora_backup[mod + ".weight"] = p.data.detach().clone() if backup == "device" else p.data.detach().cpu()
-            self._merge_into(p.data, blocks)
-            touched.append(p)
-        for a in names:
-            self._lora_merged[a] = float(lora_scale)
-            for site in self._lora_sites.values():
-                if a in site.lora_A:
-                    site.fused_adapters.add(a)
-        self._weights_rewritten(touched)
-        return [m + ".weight" for m in per_weight]
-
-    @torch.no_grad()
-    def unfuse_lora(self) -> None:
-        """Undo every fuse_lora: copy the backed-up bytes back - bit for bit - and let the merged live adapters contribute again. Without a backup
-        (`fuse_lora(backup=None)`) this raises: subtracting the product again in bf16 is NOT an inverse of the merge (W was rounded after the
-        addition), so there is nothing exact to restore."""
-        if not self._lora_merged:
-            raise L.UniGenHipError("unfuse_lora: no adapter is fused")
-        if self._lora_backup is None:
-            raise L.UniGenHipError("unfuse_lora: fuse_lora(backup=None) kept no copy of the original weights, and subtracting the adapters in bf16 does not "
-                                   "restore them; reload the base weights instead")
-        touched = []
-        for name, saved in self._lora_backup.items():
-            p = self.get_parameter(name)
-            p.data.copy_(saved)
-            touched.append(p)
-        self._lora_backup = None
-        for site in self._lora_sites.values():
-            site.fused_adapters.difference_update(self._lora_merged)
-        self._lora_merged.clear()
-        self._weights_rewritten(touched)
-
-    def unload_lora_weights(self, adapter_name: str) -> None:
-        """Remove the adapter: unfuse first if it is merged (every merged adapter is unfused - the backup holds the weights before all of them), then
-        drop its live layers (a holder left without adapters becomes a plain one again) and its merge-only entries."""
-        known = set(self._lora_merge_only) | {a for m in self._lora_sites.values() for a in m.lora_A}
-        if adapter_name not in known:
-            raise KeyError(f"unload_lora_weights: no adapter named {adapter_name!r} (attached: {sorted(known)})")
-        if adapter_name in self._lora_merged:
-            self.unfuse_lora()
-        self._lora_merge_only.pop(adapter_name, None)
-        self._drop_live_adapter(adapter_name)
-
-    def _drop_live_adapter(self, adapter_name: str, only=None) -> None:
-        """Remove the adapter's live layers (from the sites named in `only`, or everywhere); a holder left without adapters becomes a plain one again."""
-        for name, site in list(self._lora_sites.items()):
-            if adapter_name not in site.lora_A or (only is not None and name not in only):
-                continue
-            del site.lora_A[adapter_name], site.lora_B[adapter_name]
-            for d in (site.r, site.lora_alpha, site.scaling):
-                d.pop(adapter_name, None)
-            if adapter_name in site.active_adapters:
-                site.active_adapters.remove(adapter_name)
-            site.fused_adapters.discard(adapter_name)
-            if not site.lora_A:
-                plain = _Holder()
-                for n, p_ in site._parameters.items():
-                    plain.register_parameter(n, p_)
-                for n, m in site._modules.items():
-                    if n not in ("lora_A", "lora_B"):
-                        plain.add_module(n, m)
-                parent_name, _, leaf = name.rpartition(".")
-                (self.get_submodule(parent_name) if parent_name else self)._modules[leaf] = plain
-                del self._lora_sites[name]
-        self._pname_cache = None
-        self._lora_fused.clear()
-
-    # No longer called by the forwards - the differentiable forward carries live adapters (training._lora) - but kept as it was: its behaviour is
-    # pinned by the host tests.
-    def _refuse_lora_in_training(self):
-        if self._lora_sites and any(m.live_adapters() for m in self._lora_sites.values()):
-            raise NotImplementedError("the differentiable forward (unigen_amd/training.py) does not carry LoRA adapters: run under torch.no_grad(), "
-                                      "or disable them (enable_lora(modules, []))")
-
-    def _lora_live(self, prefixes: Sequence[str]) -> bool:
-        """Does any projection of this launch carry an adapter that contributes right now?"""
-        if not self._lora_sites:
-            return False
-        return any(p in self._lora_sites and self._lora_sites[p].live_adapters() for p in prefixes)
-
-    def _lora_operands(self, prefixes: Sequence[str], a: torch.Tensor, M: int, tag: str, lda: Optional[int] = None, a_map: RowMap = ops.IDENT):
-        """(T, B) for ONE launch over the row-concatenated weights of `prefixes` (the fused q|k|v[|proj_mlp] launch, or a single projection):
-        T = a A_cat^T [M, R] - ONE GEMM for all live adapters of all projections of the launch - and the block-diagonal, scaling-folded B [N, R]
-        (lora.fuse_adapters). (None, None) when no adapter is live: the caller's launch is then exactly the adapter-free one."""
-        if not self._lora_live(prefixes):
-            return None, None
-        sites = [self._lora_sites.get(p) for p in prefixes]
-        state = tuple((p, tuple((n, s.scaling[n], s.lora_A[n].weight._version, s.lora_B[n].weight._version, s.lora_A[n].weight.data_ptr(),
-                                 s.lora_B[n].weight.data_ptr())
-                                for n in s.live_adapters())) for p, s in zip(prefixes, sites) if s is not None)
-        key = (tuple(prefixes), self.dtype)
-        hit = self._lora_fused.get(key)
-        if hit is None or hit[0] != state:
-            widths = [self.get_parameter(p + ".weight").shape[0] for p in prefixes]
-            hit = (state,) + fuse_adapters(sites, widths, self.dtype, self.device)
-            self._lora_fused[key] = hit
-        A_cat, B_bd = hit[1], hit[2]
-        t = self._w("lora_t_" + tag, (M, A_cat.shape[0]))
-        ops.gemm(a, A_cat, None, t, M=M, lda=lda, a_map=a_map)
-        return t, B_bd
-
     # ------------------------------------------------------------------ weight packing --------------------------------
     @staticmethod
     def _storage_moved():
@@ -573,10 +196,18 @@ class HipModule(nn.Module):
         from . import autograd
         autograd.clear_caches()
 
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)          # .to() / .cuda() / .float(): every parameter gets new storage
+    def _weights_rewritten(self, params=()) -> None:
+        """Base weights were overwritten through raw pointers (the merge GEMM of lora.LoRAHost) - `_version` did not move - restored, or moved: drop
+        everything derived from them: the backward's transposed copies of frozen weights (autograd._wt_cache) and the fused adapter operands
+        (self._lora_fused)."""
+        if params:
+            torch.autograd.graph.increment_version(list(params))
         self._storage_moved()
         self._lora_fused.clear()
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)          # .to() / .cuda() / .float(): every parameter gets new storage
+        self._weights_rewritten()
         return r
 
     def _P(self, name: str) -> torch.Tensor:
@@ -793,10 +424,11 @@ class HipModule(nn.Module):
         cs = getattr(rope, "cs", None)
         # live LoRA adapters of to_q / to_k / to_v: T = ns A_cat^T in one GEMM, then the K-segment of this launch (the q/k RMSNorm + RoPE then
         # runs as its own kernel: UG_EPI_QKV_ROPE is not LoRA-extended)
-        lt, lb = self._lora_operands([a + ".to_q", a + ".to_k", a + ".to_v"], ns, B * Ls, "s")
-        fused = (lt is None and wq is not None and (cs is not None or (cos is None and dh == 64)) and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, ns.dtype, c_rpb=Ls, rope_rpb=Ls))
-        ops.gemm(ns, w_qkv, b_qkv, qkv2[Lc:], M=B * Ls, ldc=3 * D, c_map=RowMap(Ls, Lj),
-                 qk_rope=ops.QkRope(wq, wk, cs, Ls, Lc, 2 * D, dh=dh) if fused else None, lora_t=lt, lora_b=lb)
+        qkv_s = [a + ".to_q", a + ".to_k", a + ".to_v"]
+        fused = (not self._lora_live(qkv_s) and wq is not None and (cs is not None or (cos is None and dh == 64))
+                 and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, ns.dtype, c_rpb=Ls, rope_rpb=Ls))
+        self._lora_gemm(qkv_s, ns, w_qkv, b_qkv, qkv2[Lc:], "s", M=B * Ls, ldc=3 * D, c_map=RowMap(Ls, Lj),
+                        qk_rope=ops.QkRope(wq, wk, cs, Ls, Lc, 2 * D, dh=dh) if fused else None)
         # context stream
         emb_c = None
         if c_out is not None or not ctx_cached:
@@ -808,11 +440,9 @@ class HipModule(nn.Module):
                 nc = self._modulate(c_in, emb_c, 0, 1, B, "c")
             w_a, b_a = self._attn_add_qkv(a)
             if c_out is not None:
-                lt, lb = self._lora_operands([a + ".add_q_proj", a + ".add_k_proj", a + ".add_v_proj"], nc, B * Lc, "c")
-                ops.gemm(nc, w_a, b_a, qkv2, M=B * Lc, ldc=3 * D, c_map=RowMap(Lc, Lj), lora_t=lt, lora_b=lb)
+                self._lora_gemm([a + ".add_q_proj", a + ".add_k_proj", a + ".add_v_proj"], nc, w_a, b_a, qkv2, "c", M=B * Lc, ldc=3 * D, c_map=RowMap(Lc, Lj))
             else:
-                lt, lb = self._lora_operands([a + ".add_k_proj", a + ".add_v_proj"], nc, B * Lc, "c")
-                ops.gemm(nc, w_a[D:], b_a[D:], qkv2[0, D:], M=B * Lc, ldc=3 * D, c_map=RowMap(Lc, Lj), lora_t=lt, lora_b=lb)
+                self._lora_gemm([a + ".add_k_proj", a + ".add_v_proj"], nc, w_a[D:], b_a[D:], qkv2[0, D:], "c", M=B * Lc, ldc=3 * D, c_map=RowMap(Lc, Lj))
         if touch:
             if c_out is not None and not fused:
                 ops.qk_rmsnorm_rope(qkv2, batches=B, rows_per_batch=Lj, ld=3 * D, q_off=0, k_off=D, heads=H, dh=dh, wq_a=waq, wk_a=wak,
@@ -840,36 +470,34 @@ class HipModule(nn.Module):
                            v_strides=st, o_strides=(D, Ls * D))
             att_s, att_map = att, RowMap()
         # sample: x = x + gate_msa * to_out(attn)
-        lt, lb = self._lora_operands([a + ".to_out.0"], att_s, B * Ls, "o", lda=D, a_map=att_map)
-        ops.gemm(att_s, self._P(a + ".to_out.0.weight"), self._P(a + ".to_out.0.bias"), s_out.base, M=B * Ls, epilogue=L.EPI_RES_GATE, lda=D,
-                 a_map=att_map, ldc=s_out.ld, c_map=s_out.map, residual=s_in.base, ldr=s_in.ld, r_map=s_in.map, gate=emb_s[:, 2 * D:],
-                 gate_ld=emb_s.stride(0), rows_per_sample=Ls, lora_t=lt, lora_b=lb)
+        self._lora_gemm([a + ".to_out.0"], att_s, self._P(a + ".to_out.0.weight"), self._P(a + ".to_out.0.bias"), s_out.base, "o", M=B * Ls,
+                        epilogue=L.EPI_RES_GATE, lda=D, a_map=att_map, ldc=s_out.ld, c_map=s_out.map, residual=s_in.base, ldr=s_in.ld, r_map=s_in.map,
+                        gate=emb_s[:, 2 * D:], gate_ld=emb_s.stride(0), rows_per_sample=Ls)
         if dual:
             # x = x + gate_msa2 * attn2(LN(x_in) * (1 + scale_msa2) + shift_msa2): self-attention over the sample tokens only
             a2 = p + ".attn2"
             q2 = self._w("qkv2_" + tag, (B * Ls, 3 * D))
             w2, b2 = self._attn_qkv(a2)
             w2q, w2k = opt(a2 + ".norm_q.weight"), opt(a2 + ".norm_k.weight")
-            lt, lb = self._lora_operands([a2 + ".to_q", a2 + ".to_k", a2 + ".to_v"], n2, B * Ls, "s")
-            fused2 = lt is None and w2q is not None and dh == 64 and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, n2.dtype, c_rpb=0, rope_rpb=Ls)     # attn2 has no RoPE
-            ops.gemm(n2, w2, b2, q2, M=B * Ls, qk_rope=ops.QkRope(w2q, w2k, None, Ls, 0, 2 * D, dh=dh) if fused2 else None, lora_t=lt, lora_b=lb)
+            qkv_2 = [a2 + ".to_q", a2 + ".to_k", a2 + ".to_v"]
+            fused2 = (not self._lora_live(qkv_2) and w2q is not None and dh == 64
+                      and ops.qk_rope_fusable(B * Ls, 3 * D, 2 * D, dh, n2.dtype, c_rpb=0, rope_rpb=Ls))     # attn2 has no RoPE
+            self._lora_gemm(qkv_2, n2, w2, b2, q2, "s", M=B * Ls, qk_rope=ops.QkRope(w2q, w2k, None, Ls, 0, 2 * D, dh=dh) if fused2 else None)
             if w2q is not None and not fused2:
                 ops.qk_rmsnorm_rope(q2, batches=B, rows_per_batch=Ls, ld=3 * D, q_off=0, k_off=D, heads=H, dh=dh, wq_b=w2q, wk_b=w2k, split=0)
             att2 = self._w("att2_" + tag, (B * Ls, D))
             st2 = (3 * D, Ls * 3 * D)
             ops.flash_attn(q2, q2[0, D:], q2[0, 2 * D:], att2, batches=B, heads=H, dh=dh, Lq=Ls, Lkv=Ls, q_strides=st2, k_strides=st2,
                            v_strides=st2, o_strides=(D, Ls * D))
-            lt, lb = self._lora_operands([a2 + ".to_out.0"], att2, B * Ls, "o")
-            ops.gemm(att2, self._P(a2 + ".to_out.0.weight"), self._P(a2 + ".to_out.0.bias"), s_out.base, M=B * Ls, epilogue=L.EPI_RES_GATE,
-                     ldc=s_out.ld, c_map=s_out.map, residual=s_out.base, ldr=s_out.ld, r_map=s_out.map, gate=emb_s[:, 8 * D:],
-                     gate_ld=emb_s.stride(0), rows_per_sample=Ls, lora_t=lt, lora_b=lb)
+            self._lora_gemm([a2 + ".to_out.0"], att2, self._P(a2 + ".to_out.0.weight"), self._P(a2 + ".to_out.0.bias"), s_out.base, "o", M=B * Ls,
+                            epilogue=L.EPI_RES_GATE, ldc=s_out.ld, c_map=s_out.map, residual=s_out.base, ldr=s_out.ld, r_map=s_out.map,
+                            gate=emb_s[:, 8 * D:], gate_ld=emb_s.stride(0), rows_per_sample=Ls)
         # x = x + gate_mlp * ff(norm2(x) * (1 + scale_mlp) + shift_mlp)
         self._ff(p + ".ff", B, s_out, emb_s, "s")
         if c_out is not None:
-            lt, lb = self._lora_operands([a + ".to_add_out"], att, B * Lc, "o", lda=D, a_map=RowMap(Lc, Lj))
-            ops.gemm(att, self._P(a + ".to_add_out.weight"), self._P(a + ".to_add_out.bias"), c_out.base, M=B * Lc, epilogue=L.EPI_RES_GATE, lda=D,
-                     a_map=RowMap(Lc, Lj), ldc=c_out.ld, c_map=c_out.map, residual=c_in.base, ldr=c_in.ld, r_map=c_in.map, gate=emb_c[:, 2 * D:],
-                     gate_ld=emb_c.stride(0), rows_per_sample=Lc, lora_t=lt, lora_b=lb)
+            self._lora_gemm([a + ".to_add_out"], att, self._P(a + ".to_add_out.weight"), self._P(a + ".to_add_out.bias"), c_out.base, "o", M=B * Lc,
+                            epilogue=L.EPI_RES_GATE, lda=D, a_map=RowMap(Lc, Lj), ldc=c_out.ld, c_map=c_out.map, residual=c_in.base, ldr=c_in.ld,
+                            r_map=c_in.map, gate=emb_c[:, 2 * D:], gate_ld=emb_c.stride(0), rows_per_sample=Lc)
             self._ff(p + ".ff_context", B, c_out, emb_c, "c")
 
     def _pnames(self):
@@ -883,9 +511,7 @@ class HipModule(nn.Module):
         D = self.inner_dim
         n2 = self._modulate(s, emb, 3, 4, B, tag)
         hid = self._w("ffh_" + tag, (B * s.Ls, 4 * D))
-        lt, lb = self._lora_operands([p + ".net.0.proj"], n2, B * s.Ls, "f0")
-        ops.gemm(n2, self._P(p + ".net.0.proj.weight"), self._P(p + ".net.0.proj.bias"), hid, M=B * s.Ls, epilogue=L.EPI_BIAS_GELU, lora_t=lt, lora_b=lb)
-        lt, lb = self._lora_operands([p + ".net.2"], hid, B * s.Ls, "f2")
-        ops.gemm(hid, self._P(p + ".net.2.weight"), self._P(p + ".net.2.bias"), s.base, M=B * s.Ls, epilogue=L.EPI_RES_GATE, ldc=s.ld, c_map=s.map,
-                 residual=s.base, ldr=s.ld, r_map=s.map, gate=emb[:, 5 * D:], gate_ld=emb.stride(0), rows_per_sample=s.Ls, lora_t=lt, lora_b=lb)
+        self._lora_gemm([p + ".net.0.proj"], n2, self._P(p + ".net.0.proj.weight"), self._P(p + ".net.0.proj.bias"), hid, "f0", M=B * s.Ls, epilogue=L.EPI_BIAS_GELU)
+        self._lora_gemm([p + ".net.2"], hid, self._P(p + ".net.2.weight"), self._P(p + ".net.2.bias"), s.base, "f2", M=B * s.Ls, epilogue=L.EPI_RES_GATE,
+                        ldc=s.ld, c_map=s.map, residual=s.base, ldr=s.ld, r_map=s.map, gate=emb[:, 5 * D:], gate_ld=emb.stride(0), rows_per_sample=s.Ls)
 

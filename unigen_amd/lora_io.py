@@ -265,12 +265,7 @@ def save_lora_weights(save_directory, model, adapter: str) -> str:
     adapter's merge-only entries (load_lora_weights) are written too, so that a loaded file round-trips. Returns the file's path."""
     from safetensors.torch import save_file
     out: Dict[str, torch.Tensor] = {}
-    sites = {n: m for n, m in model._lora_sites.items() if adapter in m.lora_A}
-    for name, m in sites.items():
-        out[f"transformer.{name}.lora_A.weight"] = m.lora_A[adapter].weight.detach().cpu().contiguous()
-        out[f"transformer.{name}.lora_B.weight"] = m.lora_B[adapter].weight.detach().cpu().contiguous()
-        out[f"transformer.{name}.alpha"] = torch.tensor(float(m.lora_alpha[adapter]), dtype=torch.float32)
-    for name, (A, B, alpha) in model._lora_merge_only.get(adapter, {}).items():
+    for name, A, B, alpha in model.lora_entries(adapter):
         out[f"transformer.{name}.lora_A.weight"] = A.detach().cpu().contiguous()
         out[f"transformer.{name}.lora_B.weight"] = B.detach().cpu().contiguous()
         out[f"transformer.{name}.alpha"] = torch.tensor(float(alpha), dtype=torch.float32)

@@ -184,7 +184,7 @@ class _LoraLoaderMixin:
     def unload_lora_weights(self, adapter_name: Optional[str] = None):
         """diffusers removes every adapter; `adapter_name` (extra) removes one."""
         tr = self._lora_transformer("unload_lora_weights")
-        names = [adapter_name] if adapter_name is not None else sorted(set(tr._lora_merge_only) | {a for m in tr._lora_sites.values() for a in m.lora_A})
+        names = [adapter_name] if adapter_name is not None else sorted(tr.adapter_names())
         for a in names:
             tr.unload_lora_weights(a)
 

@@ -346,16 +346,7 @@ class UniGenSD3(HipModule):
         return l_aux, exp_counts
 
     # ------------------------------------------------------------------ forward ---------------------------------------
-    def forward(self, *args, **kwargs):
-        """Inference (the in-place HIP engine below, no autograd) or - autograd on and some parameter requiring a gradient, train.py:622-662 after
-        `init_trainable_param()` - the differentiable forward of unigen_amd/training.py. Same arguments, same 3-tuple."""
-        self._lora_guard()          # an adapter with merge-only entries (load_lora_weights) runs only after fuse_lora
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            from . import training
-            with self._lora_scaled(kwargs.get("joint_attention_kwargs")):
-                return training.sd3_forward(self, *args, **kwargs)
-        with torch.no_grad(), self._lora_scaled(kwargs.get("joint_attention_kwargs")):
-            return self._forward_inference(*args, **kwargs)
+    _training_forward = "sd3_forward"        # HipModule.forward: inference runs _forward_inference below, training this function of training.py
 
     def _forward_inference(self, hidden_states: torch.Tensor, condition_hidden_states: torch.Tensor = None, conditioning_scale: float = 1.0,
                 encoder_hidden_states: torch.Tensor = None, pooled_projections: torch.Tensor = None,

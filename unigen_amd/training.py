@@ -25,19 +25,8 @@ def _p(model, name: str) -> Optional[torch.Tensor]:
     return model.get_parameter(name) if name in model._pnames() else None
 
 
-def _lora(model, prefixes):
-    """The fused operands (A_cat, B_bd, has) of the live LoRA adapters of ONE launch over `prefixes` (lora.fuse_adapters_autograd), None when no
-    adapter is live - the launch is then the adapter-free one, as in engine._lora_operands. `enable_lora(...)` and a scaling of 0 act here as they do
-    on inference: such an adapter is not live, takes no launch and gets no gradient."""
-    if not model._lora_live(prefixes):
-        return None
-    from .lora import fuse_adapters_autograd
-    return fuse_adapters_autograd([model._lora_sites.get(p) for p in prefixes], [model.get_parameter(p + ".weight").shape[0] for p in prefixes],
-                                  model.dtype, model.device)
-
-
 def _lin(model, prefix: str, x: torch.Tensor) -> torch.Tensor:
-    lo = _lora(model, [prefix])
+    lo = model._lora_autograd([prefix])
     if lo is not None:
         return A.lora_linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"), lo[0], lo[1])
     return A.linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"))
@@ -45,7 +34,7 @@ def _lin(model, prefix: str, x: torch.Tensor) -> torch.Tensor:
 
 def _lin_n(model, x: torch.Tensor, prefixes):
     ws, bs = [_p(model, p + ".weight") for p in prefixes], [_p(model, p + ".bias") for p in prefixes]
-    lo = _lora(model, prefixes)
+    lo = model._lora_autograd(prefixes)
     if lo is not None:
         return A.lora_linear_n(x, ws, bs, *lo)
     return A.linear_n(x, ws, bs)
@@ -160,7 +149,7 @@ def _single_block_body(model, prefix: str, h, temb, rope):
     mlp = A.GeluTanh.apply(_lin(model, prefix + ".proj_mlp", n))      # its own GEMM: GELU wants a contiguous [M, 4 D] (a view of the fused output would be copied)
     # proj_out(cat[a, mlp]) without the [B, L, 5 D] concatenation: the mlp columns ride as the GEMM's K-segment extension (same bits)
     w_o, b_o = _p(model, prefix + ".proj_out.weight"), _p(model, prefix + ".proj_out.bias")
-    lo = _lora(model, [prefix + ".proj_out"])
+    lo = model._lora_autograd([prefix + ".proj_out"])
     o = A.lora_linear_cat2(a, mlp, w_o, b_o, lo[0], lo[1]) if lo is not None else A.linear_cat2(a, mlp, w_o, b_o)
     return A.gate_residual(h, o, gate)
 
