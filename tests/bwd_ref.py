@@ -1,4 +1,4 @@
-"""CPU float64 references of the training backward kernels (csrc/backward.hip, the attn_bwd_* kernels of csrc/attention.hip, autograd.Linear).
+"""CPU float64 references of the training backward kernels (csrc/backward.hip, the attn_bwd_* kernels of csrc/attention.hip, autograd.Projection / LinearResScale / LinearCat2).
 
 Every function takes the operands exactly as the kernel sees them (bf16 or fp32 values, here widened to float64) and returns the exact result of
 the operation. Where a GPU bound is relative to "the kernel's own rounding points", the same function also returns a second variant (`*_r` keys;

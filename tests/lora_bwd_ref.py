@@ -1,4 +1,4 @@
-"""CPU float64 references of the LoRA adapters' backward (csrc/lora_bwd.hip, autograd.LoRALinearN), in the manner of tests/bwd_ref.py: operands as
+"""CPU float64 references of the LoRA adapters' backward (csrc/lora_bwd.hip, autograd.Projection with adapter operands), in the manner of tests/bwd_ref.py: operands as
 the kernels see them (bf16 or fp32 values widened to float64), the exact result, and a rounding-point variant (`*_r`) that rounds to bf16 where
 the HIP path rounds - T and dT as matrix operands, s * B, every output. tests/test_lora_bwd_ref_cpu.py holds these to torch.autograd in float64."""
 import torch

@@ -457,3 +457,73 @@ def test_linear_backward_sweep(gpu, M, res_scale):
     _check("linear dx", xg.grad.cpu(), r_dx, c, var=BR.bf16(r_dx) if bf else None, rows_from=_tail(M))
     _check("linear dW", wg.grad.cpu(), r_dw, c, var=BR.bf16(r_dw) if bf else None, rows_from=_tail(N))
     _check("linear db", bg.grad.cpu(), r_db, c, var=BR.bf16(r_db) if bf else None)
+
+
+@pytest.mark.parametrize("dtype", [BF, F32])
+@pytest.mark.parametrize("adjacent", [True, False])
+@pytest.mark.parametrize("M", [7, 65])
+def test_linear_n_backward(gpu, M, adjacent, dtype):
+    """autograd.linear_n directly: three projections of one x, K = 128, N = (64, 128, 64); M = 65 is one full 64-row tile plus one row (wgrad pads to
+    128). adjacent: the weights / biases are row blocks of one [256, 128] / [256] buffer (the packed launch); otherwise separate allocations (one
+    launch per projection). dy reaches projections 0 and 2 only: dx = dy_0 w_0 + dy_2 w_2, accumulated in launch order (the bf16 variant rounds
+    each launch's output); projection 1 gets no gradient."""
+    from unigen_amd import autograd as A
+    K, Ns = 128, (64, 128, 64)
+    rows = [slice(sum(Ns[:i]), sum(Ns[:i + 1])) for i in range(3)]
+    c = dict(M=M, adjacent=adjacent, dtype=str(dtype))
+    g = torch.Generator().manual_seed(100 + M)
+    x = torch.randn(M, K, generator=g).to(dtype)
+    W, Bv = (torch.randn(sum(Ns), K, generator=g) * K ** -0.5).to(dtype), (0.1 * torch.randn(sum(Ns), generator=g)).to(dtype)
+    dys = {i: torch.randn(M, Ns[i], generator=g).to(dtype) for i in (0, 2)}
+    xg = x.to(gpu).requires_grad_(True)
+    if adjacent:                                         # separate leaves whose storage is one buffer, as engine._pack leaves q / k / v
+        Wg, Bg = W.to(gpu), Bv.to(gpu)
+        ws, bs = [Wg[r].detach().requires_grad_(True) for r in rows], [Bg[r].detach().requires_grad_(True) for r in rows]
+    else:                                                # one allocation each, with a spare row / element behind it: never back to back
+        spare = lambda t: torch.cat([t, t[:1]]).to(gpu)[:t.shape[0]].detach().requires_grad_(True)
+        ws, bs = [spare(W[r]) for r in rows], [spare(Bv[r]) for r in rows]
+    back_to_back = all(b.data_ptr() == a.data_ptr() + a.numel() * a.element_size() for a, b in zip(ws[:-1], ws[1:]))
+    assert back_to_back == adjacent, c
+    outs = A.linear_n(xg, ws, bs)
+    torch.autograd.backward([outs[0], outs[2]], [dys[0].to(gpu), dys[2].to(gpu)])
+    torch.cuda.synchronize()
+    bf = dtype == BF
+    var = lambda t: BR.bf16(t) if bf else None
+    for i, r in enumerate(rows):
+        y = x.double() @ W[r].double().t() + Bv[r].double()
+        _check(f"linear_n y{i}", outs[i].detach().cpu(), y, c, var=var(y), rows_from=_tail(M))
+    refs = {i: BR.linear_bwd(x, W[rows[i]], dys[i]) for i in (0, 2)}
+    dx = refs[0][0] + refs[2][0]
+    _check("linear_n dx", xg.grad.cpu(), dx, c, var=BR.bf16(BR.bf16(refs[0][0]) + BR.bf16(refs[2][0])) if bf else None, rows_from=_tail(M))
+    for i in (0, 2):
+        _check(f"linear_n dW{i}", ws[i].grad.cpu(), refs[i][1], c, var=var(refs[i][1]), rows_from=_tail(Ns[i]))
+        _check(f"linear_n db{i}", bs[i].grad.cpu(), refs[i][2], c, var=var(refs[i][2]))
+    for p in (ws[1], bs[1]):                             # no dy reached projection 1
+        assert p.grad is None or float(p.grad.abs().max()) == 0.0, c
+
+
+@pytest.mark.parametrize("dtype", [BF, F32])
+@pytest.mark.parametrize("M", [7, 65])
+def test_linear_cat2_backward(gpu, M, dtype):
+    """autograd.linear_cat2 directly: F.linear(cat([a, m], -1), w, b) with Ka = 128, Km = 256, N = 64 against the Linear backward over the
+    materialised concatenation, split at column Ka."""
+    from unigen_amd import autograd as A
+    Ka, Km, N = 128, 256, 64
+    c = dict(M=M, dtype=str(dtype))
+    g = torch.Generator().manual_seed(200 + M)
+    a, m = torch.randn(M, Ka, generator=g).to(dtype), torch.randn(M, Km, generator=g).to(dtype)
+    w, b = (torch.randn(N, Ka + Km, generator=g) * (Ka + Km) ** -0.5).to(dtype), (0.1 * torch.randn(N, generator=g)).to(dtype)
+    dy = torch.randn(M, N, generator=g).to(dtype)
+    ag, mg, wg, bg = (t.to(gpu).requires_grad_(True) for t in (a, m, w, b))
+    y = A.linear_cat2(ag, mg, wg, bg)
+    y.backward(dy.to(gpu))
+    torch.cuda.synchronize()
+    am = torch.cat([a, m], 1)
+    r_y = am.double() @ w.double().t() + b.double()
+    r_dx, r_dw, r_db = BR.linear_bwd(am, w, dy)
+    var = lambda t: BR.bf16(t) if dtype == BF else None
+    _check("linear_cat2 y", y.detach().cpu(), r_y, c, var=var(r_y), rows_from=_tail(M))
+    _check("linear_cat2 da", ag.grad.cpu(), r_dx[:, :Ka], c, var=var(r_dx[:, :Ka]), rows_from=_tail(M))
+    _check("linear_cat2 dm", mg.grad.cpu(), r_dx[:, Ka:], c, var=var(r_dx[:, Ka:]), rows_from=_tail(M))
+    _check("linear_cat2 dw", wg.grad.cpu(), r_dw, c, var=var(r_dw), rows_from=_tail(N))
+    _check("linear_cat2 db", bg.grad.cpu(), r_db, c, var=var(r_db))

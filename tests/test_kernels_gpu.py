@@ -574,7 +574,7 @@ def test_gemm_splitk_tail(gpu, M, N, K, epi):
                                         (2304, 3072, 6144, "256^2 kernel, split-K tail: the last arriver's epilogue")])
 @pytest.mark.parametrize("epi", ["res_gate", "res_scale"])
 def test_gemm_residual_aliased_to_output_every_dispatch_path(gpu, M, N, K, path, epi):
-    """include/unigen_hip.h: `R` may alias `C` (the engine's in-place `x = x + gate * f(x)` / zero-res launches, and LinearN.backward's dX
+    """include/unigen_hip.h: `R` may alias `C` (the engine's in-place `x = x + gate * f(x)` / zero-res launches, and autograd.Projection.backward's dX
     accumulation). Every dispatch path must read a residual element before the store that overwrites it - pinned here per path: aliased == the
     out-of-place result, bitwise."""
     from unigen_amd import lib as L, ops

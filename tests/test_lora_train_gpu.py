@@ -1,5 +1,5 @@
 """Training the LoRA adapters: ug_lora_wgrad (csrc/lora_bwd.hip) against the float64 references of tests/lora_bwd_ref.py, and the adapters' gradients
-through the differentiable forward (unigen_amd/training.py, autograd.LoRALinearN) against torch autograd of the CPU oracle whose projections are
+through the differentiable forward (unigen_amd/training.py, autograd.Projection) against torch autograd of the CPU oracle whose projections are
 peft 0.15's LoRA Linear (R.lora_linear) holding requires_grad A / B tensors. Geometry and adapter placement of tests/test_lora_gpu.py; bounds of
 docs/PARITY_TOLERANCES.md ("Backward sweep") for the kernel and of tests/test_training_gpu.py for the gradients.
 
@@ -361,7 +361,7 @@ def test_sd3_adapter_gradients_match_oracle_autograd(gpu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# one LoRALinearN against the float64 reference and its rounding-point variant
+# one autograd.Projection with adapters against the float64 reference and its rounding-point variant
 # ---------------------------------------------------------------------------------------------------------------------
 def test_single_layer_backward_against_rounding_point_variant(gpu):
     """n = 3 projections of one x at ragged M = 333, separate (non-adjacent) weights: projection 0 carries two adapters, projection 1 one adapter but
@@ -389,7 +389,7 @@ def test_single_layer_backward_against_rounding_point_variant(gpu):
             lays.append(lay)
         a_cat, b_bd, has = fuse_adapters_autograd([l if s else None for l, s in zip(lays, spec)], Ns, dt, gpu)
         assert has == (True, True, False) and a_cat.shape[0] == 64
-        outs = A_.lora_linear_n(x, [l.weight for l in lays], [None] * 3, a_cat, b_bd, has)
+        outs = A_.linear_n(x, [l.weight for l in lays], [None] * 3, lora=(a_cat, b_bd, has))
         torch.autograd.backward([outs[0], outs[2]], [dys0[0].to(dt).to(gpu), dys0[2].to(dt).to(gpu)])
         torch.cuda.synchronize()
         q = lambda t: t.to(dt)

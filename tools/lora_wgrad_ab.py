@@ -1,5 +1,5 @@
 """Interleaved A/B, in ONE process, of the two routes to an adapter gradient C[R, J] = P[M, R]^T Q[M, J] (dA_cat = dT^T X, dB_bd^T = T^T dY):
-  old   ops.transpose of both operands (zero-padded to a multiple of 64 rows) + ops.gemm - what autograd.Linear._grads runs for a weight gradient;
+  old   ops.transpose of both operands (zero-padded to a multiple of 64 rows) + ops.gemm - what autograd._wgrad runs for a weight gradient;
         the transposes are part of the route and are timed with it
   new   ug_lora_wgrad_bf16 (csrc/lora_bwd.hip): both operands row-major, read once
 at the activation shapes of the full-size model, R = 64. Checks both against a float64 product first. Also prints the new kernel's rate over the

@@ -68,51 +68,142 @@ def _x_transposed(x: torch.Tensor, Mp: int) -> torch.Tensor:
     return xt
 
 
-class Linear(torch.autograd.Function):
-    """F.linear on [M, K] rows: ug_gemm_bf16 forward; backward = two more GEMMs and a column sum."""
+def _dgrad(dy: torch.Tensor, wt: torch.Tensor, acc: Optional[torch.Tensor] = None, lora_t=None, lora_b=None) -> torch.Tensor:
+    """dY [M, N] times a transposed weight wt [K, N] -> [M, K] (dX = dY W): into a fresh buffer, optionally with the K-segment lora_t lora_b^T in
+    the same accumulator, or added to `acc` in place through the GEMM's residual epilogue (every element is read and written by one lane; the same
+    bf16 sums autograd would form with separate add kernels)."""
+    M, N = dy.shape
+    if N % 64 != 0:
+        raise L.UniGenHipError(f"linear backward: out_features={N} must be a multiple of 64 (it is the contraction length of dX = dY W)")
+    if acc is None:
+        return ops.gemm(dy, wt, None, torch.empty(M, wt.shape[0], device=dy.device, dtype=dy.dtype), M=M, lora_t=lora_t, lora_b=lora_b)
+    return ops.gemm(dy, wt, None, acc, M=M, epilogue=L.EPI_RES_SCALE, residual=acc, alpha=1.0)
+
+
+def _wgrad(dy: torch.Tensor, xs) -> torch.Tensor:
+    """dW = dY^T [x_0 | x_1 | ...] -> [N, sum K_j], one GEMM per column block, through transposed copies of dY and the x_j (also what the fp32
+    verification path runs). A transposed-operand kernel (dY^T X straight from the row-major operands, tools/probe: csrc/gemm_tn.hip) measured
+    6 % SLOWER per step than this (0.884 vs 0.832 s backward at B = 2): probe library only."""
+    M, N = dy.shape
+    Mp = _pad64(M)
+    dyt = ops.transpose(dy, Mp)                                            # [N, Mp]; the x_j become [K_j, Mp]
+    dw = torch.empty(N, sum(x.shape[1] for x in xs), device=dy.device, dtype=dy.dtype)
+    c0 = 0
+    for x in xs:                                                           # ldc = dw's row stride, K_j columns from column c0
+        ops.gemm(dyt, _x_transposed(x, Mp), None, dw[:, c0:] if c0 else dw, M=N)
+        c0 += x.shape[1]
+    return dw
+
+
+def _bgrad(dy: torch.Tensor) -> torch.Tensor:
+    return ops.colsum(dy).view(dy.shape[1])
+
+
+def _rows(x: torch.Tensor) -> torch.Tensor:
+    return x.reshape(-1, x.shape[-1]).contiguous()
+
+
+def _adjacent(ts) -> bool:
+    """The tensors are consecutive row blocks of one contiguous buffer (the packed QKV / QKV+MLP weights of engine._pack)."""
+    for a, b in zip(ts[:-1], ts[1:]):
+        if a is None or b is None or not a.is_contiguous() or not b.is_contiguous() or a.dtype != b.dtype:
+            return False
+        if b.data_ptr() != a.data_ptr() + a.numel() * a.element_size() or a.shape[1:] != b.shape[1:]:
+            return False
+    return ts[0] is not None and ts[0].is_contiguous()
+
+
+class Projection(torch.autograd.Function):
+    """n >= 1 Linear layers that read the SAME rows x (one projection; to_q | to_k | to_v [| proj_mlp] of an attention block), optionally with live
+    LoRA adapters:  y_i = x w_i^T + b_i [+ T B_bd[rows of i]^T,  T = bf16(x A_cat^T)]. ONE ug_gemm_bf16 over the packed weights when the parameters
+    sit back to back in memory (engine._pack re-points them so), n GEMMs into the column blocks of one buffer otherwise. Returns the n column
+    blocks as views. `a_cat` [Rp, K] / `b_bd` [sum N_i, Rp] are the fused operands of lora.fuse_adapters_autograd (differentiable: torch.autograd
+    carries their gradients on to every adapter's own lora_A / lora_B), or None; `has` [n]: whether projection i carries a live adapter (its rows
+    of b_bd are non-zero). With adapters the forward is the inference engine's (HipModule._lora_gemm: T, then the K-segment launch): the same two
+    launches, the same rounding points.
+    Backward: dx = sum_i dy_i w_i [+ dT A_cat] accumulates through the GEMM's residual epilogue (dy_1 W_1, then R + dy_2 W_2, ...), the adapter
+    term as the K-segment of the first launch; d w_i = dy_i^T x with ONE transposed copy of x. dT = sum_i dy_i B_bd[rows of i] (the projections'
+    rank columns are disjoint, so accumulating adds exact zeros); dA_cat = dT^T x and dB_bd[rows of i] = (T^T dy_i)^T through ug_lora_wgrad - no
+    transposed copy of x or dy unless a base weight itself is trainable."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, n, has, a_cat, b_bd, *wb):
+        ws, bs = wb[:n], wb[n:]
         M, K = x.shape
-        N = w.shape[0]
-        out = torch.empty(M, N, device=x.device, dtype=x.dtype)
-        ops.gemm(x, w, b, out, M=M)
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
-        return out
+        Ns = [w.shape[0] for w in ws]
+        has_b = [b is not None for b in bs]
+        t = None
+        if a_cat is not None:
+            t = ops.gemm(x, a_cat, None, torch.empty(M, a_cat.shape[0], device=x.device, dtype=x.dtype), M=M)
+        out = torch.empty(M, sum(Ns), device=x.device, dtype=x.dtype)
+        if n > 1 and _adjacent(ws) and (all(has_b) and _adjacent([b.view(-1, 1) for b in bs]) or not any(has_b)):
+            wp = torch.as_strided(ws[0], (sum(Ns), K), (K, 1))
+            bp = torch.as_strided(bs[0], (sum(Ns),), (1,)) if has_b[0] else None
+            ops.gemm(x, wp, bp, out, M=M, lora_t=t, lora_b=b_bd)
+        else:                                                    # (one projection: its launch is the packed launch)
+            c0 = 0
+            for w, b, N, h in zip(ws, bs, Ns, has):              # ldc = the buffer's row stride, N columns from column c0
+                ops.gemm(x, w, b, out[:, c0:] if c0 else out, M=M, lora_t=t if h else None, lora_b=b_bd[c0:c0 + N] if h else None)
+                c0 += N
+        ctx.save_for_backward(x, t, a_cat, b_bd, *ws)
+        ctx.Ns, ctx.has, ctx.has_b = Ns, has, has_b
+        return (out,) if n == 1 else out.split(Ns, 1)
 
     @staticmethod
-    def _grads(need_dx, need_dw, need_db, x, w, dy):
-        """(dX = dY W, dW = dY^T X, db = colsum(dY)) of y = x w^T + b for the requested ones; dy contiguous [M, N]."""
-        M, K = x.shape
-        N = w.shape[0]
-        dx = dw = db = None
-        if need_dx:
-            if N % 64 != 0:
-                raise L.UniGenHipError(f"Linear backward: out_features={N} must be a multiple of 64 (it is the contraction length of dX = dY W)")
-            dx = torch.empty(M, K, device=x.device, dtype=x.dtype)
-            ops.gemm(dy, _w_transposed(w), None, dx, M=M)
-        if need_dw:
-            # transposed copies + ug_gemm (also what the fp32 verification path runs). A transposed-operand kernel (dY^T X straight from the row-major
-            # operands, tools/probe: csrc/gemm_tn.hip) measured 6 % SLOWER per step than this (0.884 vs 0.832 s backward at B = 2): probe library only.
-            Mp = _pad64(M)
-            dyt, xt = ops.transpose(dy, Mp), _x_transposed(x, Mp)          # [N, Mp], [K, Mp]
-            dw = torch.empty(N, K, device=x.device, dtype=x.dtype)
-            ops.gemm(dyt, xt, None, dw, M=N)
-        if need_db:
-            db = ops.colsum(dy).view(N)
-        return dx, dw, db
+    def backward(ctx, *dys):
+        saved = ctx.saved_tensors            # ONE access: under torch.utils.checkpoint a second unpack of the same tensors is an error
+        x, t, a_cat, b_bd, ws = saved[0], saved[1], saved[2], saved[3], saved[4:]
+        n, need = len(ws), ctx.needs_input_grad                  # inputs: x, n, has, a_cat, b_bd, n weights, n biases
+        dys = [None if dy is None else dy.contiguous() for dy in dys]
+        d_t, live = None, [i for i in range(n) if ctx.has[i] and dys[i] is not None]
+        if live:
+            rows = [slice(sum(ctx.Ns[:i]), sum(ctx.Ns[:i + 1])) for i in range(n)]
+            if need[0] or need[3]:
+                for i in live:
+                    d_t = _dgrad(dys[i], ops.transpose(b_bd[rows[i]].detach()), d_t)                 # B_bd block transposed: [Rp, N_i]
+        dx = da = db = None
+        dws, dbs = [None] * n, [None] * n
+        for i, dy in enumerate(dys):
+            if dy is None:
+                continue
+            if need[0] and dx is None and d_t is not None:        # dy_i w_i + dT A_cat in one accumulator (lora_b [K, Rp] = A_cat^T)
+                dx = _dgrad(dy, _w_transposed(ws[i]), lora_t=d_t, lora_b=ops.transpose(a_cat.detach()))
+            elif need[0]:
+                dx = _dgrad(dy, _w_transposed(ws[i]), dx)
+            if need[5 + i]:
+                dws[i] = _wgrad(dy, [x])
+            if ctx.has_b[i] and need[5 + n + i]:
+                dbs[i] = _bgrad(dy)
+        if need[3] and d_t is not None:
+            da = ops.lora_wgrad(d_t, x)
+        if need[4] and live:
+            dbt = (torch.empty if len(live) == n else torch.zeros)(a_cat.shape[0], sum(ctx.Ns), device=x.device, dtype=x.dtype)
+            for i in live:
+                ops.lora_wgrad(t, dys[i], dbt[:, rows[i]])
+            db = dbt.t()                                          # produced as [Rp, N] (ug_lora_wgrad's orientation), viewed as [N, Rp]
+        return (dx, None, None, da, db, *dws, *dbs)
 
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        return Linear._grads(ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], x, w, dy.contiguous())
+
+def _project(x: torch.Tensor, ws, bs, lora):
+    a_cat, b_bd, has = lora if lora is not None else (None, None, (False,) * len(ws))
+    return Projection.apply(_rows(x), len(ws), has, a_cat, b_bd, *ws, *bs)
+
+
+def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], lora=None) -> torch.Tensor:
+    """F.linear(x, w, b); `lora`: the (a_cat, b_bd, has) triple of HipModule._lora_autograd when adapters are live on the projection, or None."""
+    return _project(x, [w], [b], lora)[0].view(*x.shape[:-1], w.shape[0])
+
+
+def linear_n(x: torch.Tensor, ws, bs, lora=None):
+    """[F.linear(x, w_i, b_i) for i]: x [..., K] -> views [..., N_i] of one buffer; `lora` as in linear()."""
+    lead = x.shape[:-1]
+    return [o.unflatten(0, lead) if len(lead) != 1 else o for o in _project(x, ws, bs, lora)]
 
 
 class LinearResScale(torch.autograd.Function):
     """r + alpha * F.linear(x, w, b) on [M, K] rows - the zero-res projections `x + controlnet_add_*(z) * conditioning_scale`
     (src/UniGenTransformer.py:1104,1141,1166) - as ONE ug_gemm_bf16 with the UG_EPI_RES_SCALE epilogue (the rounding points of the three torch
-    ops: Linear output, * alpha, + r each a bf16 tensor). Backward: d r = d y; d(lin) = alpha * d y, then Linear's two GEMMs and a column sum."""
+    ops: Linear output, * alpha, + r each a bf16 tensor). Backward: d r = d y; d(lin) = alpha * d y, then a Linear's two GEMMs and a column sum."""
 
     @staticmethod
     def forward(ctx, r, x, w, b, alpha):
@@ -127,16 +218,16 @@ class LinearResScale(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
         dy = dy.contiguous()
         du = dy if ctx.alpha == 1.0 else (dy * ctx.alpha)
-        dx, dw, db = Linear._grads(ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3], x, w, du)
-        return (dy if ctx.needs_input_grad[0] else None), dx, dw, db, None
+        return (dy if need[0] else None, _dgrad(du, _w_transposed(w)) if need[1] else None, _wgrad(du, [x]) if need[2] else None,
+                _bgrad(du) if ctx.has_bias and need[3] else None, None)
 
 
 def linear_res_scale(r: torch.Tensor, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], alpha: float) -> torch.Tensor:
     """r + alpha * linear(x): r [..., N], x [..., K] with equal leading dims."""
-    lead = x.shape[:-1]
-    return LinearResScale.apply(r.reshape(-1, r.shape[-1]).contiguous(), x.reshape(-1, x.shape[-1]).contiguous(), w, b, alpha).view(*lead, w.shape[0])
+    return LinearResScale.apply(_rows(r), _rows(x), w, b, alpha).view(*x.shape[:-1], w.shape[0])
 
 
 class LinearCat2(torch.autograd.Function):
@@ -158,215 +249,19 @@ class LinearCat2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         a, m, w = ctx.saved_tensors
+        need, Ka = ctx.needs_input_grad, a.shape[1]
         dy = dy.contiguous()
-        M, Ka = a.shape
-        Km, N = m.shape[1], w.shape[0]
-        da = dm = dw = db = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            if N % 64 != 0:
-                raise L.UniGenHipError(f"LinearCat2 backward: out_features={N} must be a multiple of 64")
-            wt = _w_transposed(w)                                             # [Ka + Km, N]: row blocks are the transposed column blocks of w
-            if ctx.needs_input_grad[0]:
-                da = torch.empty(M, Ka, device=a.device, dtype=a.dtype)
-                ops.gemm(dy, wt[:Ka], None, da, M=M)
-            if ctx.needs_input_grad[1]:
-                dm = torch.empty(M, Km, device=a.device, dtype=a.dtype)
-                ops.gemm(dy, wt[Ka:], None, dm, M=M)
-        if ctx.needs_input_grad[2]:
-            Mp = _pad64(M)
-            dyt = ops.transpose(dy, Mp)
-            dw = torch.empty(N, Ka + Km, device=a.device, dtype=a.dtype)
-            ops.gemm(dyt, _x_transposed(a, Mp), None, dw[:, :Ka], M=N)
-            ops.gemm(dyt, _x_transposed(m, Mp), None, dw[:, Ka:], M=N)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            db = ops.colsum(dy).view(N)
-        return da, dm, dw, db
+        wt = _w_transposed(w) if need[0] or need[1] else None             # [Ka + Km, N]: row blocks are the transposed column blocks of w
+        return (_dgrad(dy, wt[:Ka]) if need[0] else None, _dgrad(dy, wt[Ka:]) if need[1] else None, _wgrad(dy, [a, m]) if need[2] else None,
+                _bgrad(dy) if ctx.has_bias and need[3] else None)
 
 
-def linear_cat2(a: torch.Tensor, m: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
-    lead = a.shape[:-1]
-    return LinearCat2.apply(a.reshape(-1, a.shape[-1]).contiguous(), m.reshape(-1, m.shape[-1]).contiguous(), w, b).view(*lead, w.shape[0])
-
-
-def _adjacent(ts) -> bool:
-    """The tensors are consecutive row blocks of one contiguous buffer (the packed QKV / QKV+MLP weights of engine._pack)."""
-    for a, b in zip(ts[:-1], ts[1:]):
-        if a is None or b is None or not a.is_contiguous() or not b.is_contiguous() or a.dtype != b.dtype:
-            return False
-        if b.data_ptr() != a.data_ptr() + a.numel() * a.element_size() or a.shape[1:] != b.shape[1:]:
-            return False
-    return ts[0] is not None and ts[0].is_contiguous()
-
-
-class LinearN(torch.autograd.Function):
-    """n Linear layers that read the SAME rows x (to_q | to_k | to_v [| proj_mlp] of an attention block): ONE ug_gemm_bf16 over their packed
-    weights when the parameters sit back to back in memory (engine._pack re-points them so), n GEMMs into the column blocks of one buffer
-    otherwise. Returns the n column blocks as views. Backward: d x accumulates through the GEMM's residual epilogue (dy_1 W_1, then
-    R + dy_2 W_2, ...: the same bf16 sums autograd would form with separate add kernels), d w_i = dy_i^T x with ONE transposed copy of x."""
-
-    @staticmethod
-    def forward(ctx, x, n, *wb):
-        ws, bs = wb[:n], wb[n:]
-        M, K = x.shape
-        Ns = [w.shape[0] for w in ws]
-        out = torch.empty(M, sum(Ns), device=x.device, dtype=x.dtype)
-        has_b = all(b is not None for b in bs)
-        if _adjacent(list(ws)) and (has_b and _adjacent([b.view(-1, 1) for b in bs]) or all(b is None for b in bs)):
-            wp = torch.as_strided(ws[0], (sum(Ns), K), (K, 1))
-            bp = torch.as_strided(bs[0], (sum(Ns),), (1,)) if has_b else None
-            ops.gemm(x, wp, bp, out, M=M)
-        else:
-            c0 = 0
-            for w, b, N in zip(ws, bs, Ns):
-                ops.gemm(x, w, b, out[:, c0:], M=M)          # ldc = the buffer's row stride, N columns from column c0
-                c0 += N
-        ctx.save_for_backward(x, *ws)
-        ctx.n, ctx.Ns, ctx.has_b = n, Ns, [b is not None for b in bs]
-        outs, c0 = [], 0
-        for N in Ns:
-            outs.append(out[:, c0:c0 + N]); c0 += N
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *dys):
-        saved = ctx.saved_tensors            # ONE access: under torch.utils.checkpoint a second unpack of the same tensors is an error
-        x, ws = saved[0], saved[1:]
-        n, M, K = ctx.n, x.shape[0], x.shape[1]
-        dx = None
-        dws, dbs = [None] * n, [None] * n
-        Mp = _pad64(M)
-        for i, (dy, w) in enumerate(zip(dys, ws)):
-            if dy is None:
-                continue
-            dy = dy.contiguous()
-            N = w.shape[0]
-            if ctx.needs_input_grad[0]:
-                if N % 64 != 0:
-                    raise L.UniGenHipError(f"LinearN backward: out_features={N} must be a multiple of 64")
-                if dx is None:
-                    dx = torch.empty(M, K, device=x.device, dtype=x.dtype)
-                    ops.gemm(dy, _w_transposed(w), None, dx, M=M)
-                else:                                             # dx += dy W (in place: every element is read and written by one lane)
-                    ops.gemm(dy, _w_transposed(w), None, dx, M=M, epilogue=L.EPI_RES_SCALE, residual=dx, alpha=1.0)
-            if ctx.needs_input_grad[2 + i]:
-                dw = torch.empty(N, K, device=x.device, dtype=x.dtype)
-                ops.gemm(ops.transpose(dy, Mp), _x_transposed(x, Mp), None, dw, M=N)
-                dws[i] = dw
-            if ctx.has_b[i] and ctx.needs_input_grad[2 + n + i]:
-                dbs[i] = ops.colsum(dy).view(N)
-        return (dx, None, *dws, *dbs)
-
-
-def linear_n(x: torch.Tensor, ws, bs):
-    """[F.linear(x, w_i, b_i) for i]: x [..., K] -> views [..., N_i] of one buffer."""
-    lead = x.shape[:-1]
-    outs = LinearN.apply(x.reshape(-1, x.shape[-1]).contiguous(), len(ws), *ws, *bs)
-    return [o.unflatten(0, lead) if len(lead) != 1 else o for o in outs]
-
-
-class LoRALinearN(torch.autograd.Function):
-    """LinearN (n >= 1 projections of the same rows x) with live LoRA adapters:  y_i = x w_i^T + b_i + T B_bd[rows of i]^T,  T = bf16(x A_cat^T).
-    `a_cat` [Rp, K] / `b_bd` [sum N_i, Rp] are the fused operands of lora.fuse_adapters_autograd (differentiable: torch.autograd carries their
-    gradients on to every adapter's own lora_A / lora_B). The forward is the inference engine's (HipModule._lora_gemm: T, then the K-segment launch): the
-    same two launches, the same rounding points. `has` [n]: whether projection i carries a live adapter (its rows of b_bd are non-zero).
-    Backward: dT = sum_i dy_i B_bd[rows of i] (the projections' rank columns are disjoint, so accumulating through the GEMM's residual epilogue adds
-    exact zeros); dx = sum_i dy_i w_i + dT A_cat, the adapter term as the K-segment of the first launch; dA_cat = dT^T x and dB_bd[rows of i] =
-    (T^T dy_i)^T through ug_lora_wgrad - no transposed copy of x or dy unless a base weight itself is trainable."""
-
-    @staticmethod
-    def forward(ctx, x, n, has, a_cat, b_bd, *wb):
-        ws, bs = wb[:n], wb[n:]
-        M, K = x.shape
-        Ns = [w.shape[0] for w in ws]
-        t = torch.empty(M, a_cat.shape[0], device=x.device, dtype=x.dtype)
-        ops.gemm(x, a_cat, None, t, M=M)
-        out = torch.empty(M, sum(Ns), device=x.device, dtype=x.dtype)
-        has_b = all(b is not None for b in bs)
-        if _adjacent(list(ws)) and (has_b and _adjacent([b.view(-1, 1) for b in bs]) or all(b is None for b in bs)):
-            wp = torch.as_strided(ws[0], (sum(Ns), K), (K, 1))
-            bp = torch.as_strided(bs[0], (sum(Ns),), (1,)) if has_b else None
-            ops.gemm(x, wp, bp, out, M=M, lora_t=t, lora_b=b_bd)
-        else:
-            c0 = 0
-            for w, b, N, h in zip(ws, bs, Ns, has):
-                ops.gemm(x, w, b, out[:, c0:], M=M, lora_t=t if h else None, lora_b=b_bd[c0:c0 + N] if h else None)
-                c0 += N
-        ctx.save_for_backward(x, t, a_cat, b_bd, *ws)
-        ctx.n, ctx.Ns, ctx.has, ctx.has_b = n, Ns, tuple(has), [b is not None for b in bs]
-        outs, c0 = [], 0
-        for N in Ns:
-            outs.append(out[:, c0:c0 + N]); c0 += N
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *dys):
-        saved = ctx.saved_tensors            # ONE access (block checkpointing, see LinearN.backward)
-        x, t, a_cat, b_bd, ws = saved[0], saved[1], saved[2], saved[3], saved[4:]
-        n, M, K, Rp = ctx.n, x.shape[0], x.shape[1], a_cat.shape[0]
-        need_x, need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        dys = [None if dy is None else dy.contiguous() for dy in dys]
-        row0 = [sum(ctx.Ns[:i]) for i in range(n)]
-        for dy, w in zip(dys, ws):
-            if dy is not None and w.shape[0] % 64 != 0:
-                raise L.UniGenHipError(f"LoRALinearN backward: out_features={w.shape[0]} must be a multiple of 64")
-        d_t = None
-        if need_x or need_a:
-            for i, dy in enumerate(dys):
-                if dy is None or not ctx.has[i]:
-                    continue
-                bt = ops.transpose(b_bd[row0[i]:row0[i] + ctx.Ns[i]].detach())                     # [Rp, N_i]
-                if d_t is None:
-                    d_t = torch.empty(M, Rp, device=x.device, dtype=x.dtype)
-                    ops.gemm(dy, bt, None, d_t, M=M)
-                else:
-                    ops.gemm(dy, bt, None, d_t, M=M, epilogue=L.EPI_RES_SCALE, residual=d_t, alpha=1.0)
-        dx = da = db = None
-        dws, dbs = [None] * n, [None] * n
-        Mp = _pad64(M)
-        for i, (dy, w) in enumerate(zip(dys, ws)):
-            if dy is None:
-                continue
-            N = w.shape[0]
-            if need_x:
-                if dx is None:                                    # dy_i w_i + dT A_cat in one accumulator (lora_b [K, Rp] = A_cat^T)
-                    dx = torch.empty(M, K, device=x.device, dtype=x.dtype)
-                    ops.gemm(dy, _w_transposed(w), None, dx, M=M, lora_t=d_t, lora_b=ops.transpose(a_cat.detach()) if d_t is not None else None)
-                else:
-                    ops.gemm(dy, _w_transposed(w), None, dx, M=M, epilogue=L.EPI_RES_SCALE, residual=dx, alpha=1.0)
-            if ctx.needs_input_grad[5 + i]:                       # a trainable base weight: the transposed-copy route of Linear._grads
-                dw = torch.empty(N, K, device=x.device, dtype=x.dtype)
-                ops.gemm(ops.transpose(dy, Mp), _x_transposed(x, Mp), None, dw, M=N)
-                dws[i] = dw
-            if ctx.has_b[i] and ctx.needs_input_grad[5 + n + i]:
-                dbs[i] = ops.colsum(dy).view(N)
-        if need_a and d_t is not None:
-            da = ops.lora_wgrad(d_t, x)
-        if need_b and any(dy is not None and h for dy, h in zip(dys, ctx.has)):
-            full = all(dy is not None and h for dy, h in zip(dys, ctx.has))
-            dbt = (torch.empty if full else torch.zeros)(Rp, sum(ctx.Ns), device=x.device, dtype=x.dtype)
-            for i, dy in enumerate(dys):
-                if dy is not None and ctx.has[i]:
-                    ops.lora_wgrad(t, dy, dbt[:, row0[i]:row0[i] + ctx.Ns[i]])
-            db = dbt.t()                                          # produced as [Rp, N] (ug_lora_wgrad's orientation), viewed as [N, Rp]
-        return (dx, None, None, da, db, *dws, *dbs)
-
-
-def lora_linear_n(x: torch.Tensor, ws, bs, a_cat: torch.Tensor, b_bd: torch.Tensor, has):
-    """linear_n with the fused adapter operands of the launch (lora.fuse_adapters_autograd)."""
-    lead = x.shape[:-1]
-    outs = LoRALinearN.apply(x.reshape(-1, x.shape[-1]).contiguous(), len(ws), tuple(has), a_cat, b_bd, *ws, *bs)
-    return [o.unflatten(0, lead) if len(lead) != 1 else o for o in outs]
-
-
-def lora_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], a_cat: torch.Tensor, b_bd: torch.Tensor) -> torch.Tensor:
-    lead = x.shape[:-1]
-    return LoRALinearN.apply(x.reshape(-1, x.shape[-1]).contiguous(), 1, (True,), a_cat, b_bd, w, b)[0].view(*lead, w.shape[0])
-
-
-def lora_linear_cat2(a: torch.Tensor, m: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], a_cat: torch.Tensor, b_bd: torch.Tensor) -> torch.Tensor:
-    """linear_cat2 with adapters on the projection: the GEMM's one K-segment is taken by the adapters (as in the inference engine, whose
-    [attention | mlp] operand is one buffer), so the concatenation is materialised; same bits as linear_cat2 + the adapter term."""
-    return lora_linear(torch.cat([a, m], dim=-1), w, b, a_cat, b_bd)
+def linear_cat2(a: torch.Tensor, m: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], lora=None) -> torch.Tensor:
+    """With adapters on the projection the GEMM's one K-segment is taken by them (as in the inference engine, whose [attention | mlp] operand is
+    one buffer), so the concatenation is materialised; same bits as linear_cat2 + the adapter term."""
+    if lora is not None:
+        return linear(torch.cat([a, m], dim=-1), w, b, lora)
+    return LinearCat2.apply(_rows(a), _rows(m), w, b).view(*a.shape[:-1], w.shape[0])
 
 
 class MoeGate(torch.autograd.Function):
@@ -402,11 +297,6 @@ class MoeGate(torch.autograd.Function):
         gates, x, c, wg = ctx.saved_tensors
         dxc, dwg = ops.moe_gate_bwd(gates, dgates.float().contiguous(), x, c, wg)
         return (dxc if ctx.needs_input_grad[0] else None), (dxc if ctx.needs_input_grad[1] else None), (dwg if ctx.needs_input_grad[2] else None), None, None
-
-
-def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
-    lead = x.shape[:-1]
-    return Linear.apply(x.reshape(-1, x.shape[-1]).contiguous(), w, b).view(*lead, w.shape[0])
 
 
 class GeluTanh(torch.autograd.Function):

@@ -19,6 +19,18 @@ from .ops import RowMap
 BF = torch.bfloat16
 
 
+def moe_capacity(S: int, E: int, K: int) -> int:
+    """deepspeed _capacity(gates, capacity_factor * K, min_capacity = 4) of top1gating / top2gating / topkgating at capacity_factor 1: slots per
+    expert for S tokens, E experts, K choices per token."""
+    return max(int(math.ceil((S / E) * float(K))), 4)
+
+
+def gumbel_draw(S: int, E: int, device) -> torch.Tensor:
+    """top2gating's gumbel_rsample: torch.distributions.gumbel.Gumbel(0, 1).rsample([S, E]) on the device (the reference consumes the global
+    device RNG too)."""
+    return torch.distributions.gumbel.Gumbel(torch.tensor(0.0, device=device), torch.tensor(1.0, device=device)).rsample((S, E))
+
+
 def _register(root: nn.Module, name: str, shape: Tuple[int, ...], device, dtype) -> nn.Parameter:
     parts = name.split(".")
     mod = root
@@ -306,7 +318,7 @@ class HipModule(LoRAHost, nn.Module):
         exp_counts = torch.empty(E, device=dev, dtype=torch.int64)
         l_aux = torch.empty(1, device=dev, dtype=torch.float32)
         if top_k == 1:
-            C = max(int(math.ceil(S / E)), 4)          # deepspeed _capacity(capacity_factor=1, min_capacity=4)
+            C = moe_capacity(S, E, 1)
             idx, slot, tos = self._w("moe_idx", (S,), torch.int32), self._w("moe_slot", (S,), torch.int32), self._w("moe_tos", (E, C), torch.int32)
             ops.moe_gate_top1(x, c, wg, gates, idx)
             if draw is None:
@@ -318,18 +330,18 @@ class HipModule(LoRAHost, nn.Module):
             # capacity ceil(k S / E), the K largest logits per token, per expert the `capacity` largest of [chosen logit | 0], renormalised weights
             if top_k > E:
                 raise ValueError(f"top_num {top_k} exceeds the {E} experts")
-            C = max(int(math.ceil((S / E) * float(top_k))), 4)
+            C = moe_capacity(S, E, top_k)
             K = top_k
             idx, slot, tos = self._w("moe_idxk", (K, S), torch.int32), self._w("moe_slotk", (K, S), torch.int32), self._w("moe_tos", (E, C), torch.int32)
             weights, logits = self._w("moe_wk", (K, S), torch.float32), self._w("moe_logits", (S, E), torch.float32)
             ops.moe_gate_topk(x, c, wg, K, gates, logits, idx)
             ops.moe_capacity_topk(gates, logits, idx, C, slot, tos, weights, exp_counts, l_aux)
             return _Routing(K, E, C, gates, idx, slot, tos, weights, exp_counts, l_aux)
-        C = max(int(math.ceil((S / E) * 2.0)), 4)      # top2gating: _capacity(gates, capacity_factor * 2, min_capacity)
+        C = moe_capacity(S, E, 2)
         idx, slot, tos = self._w("moe_idx2", (2, S), torch.int32), self._w("moe_slot2", (2, S), torch.int32), self._w("moe_tos", (E, C), torch.int32)
         weights = self._w("moe_w2", (2, S), torch.float32)
-        if draw is None:                               # gumbel_rsample: torch.distributions.gumbel.Gumbel(0, 1).rsample on the device
-            draw = torch.distributions.gumbel.Gumbel(torch.tensor(0.0, device=dev), torch.tensor(1.0, device=dev)).rsample((S, E))
+        if draw is None:
+            draw = gumbel_draw(S, E, dev)
         ops.moe_gate_top2(x, c, wg, draw.to(torch.float32).contiguous(), gates, idx)
         ops.moe_capacity_top2(gates, idx, C, slot, tos, weights, exp_counts, l_aux)
         return _Routing(2, E, C, gates, idx, slot, tos, weights, exp_counts, l_aux)

@@ -11,7 +11,6 @@ gathers) stays torch on the GPU. Activation memory is the reference's too: wrap 
 fp32 parameters run the `_f32` verification twins end to end."""
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
@@ -19,6 +18,7 @@ import torch.nn.functional as F
 
 from . import autograd as A
 from . import ops
+from .engine import gumbel_draw, moe_capacity
 
 
 def _p(model, name: str) -> Optional[torch.Tensor]:
@@ -26,18 +26,12 @@ def _p(model, name: str) -> Optional[torch.Tensor]:
 
 
 def _lin(model, prefix: str, x: torch.Tensor) -> torch.Tensor:
-    lo = model._lora_autograd([prefix])
-    if lo is not None:
-        return A.lora_linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"), lo[0], lo[1])
-    return A.linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"))
+    return A.linear(x, _p(model, prefix + ".weight"), _p(model, prefix + ".bias"), lora=model._lora_autograd([prefix]))
 
 
 def _lin_n(model, x: torch.Tensor, prefixes):
     ws, bs = [_p(model, p + ".weight") for p in prefixes], [_p(model, p + ".bias") for p in prefixes]
-    lo = model._lora_autograd(prefixes)
-    if lo is not None:
-        return A.lora_linear_n(x, ws, bs, *lo)
-    return A.linear_n(x, ws, bs)
+    return A.linear_n(x, ws, bs, lora=model._lora_autograd(prefixes))
 
 
 def _zero_res(model, prefix: str, x, z, scale: float):
@@ -149,8 +143,7 @@ def _single_block_body(model, prefix: str, h, temb, rope):
     mlp = A.GeluTanh.apply(_lin(model, prefix + ".proj_mlp", n))      # its own GEMM: GELU wants a contiguous [M, 4 D] (a view of the fused output would be copied)
     # proj_out(cat[a, mlp]) without the [B, L, 5 D] concatenation: the mlp columns ride as the GEMM's K-segment extension (same bits)
     w_o, b_o = _p(model, prefix + ".proj_out.weight"), _p(model, prefix + ".proj_out.bias")
-    lo = model._lora_autograd([prefix + ".proj_out"])
-    o = A.lora_linear_cat2(a, mlp, w_o, b_o, lo[0], lo[1]) if lo is not None else A.linear_cat2(a, mlp, w_o, b_o)
+    o = A.linear_cat2(a, mlp, w_o, b_o, lora=model._lora_autograd([prefix + ".proj_out"]))
     return A.gate_residual(h, o, gate)
 
 
@@ -199,42 +192,36 @@ def _route(model, x, c, uniform):
     wg = model.get_parameter("moe.moe_layer.gate.wg.weight")
     x2, c2 = x.reshape(S, D).contiguous(), c.reshape(S, D).contiguous()
     exp_counts, l_aux_k = torch.empty(E, device=dev, dtype=torch.int64), torch.empty(1, device=dev, dtype=torch.float32)
+    C = moe_capacity(S, E, K)
+    tos = torch.empty(E, C, device=dev, dtype=torch.int32)
     if K == 1:
-        C = max(int(math.ceil(S / E)), 4)
         # gate logits / softmax / arg-max and their backward: HIP kernels (round 2 ran F.linear + F.softmax here: vendor BLAS on a product path)
         gates, idx, _ = A.MoeGate.apply(x2, c2, wg)
         if uniform is None:
             uniform = torch.rand(S, E, device=dev, dtype=torch.float32)
-        slot, tos = torch.empty(S, device=dev, dtype=torch.int32), torch.empty(E, C, device=dev, dtype=torch.int32)
+        slot = torch.empty(S, device=dev, dtype=torch.int32)
         ops.moe_capacity_rts(gates.detach().contiguous(), idx, uniform.contiguous(), C, slot, tos, exp_counts, l_aux_k)
         l_aux = torch.sum(gates.mean(0) * F.one_hot(idx.long(), E).float().mean(0)) * E
         kept = (slot >= 0).unsqueeze(0)
         flat = (idx.long() * C + slot.long()).clamp_min(0).unsqueeze(0)
         w = (gates.gather(1, idx.long().unsqueeze(1)).squeeze(1) * kept[0].float()).to(x.dtype).unsqueeze(0)      # combine weight, rounded as `cw.to(dt)`
-    elif K > 2:                                          # deepspeed topkgating: no random draw; the capacity rule ranks the chosen LOGITS against zeros
-        C = max(int(math.ceil((S / E) * float(K))), 4)
-        gates, idx, logits = A.MoeGate.apply(x2, c2, wg, K, None)
-        slot, tos = torch.empty(K, S, device=dev, dtype=torch.int32), torch.empty(E, C, device=dev, dtype=torch.int32)
-        w_dev = torch.empty(K, S, device=dev, dtype=torch.float32)
-        ops.moe_capacity_topk(gates.detach().contiguous(), logits, idx, C, slot, tos, w_dev, exp_counts, l_aux_k)
-        chosen = torch.zeros(S, E, device=dev, dtype=torch.float32).scatter_(1, idx.long().t(), 1.0)
-        l_aux = torch.mean(gates.mean(0) * chosen.mean(0)) * E * E / K
+    else:
+        slot = torch.empty(K, S, device=dev, dtype=torch.int32)
+        w_dev = torch.empty(K, S, device=dev, dtype=torch.float32)      # the kernel's weights: not on the tape, recomputed below from `gates`
+        if K > 2:                                        # deepspeed topkgating: no random draw; the capacity rule ranks the chosen LOGITS against zeros
+            gates, idx, logits = A.MoeGate.apply(x2, c2, wg, K, None)
+            ops.moe_capacity_topk(gates.detach().contiguous(), logits, idx, C, slot, tos, w_dev, exp_counts, l_aux_k)
+            chosen = torch.zeros(S, E, device=dev, dtype=torch.float32).scatter_(1, idx.long().t(), 1.0)
+            l_aux = torch.mean(gates.mean(0) * chosen.mean(0)) * E * E / K
+        else:
+            if uniform is None:
+                uniform = gumbel_draw(S, E, dev)
+            gates, idx, _ = A.MoeGate.apply(x2, c2, wg, 2, uniform.to(torch.float32).contiguous())
+            ops.moe_capacity_top2(gates.detach().contiguous(), idx, C, slot, tos, w_dev, exp_counts, l_aux_k)
+            l_aux = torch.mean(gates.mean(0) * F.one_hot(idx[0].long(), E).float().mean(0)) * E * E
         kept = slot >= 0
         flat = (idx.long() * C + slot.long()).clamp_min(0)
         g = torch.stack([gates.gather(1, idx[k].long().unsqueeze(1)).squeeze(1) for k in range(K)]) * kept.float()
-        w = (g / torch.clamp(g.sum(0, keepdim=True), min=torch.finfo(torch.float32).eps)).to(x.dtype)
-    else:
-        C = max(int(math.ceil((S / E) * 2.0)), 4)
-        if uniform is None:                            # gumbel_rsample
-            uniform = torch.distributions.gumbel.Gumbel(torch.tensor(0.0, device=dev), torch.tensor(1.0, device=dev)).rsample((S, E))
-        gates, idx, _ = A.MoeGate.apply(x2, c2, wg, 2, uniform.to(torch.float32).contiguous())
-        slot, tos = torch.empty(2, S, device=dev, dtype=torch.int32), torch.empty(E, C, device=dev, dtype=torch.int32)
-        w_dev = torch.empty(2, S, device=dev, dtype=torch.float32)      # the kernel's weights: not on the tape, recomputed below from `gates`
-        ops.moe_capacity_top2(gates.detach().contiguous(), idx, C, slot, tos, w_dev, exp_counts, l_aux_k)
-        l_aux = torch.mean(gates.mean(0) * F.one_hot(idx[0].long(), E).float().mean(0)) * E * E
-        kept = slot >= 0
-        flat = (idx.long() * C + slot.long()).clamp_min(0)
-        g = torch.stack([gates.gather(1, idx[k].long().unsqueeze(1)).squeeze(1) for k in range(2)]) * kept.float()
         w = (g / torch.clamp(g.sum(0, keepdim=True), min=torch.finfo(torch.float32).eps)).to(x.dtype)             # gates1_s / denom_s, gates2_s / denom_s
     tos_l = tos.view(-1).long()
     valid, src = tos_l >= 0, tos_l.clamp_min(0)
