@@ -300,6 +300,44 @@ int ug_nhwc_to_nchw(const void* in, void* out, int64_t B, int64_t C, int64_t HW,
 int ug_vae_sample(const void* moments, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale,
                   ug_stream_t stream);
 
+/* One tile of AutoencoderKL.tiled_decode / tiled_encode as the blend kernel sees it: logical element (b, c, y, x) of a [B][C][H][W] tile
+ * lives at p + b * sb + c * sc + y * sy + x * sx (strides in ELEMENTS, any layout: NHWC rows [B*H*W][Cp] are sb = H W Cp, sc = 1, sy = W Cp,
+ * sx = Cp; NCHW is sb = C H W, sc = H W, sy = W, sx = 1). p == NULL: there is no such neighbour (first row / first column of tiles). */
+typedef struct ug_vae_tile {
+    const void* p;
+    int64_t H, W;
+    int64_t sb, sc, sy, sx;
+} ug_vae_tile;
+
+typedef struct ug_vae_blend_desc {
+    ug_vae_tile T, U, Lf, UL;            /* the tile, its upper, left and upper-left neighbours, all RAW (as the decoder / encoder wrote them) */
+    void* out;                           /* canvas element that receives T(0, 0): out + b * ob + c * oc + y * oy + x * ox */
+    int64_t ob, oc, oy, ox;
+    int64_t B, C;
+    int64_t h, w;                        /* the region written: rows [0, h) x columns [0, w) of the tile (diffusers' [:row_limit, :row_limit] crop) */
+    int64_t E;                           /* blend extent in rows / columns (>= 0; 0 = plain copy of the crop) */
+} ug_vae_blend_desc;
+
+/* diffusers AutoencoderKL.tiled_decode / tiled_encode after the per-tile decoder / encoder: blend_v with the upper tile, blend_h with the left
+ * tile, crop, and the two torch.cat calls, as ONE pass per tile that writes every element of the tile's canvas region exactly once.
+ * The reference blends in place in row-major tile order, so a tile's neighbours are already blended when it reads them; because a blend only
+ * touches a tile's first E rows / columns, that order collapses to a closed form over the four RAW tiles (needs U.H >= e_v + E and
+ * Lf.W >= e_h + E, i.e. a full tile of at least 2 E: tile_overlap_factor <= 0.5; UG_ERR_UNSUPPORTED otherwise). With
+ * e_v = U ? min(U.H, T.H, E) : 0, e_h = Lf ? min(Lf.W, T.W, E) : 0 and lerp(a, b, k, e) = rnd(rnd(a * f32(1 - k / e)) + rnd(b * f32(k / e)))
+ * (k / e and 1 - k / e in double, rnd = round to the tensor dtype: torch's three roundings of `a * (1 - k / e) + b * (k / e)`):
+ *     U'(r, x)  = x < e_h ? lerp(UL(r, UL.W - e_h + x), U(r, x), x, e_h) : U(r, x)
+ *     Lf'(y, c) = y < e_v ? lerp(UL(UL.H - e_v + y, c), Lf(y, c), y, e_v) : Lf(y, c)
+ *     t1        = y < e_v ? lerp(U'(U.H - e_v + y, x), T(y, x), y, e_v) : T(y, x)
+ *     out(y, x) = x < e_h ? lerp(Lf'(y, Lf.W - e_h + x), t1, x, e_h) : t1            for y < h <= T.H, x < w <= T.W, every b < B, c < C.
+ * Shapes: U.W == T.W, Lf.H == T.H, UL.H == U.H, UL.W == Lf.W; UL is required when both U and Lf are given (UG_ERR_BAD_SHAPE).
+ * Aliasing: the region written must not overlap any of the four tiles; the tiles are only read and may overlap each other. No workspace, no
+ * atomics, nothing kept between launches. Fast paths (16-byte loads and stores) when every tile given is channel-contiguous with pixels
+ * of whole 8-channel groups (sc == 1, p 16-byte aligned, sb / sy / sx multiples of 8, sx >= C rounded up to 8: the channels up to that bound are
+ * READ at every pixel of a tile, so they must exist, as they do in NHWC rows [B*H*W][Cp]) and the canvas is channel-contiguous in the same way (the encoder's NHWC moments) or x-contiguous (ox == 1:
+ * the decoder's NCHW image, written straight from the NHWC conv_out rows); rows that are not 16-byte aligned, ragged row ends and
+ * C % 8 channels go through scalar accesses. Any other stride combination runs element by element. */
+int ug_vae_tile_blend(const ug_vae_blend_desc* d, ug_stream_t stream);
+
 /* ---- fp32 verification twins (see the conventions at the top). Same arguments as the functions they mirror; every `void*` tensor
  * that is bf16 there is fp32 here (weights included); fp32 / integer arguments are unchanged. ug_gemm_f32: K, N unconstrained,
  * the column-split boundaries multiples of 64, no workspace. ug_small_linear_f32: M <= 64. ---- */
@@ -352,6 +390,7 @@ int ug_nchw_to_nhwc_f32(const void* in, void* out, int64_t B, int64_t C, int64_t
 int ug_nhwc_to_nchw_f32(const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, ug_stream_t stream);
 int ug_vae_sample_f32(const void* moments, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale,
                       ug_stream_t stream);
+int ug_vae_tile_blend_f32(const ug_vae_blend_desc* d, ug_stream_t stream);
 int ug_pack_latents_f32(const void* latents, void* packed, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t stream);
 int ug_unpack_latents_f32(const void* packed, void* latents, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t stream);
 

@@ -1,10 +1,15 @@
-"""AutoencoderKL (FLUX geometry) at 1024^2: decode and encode latency, per-call conv shapes. usage: python tools/vae_bench.py [--size 1024] [--batch 1]"""
+"""AutoencoderKL (FLUX geometry) at 1024^2: decode and encode latency, per-call conv shapes. usage: python tools/vae_bench.py [--size 1024] [--batch 1]
+--tiled [--size 2048] [--rounds 5]: untiled against tiled (enable_tiling(), default tile sizes 1024 / 128 / 0.25) decode and encode of ONE process,
+interleaved round by round (untiled decode, tiled decode, untiled encode, tiled encode, again ...), every timing a host clock around calls that end in a
+device synchronise; then one instrumented pass with a device-event pair around every ug_vae_tile_blend launch for the blend's share of the tiled time."""
 import argparse, os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from unigen_amd.vae import AutoencoderKL
 
-ap = argparse.ArgumentParser(); ap.add_argument("--size", type=int, default=1024); ap.add_argument("--batch", type=int, default=1); a = ap.parse_args()
+ap = argparse.ArgumentParser(); ap.add_argument("--size", type=int, default=None); ap.add_argument("--batch", type=int, default=1)
+ap.add_argument("--tiled", action="store_true"); ap.add_argument("--rounds", type=int, default=5); a = ap.parse_args()
+a.size = a.size or (2048 if a.tiled else 1024)
 dev = torch.device("cuda:0")
 vae = AutoencoderKL(device=dev, dtype=torch.bfloat16)
 vae.init_synthetic_(seed=0)
@@ -25,6 +30,49 @@ def timeit(f, n=5):
     f(); torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(n): f()
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / n * 1e3
+def tiled_report():
+    import statistics
+    def mode(on, f):
+        def run():
+            vae.enable_tiling(on); return f()
+        return run
+    runs = [("decode_untiled", mode(False, lambda: vae.decode(lat).sample)), ("decode_tiled", mode(True, lambda: vae.decode(lat).sample)),
+            ("encode_untiled", mode(False, lambda: vae.encode(img).latent_dist._m)), ("encode_tiled", mode(True, lambda: vae.encode(img).latent_dist._m))]
+    outs = {}
+    for name, f in runs:                                   # warm-up of every shape the timed window uses; the outputs serve the difference below
+        outs[name] = f().float(); torch.cuda.synchronize()
+    rel = lambda x, y: float((x - y).norm() / y.norm())
+    ms = {name: [] for name, _ in runs}
+    for _ in range(a.rounds):
+        for name, f in runs:
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(2): f()
+            torch.cuda.synchronize(); ms[name].append((time.perf_counter() - t0) / 2 * 1e3)
+    res = dict(size=a.size, batch=a.batch, rounds=a.rounds, tile_sample_min_size=vae.tile_sample_min_size, tile_latent_min_size=vae.tile_latent_min_size,
+               tile_overlap_factor=vae.tile_overlap_factor)
+    for name, v in ms.items():
+        res[name + "_ms"] = dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2))
+    res["decode_tiled_vs_untiled_relL2"] = round(rel(outs["decode_tiled"], outs["decode_untiled"]), 4)          # different by design: per-tile GroupNorm / attention
+    res["encode_tiled_vs_untiled_relL2"] = round(rel(outs["encode_tiled"], outs["encode_untiled"]), 4)
+    # the blend launches' share: device events around each launch, in a pass of its own (the events cost host time, so it is not one of the timings above)
+    blend = ops.vae_tile_blend
+    for name, f in runs[1::2]:
+        ev, nbytes = [], [0]
+        def timed(tile, up, left, ul, out, extent):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record(); r = blend(tile, up, left, ul, out, extent); e.record(); ev.append((s, e))
+            nbytes[0] += out.element_size() * out.shape[0] * out.shape[2] * out.shape[3] * (out.shape[1] + tile.stride(3))      # crop written + the tile's crop read (whole pixels)
+            return r
+        _v.ops.vae_tile_blend = timed
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record(); f(); e.record(); torch.cuda.synchronize()
+        _v.ops.vae_tile_blend = blend
+        total, b = s.elapsed_time(e), sum(x.elapsed_time(y) for x, y in ev)
+        res[name + "_blend"] = dict(launches=len(ev), blend_ms=round(b, 3), pass_ms=round(total, 2), share=round(b / total, 4), crop_bytes=nbytes[0],
+                                    crop_gbps=round(nbytes[0] / (b * 1e-3) / 1e9, 1))
+    print("VAE_TILED_BENCH", json.dumps(res))
+if a.tiled:
+    tiled_report(); sys.exit(0)
 dec = timeit(lambda: vae.decode(lat))
 enc = timeit(lambda: vae.encode(img))
 fd, fe = count(lambda: vae.decode(lat)), count(lambda: vae.encode(img))

@@ -34,4 +34,4 @@ int ug_env_int(const char* name, int dflt) {
 }
 
 extern "C" const char* ug_last_error(void) { return g_err; }
-extern "C" int ug_version(void) { return 220; /* 0.2.2: ug_gelu_erf, the projected CLIP of SD3 (csrc/text.hip) */ }
+extern "C" int ug_version(void) { return 230; /* 0.2.3: ug_vae_tile_blend, AutoencoderKL tiling (csrc/vae.hip) */ }

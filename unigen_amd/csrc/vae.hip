@@ -17,6 +17,7 @@
 //                       registers); rows of 1024 n <= 16384 scores are read once and kept in registers.
 //   ug_nchw_to_nhwc / ug_nhwc_to_nchw   boundary layout changes (+ channel zero-padding to the conv's K granularity, + the latent scale / shift).
 //   ug_vae_sample       DiagonalGaussianDistribution.sample() + (z - shift) * scale.
+//   ug_vae_tile_blend   tiled_decode / tiled_encode: blend_v + blend_h + crop + cat of one tile into the canvas, straight from the raw tiles.
 // Every kernel is a template over the element type: bf16 = product, fp32 = verification twin (the fp32 convolution is a direct loop).
 #include "ug_common.h"
 #include "gemm_epilogue.h"
@@ -453,6 +454,122 @@ __global__ void vae_sample_kernel(const T* __restrict__ mom, int Cp, const T* __
     }
 }
 
+// ---- ug_vae_tile_blend: blend_v + blend_h + crop + cat of AutoencoderKL.tiled_decode / tiled_encode, one launch per tile (the closed form over
+// the four raw tiles is written out in include/unigen_hip.h). HBM-bound: per launch it reads the tile's crop once, the three neighbours' E-wide
+// strips once, and writes the crop once. The decoder's tiles are read as the NHWC conv_out rows they are (Cp = 8: one 16-byte load is one pixel's
+// channels) and written as NCHW straight into the canvas, which replaces ug_nhwc_to_nchw for tiles: 16 + 6 bytes per bf16 pixel, against
+// 16 + 6 (layout change) + 6 + 6 (blend of NCHW tiles) for the other order - fewer bytes, so this is the one built.
+struct BlendP {
+    ug_vae_tile T, U, Lf, UL;
+    void* out; int64_t ob, oc, oy, ox, B, C, h, w;
+    int ev, eh;             // blend extents of this tile pair
+};
+
+template <typename T, int N>
+__device__ __forceinline__ void tile_ld(const ug_vae_tile& t, int64_t b, int64_t c, int64_t y, int64_t x, float* f) {
+    const T* p = (const T*)t.p + b * t.sb + c * t.sc + y * t.sy + x * t.sx;
+    if constexpr (N == 8) ElemT<T>::load8(p, f); else f[0] = ElemT<T>::ld(p);
+}
+// b = rnd(rnd(a * wa) + rnd(b * wb)): torch's `a * (1 - k / e) + b * (k / e)` on tensors of type T (no contraction into an FMA)
+template <typename T, int N>
+__device__ __forceinline__ void tile_lerp(const float* a, float* b, float wa, float wb) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) b[i] = ElemT<T>::rnd(__fadd_rn(ElemT<T>::rnd(__fmul_rn(a[i], wa)), ElemT<T>::rnd(__fmul_rn(b[i], wb))));
+}
+// t[0..N) = out(y, x) for channels [c, c + N)
+template <typename T, int N>
+__device__ __forceinline__ void blend_at(const BlendP& p, int64_t b, int64_t c, int64_t y, int64_t x, float* t) {
+    tile_ld<T, N>(p.T, b, c, y, x, t);
+    const bool vz = y < p.ev, hz = x < p.eh;
+    if (!vz && !hz) return;
+    float wva = 0.f, wvb = 0.f, wha = 0.f, whb = 0.f;
+    if (vz) { const double q = (double)y / (double)p.ev; wvb = (float)q; wva = (float)(1.0 - q); }
+    if (hz) { const double q = (double)x / (double)p.eh; whb = (float)q; wha = (float)(1.0 - q); }
+    float ul[N];
+    if (vz && hz) tile_ld<T, N>(p.UL, b, c, p.UL.H - p.ev + y, p.UL.W - p.eh + x, ul);
+    if (vz) {
+        float u[N];
+        tile_ld<T, N>(p.U, b, c, p.U.H - p.ev + y, x, u);
+        if (hz) tile_lerp<T, N>(ul, u, wha, whb);           // U' : the upper tile was h-blended with its own left neighbour
+        tile_lerp<T, N>(u, t, wva, wvb);
+    }
+    if (hz) {
+        float l[N];
+        tile_ld<T, N>(p.Lf, b, c, y, p.Lf.W - p.eh + x, l);
+        if (vz) tile_lerp<T, N>(ul, l, wva, wvb);           // Lf': the left tile was v-blended with its own upper neighbour
+        tile_lerp<T, N>(l, t, wha, whb);
+    }
+}
+
+// MODE 0: any strides, one element per step. MODE 1: channel-contiguous tiles and canvas (NHWC -> NHWC), 8 channels per step.
+// MODE 2: channel-contiguous tiles, x-contiguous canvas (NHWC -> NCHW): a step is up to 8 consecutive x of one row for up to 8 channels.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void vae_tile_blend_kernel(const BlendP p) {
+    using E = ElemT<T>;
+    T* out = (T*)p.out;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if constexpr (MODE == 0) {
+        const int64_t total = p.B * p.C * p.h * p.w;
+        for (int64_t i = i0; i < total; i += step) {
+            const int64_t x = i % p.w; int64_t r = i / p.w; const int64_t y = r % p.h; r /= p.h; const int64_t c = r % p.C, b = r / p.C;
+            float v;
+            blend_at<T, 1>(p, b, c, y, x, &v);
+            E::st(out + b * p.ob + c * p.oc + y * p.oy + x * p.ox, v);
+        }
+    } else if constexpr (MODE == 1) {
+        const int64_t ng = (p.C + 7) / 8, total = p.B * p.h * p.w * ng;
+        for (int64_t i = i0; i < total; i += step) {
+            const int64_t g = i % ng; int64_t r = i / ng; const int64_t x = r % p.w; r /= p.w; const int64_t y = r % p.h, b = r / p.h;
+            const int64_t c0 = g * 8;
+            T* o = out + b * p.ob + y * p.oy + x * p.ox + c0;
+            if (c0 + 8 <= p.C) {
+                float v[8];
+                blend_at<T, 8>(p, b, c0, y, x, v);
+                E::store8(o, v);
+            } else {
+                for (int64_t c = c0; c < p.C; ++c) { float v; blend_at<T, 1>(p, b, c, y, x, &v); E::st(o + (c - c0), v); }
+            }
+        }
+    } else {
+        const int64_t ng = (p.C + 7) / 8, nu = (p.w + 7) / 8 + 1, total = p.B * ng * p.h * nu;
+        for (int64_t i = i0; i < total; i += step) {
+            const int64_t u = i % nu; int64_t r = i / nu; const int64_t y = r % p.h; r /= p.h; const int64_t g = r % ng, b = r / ng;
+            const int64_t c0 = g * 8;
+            const int nc = (int)(p.C - c0 < 8 ? p.C - c0 : 8);
+            T* o0 = out + b * p.ob + c0 * p.oc + y * p.oy;
+            // step 0 is the scalar head up to the first 16-byte boundary of channel c0's row, steps 1.. are the groups of 8 after it
+            int64_t head = (int64_t)(((16 - ((uintptr_t)o0 & 15)) & 15) / sizeof(T));
+            if (head > p.w) head = p.w;
+            const int64_t xa = u == 0 ? 0 : head + (u - 1) * 8;
+            int64_t xb = u == 0 ? head : xa + 8;
+            if (xb > p.w) xb = p.w;
+            if (xa >= xb) continue;
+            const int n = (int)(xb - xa);
+            float v[8][8];                                  // [channel][pixel]; a pixel's whole group of 8 is read (sx >= C rounded up to 8), nc of it written
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < n) {
+                    float t[8];
+                    blend_at<T, 8>(p, b, c0, y, xa + k, t);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) v[c][k] = t[c];
+                }
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < nc) {
+                    T* o = o0 + c * p.oc + xa;
+                    if (n == 8 && ((uintptr_t)o & 15) == 0) {
+                        E::store8(o, v[c]);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k)
+                            if (k < n) E::st(o + k, v[c][k]);
+                    }
+                }
+        }
+    }
+}
+
 template <typename T>
 int groupnorm_impl(const void* x, const void* gamma, const void* beta, void* out, void* workspace, int64_t workspace_bytes, int64_t B, int64_t HW, int64_t C,
                    int32_t G, float eps, int32_t silu, ug_stream_t stream) {
@@ -550,6 +667,45 @@ int sample_impl(const void* mom, int64_t Cp, const void* noise, void* z, int64_t
     hipLaunchKernelGGL(vae_sample_kernel<T>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)mom, (int)Cp, (const T*)noise,
                        (T*)z, (int)B, (int)L, (int)HW, shift, scale);
     UG_CHECK_LAUNCH("ug_vae_sample");
+    return UG_OK;
+}
+
+template <typename T>
+int tile_blend_impl(const ug_vae_blend_desc* dp, ug_stream_t stream) {
+    UG_REQUIRE(dp != nullptr, UG_ERR_BAD_SHAPE, "ug_vae_tile_blend: null descriptor");
+    const ug_vae_blend_desc& d = *dp;
+    if (d.B == 0 || d.C == 0 || d.h == 0 || d.w == 0) return UG_OK;
+    const int64_t lim = 1ll << 31;
+    UG_REQUIRE(d.T.p && d.out && d.B > 0 && d.C > 0 && d.h > 0 && d.w > 0 && d.E >= 0 && d.E < lim && d.h <= d.T.H && d.w <= d.T.W && d.T.H < lim && d.T.W < lim &&
+               d.B < lim && d.C < lim && d.B * d.C * d.h * d.w < (1ll << 40), UG_ERR_BAD_SHAPE, "ug_vae_tile_blend: bad arguments");
+    const ug_vae_tile* tiles[4] = {&d.T, &d.U, &d.Lf, &d.UL};
+    for (const ug_vae_tile* t : tiles)
+        UG_REQUIRE(!t->p || (t->H > 0 && t->W > 0 && t->H < lim && t->W < lim && t->sb >= 0 && t->sc >= 0 && t->sy >= 0 && t->sx >= 0), UG_ERR_BAD_SHAPE,
+                   "ug_vae_tile_blend: bad tile geometry");
+    UG_REQUIRE(d.ob >= 0 && d.oc >= 0 && d.oy >= 0 && d.ox >= 0, UG_ERR_BAD_SHAPE, "ug_vae_tile_blend: negative canvas stride");
+    UG_REQUIRE((!d.U.p || d.U.W == d.T.W) && (!d.Lf.p || d.Lf.H == d.T.H), UG_ERR_BAD_SHAPE, "ug_vae_tile_blend: the upper tile must have T's width, the left tile T's height");
+    BlendP p;
+    p.T = d.T; p.U = d.U; p.Lf = d.Lf; p.UL = d.UL; p.out = d.out; p.ob = d.ob; p.oc = d.oc; p.oy = d.oy; p.ox = d.ox; p.B = d.B; p.C = d.C; p.h = d.h; p.w = d.w;
+    p.ev = d.U.p ? (int)std::min(std::min(d.U.H, d.T.H), d.E) : 0;
+    p.eh = d.Lf.p ? (int)std::min(std::min(d.Lf.W, d.T.W), d.E) : 0;
+    if (p.ev > 0 && p.eh > 0)
+        UG_REQUIRE(d.UL.p && d.UL.H == d.U.H && d.UL.W == d.Lf.W, UG_ERR_BAD_SHAPE, "ug_vae_tile_blend: the upper-left tile [U.H][Lf.W] is required when both neighbours blend");
+    // the rows of U and the columns of Lf that are read must lie outside what their own blends touched (at most E): a full tile of >= 2 E
+    UG_REQUIRE((p.ev == 0 || d.U.H >= p.ev + d.E) && (p.eh == 0 || d.Lf.W >= p.eh + d.E), UG_ERR_UNSUPPORTED,
+               "ug_vae_tile_blend: the one-pass form needs neighbour tiles of at least 2 E rows / columns (tile_overlap_factor <= 0.5)");
+    // channel-contiguous tiles whose pixels hold whole groups of 8 channels (NHWC rows [..][Cp], Cp = sx >= C rounded up to 8): 16-byte loads
+    bool cvec = true;
+    for (const ug_vae_tile* t : tiles)
+        cvec = cvec && (!t->p || (t->sc == 1 && ug_aligned(t->p, 16) && t->sb % 8 == 0 && t->sy % 8 == 0 && t->sx % 8 == 0 && t->sx >= (d.C + 7) / 8 * 8));
+    const int mode = !cvec ? 0 : (d.oc == 1 && ug_aligned(d.out, 16) && d.ob % 8 == 0 && d.oy % 8 == 0 && d.ox % 8 == 0) ? 1 : d.ox == 1 ? 2 : 0;
+    const int64_t ng = (d.C + 7) / 8;
+    const int64_t total = mode == 0 ? d.B * d.C * d.h * d.w : mode == 1 ? d.B * d.h * d.w * ng : d.B * ng * d.h * ((d.w + 7) / 8 + 1);
+    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 8192));
+    const hipStream_t s = (hipStream_t)stream;
+    if (mode == 0) hipLaunchKernelGGL((vae_tile_blend_kernel<T, 0>), grid, dim3(256), 0, s, p);
+    else if (mode == 1) hipLaunchKernelGGL((vae_tile_blend_kernel<T, 1>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((vae_tile_blend_kernel<T, 2>), grid, dim3(256), 0, s, p);
+    UG_CHECK_LAUNCH("ug_vae_tile_blend");
     return UG_OK;
 }
 
@@ -668,3 +824,5 @@ extern "C" int ug_vae_sample(const void* mom, int64_t Cp, const void* noise, voi
 extern "C" int ug_vae_sample_f32(const void* mom, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale, ug_stream_t s) {
     return sample_impl<float>(mom, Cp, noise, z, B, L, HW, shift, scale, s);
 }
+extern "C" int ug_vae_tile_blend(const ug_vae_blend_desc* d, ug_stream_t s) { return tile_blend_impl<bf16_t>(d, s); }
+extern "C" int ug_vae_tile_blend_f32(const ug_vae_blend_desc* d, ug_stream_t s) { return tile_blend_impl<float>(d, s); }

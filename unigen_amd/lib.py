@@ -50,6 +50,19 @@ class ConvDesc(C.Structure):
                 ("Cout", i64), ("KH", i32), ("KW", i32), ("stride", i32), ("pad_t", i32), ("pad_l", i32), ("up", i32), ("zero_page", vp), ("zero_page_bytes", i64)]
 
 
+class VaeTile(C.Structure):
+    """Mirror of struct ug_vae_tile (include/unigen_hip.h): element strides of a logical [B][C][H][W] tile."""
+
+    _fields_ = [("p", vp), ("H", i64), ("W", i64), ("sb", i64), ("sc", i64), ("sy", i64), ("sx", i64)]
+
+
+class VaeBlendDesc(C.Structure):
+    """Mirror of struct ug_vae_blend_desc (include/unigen_hip.h)."""
+
+    _fields_ = [("T", VaeTile), ("U", VaeTile), ("Lf", VaeTile), ("UL", VaeTile), ("out", vp), ("ob", i64), ("oc", i64), ("oy", i64), ("ox", i64),
+                ("B", i64), ("C", i64), ("h", i64), ("w", i64), ("E", i64)]
+
+
 UG_DT_BF16, UG_DT_F32 = 0, 1
 UG_OPTIM_CHUNK, UG_ADAMW_MAX_GROUPS = 65536, 32
 
@@ -106,6 +119,7 @@ SIGNATURES = {
     "ug_nchw_to_nhwc": (i32, [vp, vp, i64, i64, i64, i64, f32, f32, vp]),
     "ug_nhwc_to_nchw": (i32, [vp, vp, i64, i64, i64, i64, vp]),
     "ug_vae_sample": (i32, [vp, i64, vp, vp, i64, i64, i64, f32, f32, vp]),
+    "ug_vae_tile_blend": (i32, [C.POINTER(VaeBlendDesc), vp]),
     "ug_probe_mfma_bf16": (i32, [i32, i64, i64, vp, C.POINTER(C.c_double), vp]),
     "ug_pack_latents": (i32, [vp, vp, i64, i64, i64, i64, vp]),
     "ug_unpack_latents": (i32, [vp, vp, i64, i64, i64, i64, vp]),
@@ -205,7 +219,8 @@ _F32_TWINS = {"ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32":
               "ug_moe_gate_top2_f32": "ug_moe_gate_top2", "ug_moe_gate_topk_f32": "ug_moe_gate_topk", "ug_moe_combine_topk_f32": "ug_moe_combine_topk",
               "ug_pack_latents_f32": "ug_pack_latents", "ug_unpack_latents_f32": "ug_unpack_latents",
               "ug_conv2d_nhwc_f32": "ug_conv2d_nhwc", "ug_groupnorm_nhwc_f32": "ug_groupnorm_nhwc", "ug_softmax_rows_f32": "ug_softmax_rows",
-              "ug_nchw_to_nhwc_f32": "ug_nchw_to_nhwc", "ug_nhwc_to_nchw_f32": "ug_nhwc_to_nchw", "ug_vae_sample_f32": "ug_vae_sample"}
+              "ug_nchw_to_nhwc_f32": "ug_nchw_to_nhwc", "ug_nhwc_to_nchw_f32": "ug_nhwc_to_nchw", "ug_vae_sample_f32": "ug_vae_sample",
+              "ug_vae_tile_blend_f32": "ug_vae_tile_blend"}
 for _twin, _base in _F32_TWINS.items():
     SIGNATURES[_twin] = SIGNATURES[_base]
 

@@ -615,6 +615,43 @@ def vae_sample(moments: torch.Tensor, noise: torch.Tensor, *, B: int, latent: in
     return z
 
 
+def _chk_view(t: torch.Tensor, name: str, dt) -> None:
+    """a strided [B, C, H, W] view handed over with its element strides: any layout, but on the device, of the call's dtype, and no stride negative"""
+    if not t.is_cuda:
+        raise L.UniGenHipError(f"{name}: expected a GPU tensor (unigen_amd has no CPU path)")
+    if t.dtype != dt:
+        raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+    if t.dim() != 4 or min(t.stride()) < 0:
+        raise ValueError(f"{name}: expected a [B, C, H, W] view with non-negative strides, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
+def _vae_tile(t: Optional[torch.Tensor], dt, B: int, Cc: int) -> L.VaeTile:
+    v = L.VaeTile()
+    if t is not None:
+        _chk_view(t, "tile", dt)
+        assert t.dim() == 4 and t.shape[0] == B and t.shape[1] == Cc, (t.shape, B, Cc)
+        v.p, v.H, v.W = t.data_ptr(), t.shape[2], t.shape[3]
+        v.sb, v.sc, v.sy, v.sx = t.stride()
+    return v
+
+
+def vae_tile_blend(tile: torch.Tensor, upper: Optional[torch.Tensor], left: Optional[torch.Tensor], upper_left: Optional[torch.Tensor], out: torch.Tensor,
+                   extent: int) -> torch.Tensor:
+    """One tile of AutoencoderKL.tiled_decode / tiled_encode into its canvas region (ug_vae_tile_blend: blend_v, blend_h, crop and cat in one pass).
+    Every tensor is a logical [B, C, H, W] VIEW of any strides (NHWC rows: `rows.view(B, H, W, Cp).permute(0, 3, 1, 2)[:, :C]`); `out` is the view of
+    the canvas region [B, C, h, w] that receives rows [0, h) x columns [0, w) of the blended tile. Neighbours are the RAW tiles, or None."""
+    dt = _act(tile, "tile")
+    _chk_view(out, "out", dt)
+    B, Cc, h, w = out.shape
+    d = L.VaeBlendDesc()
+    d.T, d.U, d.Lf, d.UL = (_vae_tile(t, dt, B, Cc) for t in (tile, upper, left, upper_left))
+    d.out = out.data_ptr()
+    d.ob, d.oc, d.oy, d.ox = out.stride()
+    d.B, d.C, d.h, d.w, d.E = B, Cc, h, w, int(extent)
+    L.check(_fn("ug_vae_tile_blend", dt)(C.byref(d), _stream()), "ug_vae_tile_blend")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # backward-pass entry points (include/unigen_hip.h "Backward pass of the control-module training step")
 # ---------------------------------------------------------------------------------------------------------------------

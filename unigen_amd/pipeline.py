@@ -189,7 +189,34 @@ class _LoraLoaderMixin:
             tr.unload_lora_weights(a)
 
 
-class UniGenFLUXPipeline(_LoraLoaderMixin):
+class _VaeSwitchMixin:
+    """diffusers' pipeline-level VAE switches: forwarded to the attached `self.vae` (unigen_amd.vae.AutoencoderKL or any object with the same names)."""
+
+    def _vae_switch(self, name: str):
+        vae = getattr(self, "vae", None)
+        if vae is None:
+            raise RuntimeError(f"{type(self).__name__}.{name.replace('_', '_vae_', 1)}(): no VAE is attached: set `pipe.vae` (AutoencoderKL surface) first")
+        fn = getattr(vae, name, None)
+        if fn is None:
+            raise RuntimeError(f"the attached VAE ({type(vae).__name__}) has no {name}()")
+        fn()
+
+    def enable_vae_tiling(self) -> None:
+        """Decode / encode large images tile by tile (AutoencoderKL.enable_tiling)."""
+        self._vae_switch("enable_tiling")
+
+    def disable_vae_tiling(self) -> None:
+        self._vae_switch("disable_tiling")
+
+    def enable_vae_slicing(self) -> None:
+        """Run the VAE one sample at a time (AutoencoderKL.enable_slicing)."""
+        self._vae_switch("enable_slicing")
+
+    def disable_vae_slicing(self) -> None:
+        self._vae_switch("disable_slicing")
+
+
+class UniGenFLUXPipeline(_LoraLoaderMixin, _VaeSwitchMixin):
     """Call-surface twin of the reference `UniGenFLUXPipeline(FluxPipeline)`: the denoise loop runs here; text encoding and the VAE are
     delegated to attributes the caller attaches (`encode_prompt`, `vae`, `image_processor`), with the reference's keyword arguments."""
 
@@ -445,7 +472,7 @@ def sd3_denoise_loop(transformer, *, latents: torch.Tensor, control_latents: tor
     return latents
 
 
-class UniGenSD3Pipeline(_LoraLoaderMixin):
+class UniGenSD3Pipeline(_LoraLoaderMixin, _VaeSwitchMixin):
     """Call-surface twin of the reference `UniGenSD3Pipeline`: the denoise loop runs here, prompts are encoded by the attached native text
     encoders (unigen_amd.text) or by an attached `encode_prompt` callable; the VAE is delegated as in UniGenFLUXPipeline."""
 

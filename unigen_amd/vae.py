@@ -11,6 +11,10 @@ Nothing here computes in torch: activations are NHWC 2-D tensors [B*H*W, C] and 
 ug_conv2d_nhwc (implicit GEMM on MFMA; nearest-2x upsampling and Downsample2D's one-sided padding folded into its gather), ug_groupnorm_nhwc
 (+ SiLU), ug_gemm_bf16 (1x1 shortcuts, attention projections, scores, P.V), ug_softmax_rows, ug_vae_sample, ug_nchw_to_nhwc / ug_nhwc_to_nchw.
 fp32 parameters select the verification twins, as for the transformer.
+
+Tiling and slicing (diffusers 0.32.2 `enable_tiling` / `enable_slicing` / `tiled_decode` / `tiled_encode`, restated; parity unpinned like the rest): off by
+default, and then nothing below the routing functions changes. On, an input larger than the tile on either side is cut into overlapping tiles, each run through
+the untiled code on its own (torch only slices and concatenates), and ug_vae_tile_blend writes every tile's blended, cropped region into the canvas in one pass.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ from .engine import _Holder, _register, _Workspace
 
 BF = torch.bfloat16
 FLUX_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=16, block_out_channels=(128, 256, 512, 512), layers_per_block=2, norm_num_groups=32,
-                       scaling_factor=0.3611, shift_factor=0.1159, use_quant_conv=False, use_post_quant_conv=False, mid_block_add_attention=True)
+                       scaling_factor=0.3611, shift_factor=0.1159, use_quant_conv=False, use_post_quant_conv=False, mid_block_add_attention=True, sample_size=1024)
 
 
 def _pad_to(n: int, q: int) -> int:
@@ -125,6 +129,12 @@ class AutoencoderKL(nn.Module):
         self._packed: Dict[str, Tuple] = {}
         for name, shape in vae_param_shapes(self.config).items():
             _register(self, name, shape, device, dtype)
+        # diffusers' tiling / slicing switches: plain attributes, off by default (tiled_decode / tiled_encode below)
+        self.use_slicing = False
+        self.use_tiling = False
+        self.tile_sample_min_size = self.config.sample_size
+        self.tile_latent_min_size = int(self.config.sample_size / (2 ** (len(self.config.block_out_channels) - 1)))
+        self.tile_overlap_factor = 0.25
 
     # ------------------------------------------------------------------ construction ---------------------------------
     @classmethod
@@ -293,11 +303,22 @@ class AutoencoderKL(nn.Module):
         return m, B, H, W
 
     def encode(self, x: torch.Tensor, return_dict: bool = True):
+        if self.use_slicing and x.shape[0] > 1:          # diffusers: one sample at a time through the same route, results concatenated
+            parts = [self._encode_route(xs) for xs in x.split(1)]
+            m, B, H, W = torch.cat([q[0] for q in parts]), x.shape[0], parts[0][2], parts[0][3]
+        else:
+            m, B, H, W = self._encode_route(x)
+        dist = DiagonalGaussianDistribution(m, B, self.config.latent_channels, H, W)
+        return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
+
+    def _encode_route(self, x: torch.Tensor):
+        """-> (moments [B*H*W, Cp] owned by the caller, B, H, W): tiled when tiling is on and the image exceeds the tile on either side."""
+        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_size or x.shape[-2] > self.tile_sample_min_size):
+            return self._tiled_moments(x)
         m, B, H, W = self._encode_moments(x)
         # the moments live in a reused workspace: the distribution owns a copy (2 * latent channels at latent resolution - tiny), so a second
         # encode() before .sample() / .mode() cannot overwrite it (diffusers semantics)
-        dist = DiagonalGaussianDistribution(m.clone(), B, self.config.latent_channels, H, W)
-        return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
+        return m.clone(), B, H, W
 
     @torch.no_grad()
     def encode_scaled(self, image: torch.Tensor, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -306,6 +327,11 @@ class AutoencoderKL(nn.Module):
 
     @torch.no_grad()
     def _decode(self, z: torch.Tensor, div: float, add: float) -> torch.Tensor:
+        y, B, H, W = self._decode_rows(z, div, add, "d_out")
+        return ops.nhwc_to_nchw(y, B, self.config.out_channels, H, W)
+
+    def _decode_rows(self, z: torch.Tensor, div: float, add: float, out_tag: str):
+        """-> (conv_out rows [B*H*W, Cout_p] in the workspace buffer `out_tag`, B, H, W at image resolution)."""
         cfg, dt = self.config, self.dtype
         B, Lc, H, W = z.shape
         if Lc != cfg.latent_channels:
@@ -322,13 +348,144 @@ class AutoencoderKL(nn.Module):
             if i < n - 1:           # Upsample2D: nearest 2x folded into the convolution's gather
                 x, H, W = self._conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", x, B, H, W, "d_us", up=1)
         x = self._gn("decoder.conv_norm_out", x, B, H * W, "d_no", True)
-        y, _, _ = self._conv("decoder.conv_out", x, B, H, W, "d_out")
-        return ops.nhwc_to_nchw(y, B, cfg.out_channels, H, W)
+        y, _, _ = self._conv("decoder.conv_out", x, B, H, W, out_tag)
+        return y, B, H, W
+
+    def _decode_route(self, z: torch.Tensor, div: float, add: float) -> torch.Tensor:
+        if self.use_slicing and z.shape[0] > 1:          # diffusers: one sample at a time through the same route, results concatenated
+            return torch.cat([self._decode_route(zs, div, add) for zs in z.split(1)])
+        if self.use_tiling and (z.shape[-1] > self.tile_latent_min_size or z.shape[-2] > self.tile_latent_min_size):
+            return self._tiled_decode(z, div, add)
+        return self._decode(z, div, add)
 
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
-        img = self._decode(z, 0.0, 0.0)
+        img = self._decode_route(z, 0.0, 0.0)
         return SimpleNamespace(sample=img) if return_dict else (img,)
 
     def decode_scaled(self, latents: torch.Tensor) -> torch.Tensor:
         """src/UniGenPipeline.py:797-798 in one go: vae.decode(latents / scaling_factor + shift_factor)."""
-        return self._decode(latents, self.config.scaling_factor, self.config.shift_factor)
+        return self._decode_route(latents, self.config.scaling_factor, self.config.shift_factor)
+
+    # ------------------------------------------------------------------ tiling / slicing (diffusers 0.32.2 names) -------
+    def enable_tiling(self, use_tiling: bool = True) -> None:
+        """Decode / encode images larger than the tile size as overlapping tiles blended at the seams: the mid-block attention's [HW, HW] scratch
+        and every full-resolution activation stay those of ONE tile (tile_sample_min_size / tile_latent_min_size / tile_overlap_factor)."""
+        self.use_tiling = use_tiling
+
+    def disable_tiling(self) -> None:
+        self.enable_tiling(False)
+
+    def enable_slicing(self) -> None:
+        """Run a batch one sample at a time (B > 1): peak scratch is that of one sample."""
+        self.use_slicing = True
+
+    def disable_slicing(self) -> None:
+        self.use_slicing = False
+
+    def _tile_plan(self, H: int, W: int, tile: int, out_tile: int, down: bool):
+        """Tile starts, blend extent and crop of tiled_decode (tile = tile_latent_min_size, sizes grow by the scale factor) or tiled_encode
+        (tile = tile_sample_min_size, sizes shrink by it), checked BEFORE any launch: the overlap factor, the sizes the one-pass blend needs, and
+        every tile's mid-block attention shape. -> (stride, extent, crop, scale)."""
+        f = self.tile_overlap_factor
+        if not 0.0 <= f <= 0.5:
+            raise ValueError(f"tile_overlap_factor must be within [0, 0.5] (got {f}): ug_vae_tile_blend evaluates the blends of a tile and its three "
+                             "neighbours in one pass from the raw tiles, which needs the overlap of a tile with its neighbour on one side not to reach "
+                             "the overlap on the other side (a tile of at least twice the blend extent)")
+        scale = 2 ** (len(self.config.block_out_channels) - 1)
+        stride, extent = int(tile * (1 - f)), int(out_tile * f)
+        crop = out_tile - extent
+        to_out = (lambda n: n // scale) if down else (lambda n: n * scale)
+        if stride < 1 or crop < 1 or (down and (tile % scale or stride % scale)):
+            raise ValueError(f"tile size {tile} with tile_overlap_factor {f} gives no usable tile grid (stride {stride}, crop {crop}, scale factor {scale})")
+        if to_out(tile) < 2 * extent or to_out(stride) < extent:
+            raise ValueError(f"tile_sample_min_size {self.tile_sample_min_size} and tile_latent_min_size {self.tile_latent_min_size} do not fit each other: a tile's "
+                             f"output ({to_out(tile)}) must be at least twice the blend extent ({extent}) and its stride ({to_out(stride)}) at least the extent")
+        if self.config.mid_block_add_attention:
+            for th in [min(tile, H - i) for i in range(0, H, stride)]:           # row-major: the first tile that breaks the rule is the one named
+                for tw in [min(tile, W - j) for j in range(0, W, stride)]:
+                    hw = (th // scale) * (tw // scale) if down else th * tw
+                    if hw % 64 != 0:
+                        raise L.UniGenHipError(f"VAE mid-block attention needs H*W at the latent resolution to be a multiple of 64 (got {hw})")
+        return stride, extent, crop, scale
+
+    @staticmethod
+    def _nchw_view(rows: torch.Tensor, B: int, H: int, W: int, Cc: int) -> torch.Tensor:
+        """NHWC rows [B*H*W, Cp] as the logical [B, C, H, W] view ops.vae_tile_blend takes (no copy)."""
+        return rows.view(B, H, W, rows.shape[1]).permute(0, 3, 1, 2)[:, :Cc]
+
+    @staticmethod
+    def _blend_tiles(canvas: torch.Tensor, grid, extent: int, crop: int) -> None:
+        """canvas: logical [B, C, H, W] view; grid[i][j]: raw tile (i, j) as such a view. One ug_vae_tile_blend launch per tile."""
+        oy = 0
+        for i, row in enumerate(grid):
+            ox = 0
+            h = min(row[0].shape[2], crop)
+            for j, t in enumerate(row):
+                w = min(t.shape[3], crop)
+                up, left = (grid[i - 1][j] if i else None), (row[j - 1] if j else None)
+                ops.vae_tile_blend(t, up, left, grid[i - 1][j - 1] if i and j else None, canvas[:, :, oy:oy + h, ox:ox + w], extent)
+                ox += w
+            oy += h
+
+    @staticmethod
+    def _canvas_size(n: int, tile: int, stride: int, out_of, crop: int) -> int:
+        return sum(min(out_of(min(tile, n - i)), crop) for i in range(0, n, stride))
+
+    @torch.no_grad()
+    def _tiled_decode(self, z: torch.Tensor, div: float, add: float) -> torch.Tensor:
+        cfg = self.config
+        B, Lc, H, W = z.shape
+        if Lc != cfg.latent_channels:
+            raise ValueError(f"latents must be [B, {cfg.latent_channels}, h, w]")
+        tile = self.tile_latent_min_size
+        stride, extent, crop, scale = self._tile_plan(H, W, tile, self.tile_sample_min_size, down=False)
+        up = lambda n: n * scale
+        canvas = torch.empty(B, cfg.out_channels, self._canvas_size(H, tile, stride, up, crop), self._canvas_size(W, tile, stride, up, crop), device=self.device, dtype=self.dtype)
+        # a tile's conv_out rows stay NHWC in a workspace buffer of their own (tag = row parity x column): only the previous row of tiles and the
+        # current one are alive, and ug_vae_tile_blend writes NCHW into the canvas straight from them (it takes over ug_nhwc_to_nchw for tiles)
+        prev, oy = None, 0
+        for ri, i in enumerate(range(0, H, stride)):
+            cur, ox = [], 0
+            for cj, j in enumerate(range(0, W, stride)):
+                y, _, th, tw = self._decode_rows(z[:, :, i:i + tile, j:j + tile], div, add, f"td_{ri % 2}_{cj}")
+                t = self._nchw_view(y, B, th, tw, cfg.out_channels)
+                cur.append(t)
+                h, w = min(th, crop), min(tw, crop)
+                ops.vae_tile_blend(t, prev[cj] if prev else None, cur[cj - 1] if cj else None, prev[cj - 1] if prev and cj else None,
+                                   canvas[:, :, oy:oy + h, ox:ox + w], extent)
+                ox += w
+            prev, oy = cur, oy + h
+        return canvas
+
+    def tiled_decode(self, z: torch.Tensor, return_dict: bool = True):
+        """diffusers AutoencoderKL.tiled_decode: every tile decoded on its own, seams blended over int(tile_sample_min_size * tile_overlap_factor) pixels."""
+        img = self._tiled_decode(z, 0.0, 0.0)
+        return SimpleNamespace(sample=img) if return_dict else (img,)
+
+    @torch.no_grad()
+    def _tiled_moments(self, x: torch.Tensor):
+        cfg = self.config
+        B, Cc, H, W = x.shape
+        tile, scale = self.tile_sample_min_size, 2 ** (len(cfg.block_out_channels) - 1)
+        if Cc != cfg.in_channels or H % scale or W % scale:
+            raise ValueError(f"image must be [B, {cfg.in_channels}, H, W] with H, W multiples of {scale}")
+        stride, extent, crop, _ = self._tile_plan(H, W, tile, self.tile_latent_min_size, down=True)
+        down = lambda n: n // scale
+        Hl, Wl = self._canvas_size(H, tile, stride, down, crop), self._canvas_size(W, tile, stride, down, crop)
+        canvas, grid = None, []
+        for i in range(0, H, stride):
+            row = []
+            for j in range(0, W, stride):
+                m, _, th, tw = self._encode_moments(x[:, :, i:i + tile, j:j + tile])     # after quant_conv where the config has one
+                if canvas is None:
+                    canvas = torch.empty(B * Hl * Wl, m.shape[1], device=m.device, dtype=m.dtype)
+                row.append(self._nchw_view(m.clone(), B, th, tw, m.shape[1]))           # the moments sit in a reused workspace: keep a copy (tiny)
+            grid.append(row)
+        self._blend_tiles(self._nchw_view(canvas, B, Hl, Wl, canvas.shape[1]), grid, extent, crop)
+        return canvas, B, Hl, Wl
+
+    def tiled_encode(self, x: torch.Tensor, return_dict: bool = True):
+        """diffusers AutoencoderKL.tiled_encode: every tile encoded on its own, the MOMENTS blended over int(tile_latent_min_size * tile_overlap_factor)."""
+        m, B, H, W = self._tiled_moments(x)
+        dist = DiagonalGaussianDistribution(m, B, self.config.latent_channels, H, W)
+        return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
