@@ -91,9 +91,11 @@ __global__ __launch_bounds__(512, DH == 128 ? 2 : 4) void flash_attn_kernel(
     const int qd = nwg >> 3, rm = nwg & 7;
     const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
     const int logical = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + kk;
-    const int qt = logical % nQ;
-    const int bh = logical / nQ;
-    const int head = bh % heads, b = bh / heads;
+    // The divisions run on the VALU, so hipcc takes their (wave-uniform) results for per-lane values: at head width 64 the (batch, head) base pointers
+    // derived from them were 64-bit VGPR pairs, live through the loop, that the 128-register budget pushed to scratch (10-12 VGPRs, one reload per tile).
+    const int qt = DH == 64 ? __builtin_amdgcn_readfirstlane(logical % nQ) : logical % nQ;
+    const int bh = DH == 64 ? __builtin_amdgcn_readfirstlane(logical / nQ) : logical / nQ;
+    const int head = DH == 64 ? __builtin_amdgcn_readfirstlane(bh % heads) : bh % heads, b = DH == 64 ? __builtin_amdgcn_readfirstlane(bh / heads) : bh / heads;
 
     const bf16_t* Qb = q + (int64_t)b * q_bs + head * DH;
     const bf16_t* Kb = k + (int64_t)b * k_bs + head * DH;

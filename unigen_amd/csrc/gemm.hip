@@ -167,7 +167,7 @@ constexpr int KT_BYTES = 4 * HT_BYTES;
 constexpr int LDS256_BYTES = 2 * KT_BYTES;
 constexpr int SLOT_A0 = 0, SLOT_B0 = HT_BYTES, SLOT_B1 = 2 * HT_BYTES, SLOT_A1 = 3 * HT_BYTES;
 #ifndef UG_EPI_RES_PREFETCH
-#define UG_EPI_RES_PREFETCH 8          /* row-groups of residual chunks in flight in the full-tile epilogue: all 8 (2 = rounds 1-2). Two-library A/B: 4: +-0.5 %, 8: +0.5...+1.1 % on the R + gate * v shapes; no spills (252 registers) */
+#define UG_EPI_RES_PREFETCH 8          /* row-groups of residual chunks in flight in the full-tile epilogue: all 8 (2 = rounds 1-2). Two-library A/B: 4: +-0.5 %, 8: +0.5...+1.1 % on the R + gate * v shapes; no spills (242-254 registers on the residual instantiations: tests/code_object_contracts.py) */
 #endif
 #ifdef UG_DIAG_PHASES          /* tools/gemm_phase_stamps.py: per-segment stamps of one steady K-tile (implies UG_DIAG_STAMPS) */
 #define UG_DIAG_STAMPS
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
     // (Round 3's cross-tile stream - the last two K-tiles of a tile staging the next tile's first two, UG_GEMM_XTILE - measured neutral
     // (profiles/r03o_*: -0.7...+0.9 % per shape) and lived on in the probe build until round 5, when the buffer-form DMAs replaced the per-lane pointers it
     // swapped; removed from the source. Rebuilt on the round-5 loop in buffer form the same round - the next tile's A0 / B0 pieces of K-tiles 0 and 1
-    // issued by the last two K-tiles of this one, sources selected by value, no spills, 242-250 VGPRs, bit-identical: -0.6...+0.2 % per shape and
+    // issued by the last two K-tiles of this one, sources selected by value, no spills and 242-250 VGPRs as compiled then (the shipped kernel's rows: tests/code_object_contracts.py), bit-identical: -0.6...+0.2 % per shape and
     // -0.3 % images/s interleaved on one box; with the epilogue's bias / gate loads hoisted ahead of those DMAs as well, 16-40 B/lane of scratch and
     // -2 %: profiles/r05_gemm_loop_ab.log steps 8 and 9. Issuing the first K-tiles' DMAs earlier does not buy back the 3-5 us a tile waits for them
     // (profiles/r05x_gemm_tile_stamps.log); what they queue behind there was not identified.)
@@ -680,7 +680,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
 #pragma unroll
                         for (int b = 0; b < 2; ++b) acc[i][j][a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
             for (int sl = 0; sl < nslices; ++sl) {
-                const float* sp = slabs + ((size_t)rem * nslices + sl) * 65536;
+                // This lane's slab pointer is made opaque once per slice, so each chunk address below is that pointer + a constant: left to hipcc, the 32
+                // chunk offsets were hoisted out of this loop (64-bit each: 64 VGPRs beside the 128 accumulators and the 32 load registers) and 3-30 VGPRs
+                // of the epilogue's lane constants went to scratch around it. (Not in the fp32-output instantiation: it fitted, and stays as compiled.)
+                const float* sp = slabs + ((size_t)rem * nslices + sl) * 65536 + tid_e * 4;
+                if constexpr (EPI != UG_EPI_F32) asm volatile("" : "+v"(sp));
+                // The loads and their s_waitcnt are SEPARATE asm statements: hipcc does not count these loads, so a scratch access it placed between them would wait on a counter that lies - tests/test_code_object_cpu.py (no scratch in this kernel) is what keeps the window empty.
                 // system-scope loads, 8 in flight per lane (the accumulators leave no room for a whole slab's 32), same slice and element order as before
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -691,7 +696,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
                         for (int a = 0; a < 4; ++a)
 #pragma unroll
                             for (int b = 0; b < 2; ++b)
-                                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(t[a][b]) : "v"(sp + ((((i * 2 + j) * 4 + a) * 2 + b) * 512 + tid_e) * 4) : "memory");
+                                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(t[a][b]) : "v"(sp + (((i * 2 + j) * 4 + a) * 2 + b) * 512 * 4) : "memory");
                         asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
 #pragma unroll
                         for (int a = 0; a < 4; ++a)
