@@ -144,6 +144,19 @@ int ug_flash_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_batch_strid
                       int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
                       float softmax_scale, ug_stream_t stream);
 
+/* ug_flash_attn_fwd at head width 512: the single-head mid-block attention of AutoencoderKL (diffusers Attention(heads = 1, dim_head = 512);
+ * unigen_amd/vae.py), without the [Lq, Lkv] score matrix in memory. Same arguments, strides in elements, same stride and alignment rules
+ * (q / k / v row and batch strides multiples of 8, bases 16-byte aligned; o: multiples of 4, 8-byte aligned); any Lq, Lkv >= 1. dh must be 512
+ * (UG_ERR_UNSUPPORTED otherwise; 64 and 128 stay with ug_flash_attn_fwd), K / V row strides within (0, 2^24), softmax_scale > 0.
+ * bf16 in / out, fp32 accumulation, online softmax, P rounded to bf16 as the P.V operand. No workspace, no atomics, no state between launches:
+ * two launches give the same bits, and the launch can be captured in a graph (128 KiB of dynamic LDS; one workgroup = 128 query rows). */
+int ug_flash_attn_fwd_wide(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                           const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                           const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                           void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                           int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                           float softmax_scale, ug_stream_t stream);
+
 /* Sinusoidal Timesteps(256, flip_sin_to_cos=True, downscale_freq_shift=0): out[b] = [cos(t f) | sin(t f)] as bf16.
  * (diffusers embeddings.get_timestep_embedding; called inside time_text_embed, UniGenTransformer.py:1222). */
 int ug_timestep_embed(const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t stream);
@@ -358,6 +371,13 @@ int ug_flash_attn_fwd_f32(const void* q, int64_t q_row_stride, int64_t q_batch_s
                           void* o, int64_t o_row_stride, int64_t o_batch_stride,
                           int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
                           float softmax_scale, ug_stream_t stream);
+/* fp32 twin of ug_flash_attn_fwd_wide (dh = 512 only): plain FMA loops, exact online softmax; strides multiples of 4 elements, bases 16-byte aligned */
+int ug_flash_attn_fwd_wide_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                               const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                               const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                               void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                               int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                               float softmax_scale, ug_stream_t stream);
 int ug_timestep_embed_f32(const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t stream);
 int ug_euler_step_f32(void* x, const void* v, float dt, int64_t n, ug_stream_t stream);
 int ug_cfg_combine_f32(const void* uncond, const void* text, float guidance_scale, void* out, int64_t n, ug_stream_t stream);

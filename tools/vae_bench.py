@@ -1,16 +1,77 @@
 """AutoencoderKL (FLUX geometry) at 1024^2: decode and encode latency, per-call conv shapes. usage: python tools/vae_bench.py [--size 1024] [--batch 1]
 --tiled [--size 2048] [--rounds 5]: untiled against tiled (enable_tiling(), default tile sizes 1024 / 128 / 0.25) decode and encode of ONE process,
 interleaved round by round (untiled decode, tiled decode, untiled encode, tiled encode, again ...), every timing a host clock around calls that end in a
-device synchronise; then one instrumented pass with a device-event pair around every ug_vae_tile_blend launch for the blend's share of the tiled time."""
+device synchronise; then one instrumented pass with a device-event pair around every ug_vae_tile_blend launch for the blend's share of the tiled time.
+--flash [--rounds 5] [--cells 1024x1,1024x4,2048x1,4096x1]: the default attention route against enable_flash_attention() in ONE process, per cell (size x
+batch) decode and encode interleaved round by round (default decode, flash decode, default encode, flash encode, again ...), median ms of host clocks around
+calls that end in a device synchronise, and torch.cuda.max_memory_allocated of one call of each route on an empty workspace; 4096 runs the flash route only
+(the default route's [HW, HW] scratch, about 275 GB, cannot be allocated). Then ug_flash_attn_fwd_wide alone at each cell's token count: device events
+around 3 launches after 2 warm ones, TFLOP/s of 4 B N^2 512. One line of JSON per cell (profiles/vae_flash_bench.log)."""
 import argparse, os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from unigen_amd.vae import AutoencoderKL
 
 ap = argparse.ArgumentParser(); ap.add_argument("--size", type=int, default=None); ap.add_argument("--batch", type=int, default=1)
-ap.add_argument("--tiled", action="store_true"); ap.add_argument("--rounds", type=int, default=5); a = ap.parse_args()
+ap.add_argument("--tiled", action="store_true"); ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--flash", action="store_true"); ap.add_argument("--cells", default="1024x1,1024x4,2048x1,4096x1"); a = ap.parse_args()
 a.size = a.size or (2048 if a.tiled else 1024)
 dev = torch.device("cuda:0")
+def flash_report():
+    import statistics
+    from unigen_amd import ops
+    vae = AutoencoderKL(device=dev, dtype=torch.bfloat16).init_synthetic_(seed=0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rel = lambda x, y: float((x.float() - y.float()).norm() / y.float().norm())
+    for cell in a.cells.split(","):
+        size, B = (int(x) for x in cell.split("x"))
+        routes = ("flash",) if size >= 4096 else ("default", "flash")
+        img = torch.randn(B, 3, size, size, generator=g, device=dev).to(torch.bfloat16)
+        lat = torch.randn(B, 16, size // 8, size // 8, generator=g, device=dev).to(torch.bfloat16)
+        def call(route, op):
+            vae.use_flash_attention = route == "flash"
+            return vae.decode(lat).sample if op == "decode" else vae.encode(img).latent_dist._m
+        res, outs = dict(size=size, batch=B, tokens=(size // 8) ** 2, rounds=a.rounds), {}
+        for op in ("decode", "encode"):
+            for route in routes:                           # peak memory of ONE call on an empty workspace (inputs and weights included); also the warm-up
+                vae._ws.clear(); torch.cuda.synchronize(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                outs[route, op] = call(route, op).clone(); torch.cuda.synchronize()
+                res[f"{op}_{route}_peak_gb"] = round(torch.cuda.max_memory_allocated() / 1e9, 2)
+                res[f"{op}_{route}_peak_over_resident_gb"] = round((torch.cuda.max_memory_allocated() - base) / 1e9, 2)
+        for op in ("decode", "encode"):
+            for route in routes:
+                call(route, op)
+        torch.cuda.synchronize()
+        ms = {(r_, op): [] for r_ in routes for op in ("decode", "encode")}
+        for _ in range(a.rounds):
+            for op in ("decode", "encode"):
+                for route in routes:
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    call(route, op)
+                    torch.cuda.synchronize(); ms[route, op].append((time.perf_counter() - t0) * 1e3)
+        for (route, op), v in ms.items():
+            res[f"{op}_{route}_ms"] = dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2))
+        if "default" in routes:
+            res["decode_flash_vs_default_relL2"] = round(rel(outs["flash", "decode"], outs["default", "decode"]), 5)
+            res["encode_flash_vs_default_relL2"] = round(rel(outs["flash", "encode"], outs["default", "encode"]), 5)
+        # the kernel alone, on N(0, 1) operands at the mid-block's shape: [B*N, 512] q, k, v, one launch over the batch
+        vae._ws.clear(); outs.clear(); torch.cuda.empty_cache()
+        N = (size // 8) ** 2
+        q, k, v = (torch.randn(B * N, 512, generator=g, device=dev).to(torch.bfloat16) for _ in range(3))
+        o, st = torch.empty_like(q), (512, N * 512)
+        run = lambda: ops.flash_attn(q, k, v, o, batches=B, heads=1, dh=512, Lq=N, Lkv=N, q_strides=st, k_strides=st, v_strides=st, o_strides=st)
+        for _ in range(2): run()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(3)]
+        for s_, e_ in ev:
+            s_.record(); run(); e_.record()
+        torch.cuda.synchronize()
+        t = statistics.median(x.elapsed_time(y) for x, y in ev)
+        res["attn_kernel_ms"] = round(t, 3); res["attn_kernel_tflops"] = round(4.0 * B * N * N * 512 / (t * 1e-3) / 1e12, 1)
+        del q, k, v, o
+        print("VAE_FLASH_BENCH", json.dumps(res), flush=True)
+if a.flash:
+    flash_report(); sys.exit(0)
 vae = AutoencoderKL(device=dev, dtype=torch.bfloat16)
 vae.init_synthetic_(seed=0)
 g = torch.Generator(device=dev).manual_seed(0)

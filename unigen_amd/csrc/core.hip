@@ -34,4 +34,4 @@ int ug_env_int(const char* name, int dflt) {
 }
 
 extern "C" const char* ug_last_error(void) { return g_err; }
-extern "C" int ug_version(void) { return 230; /* 0.2.3: ug_vae_tile_blend, AutoencoderKL tiling (csrc/vae.hip) */ }
+extern "C" int ug_version(void) { return 240; /* 0.2.4: ug_flash_attn_fwd_wide, flash attention at head width 512 for the AutoencoderKL mid-block (csrc/attn_wide.hip) */ }

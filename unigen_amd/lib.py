@@ -97,6 +97,7 @@ SIGNATURES = {
     "ug_adaln_modulate": (i32, [vp, i64, i64, i64, vp, vp, i64, i64, vp, i64, i64, i64, f32, vp]),
     "ug_qk_rmsnorm_rope": (i32, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, f32, vp]),
     "ug_flash_attn_fwd": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp]),
+    "ug_flash_attn_fwd_wide": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp]),     # head width 512 (csrc/attn_wide.hip)
     "ug_timestep_embed": (i32, [vp, vp, i64, i64, i32, vp]),
     "ug_euler_step": (i32, [vp, vp, f32, i64, vp]),
     "ug_cfg_combine": (i32, [vp, vp, f32, vp, i64, vp]),
@@ -212,7 +213,7 @@ _F32_TWINS = {"ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32":
               "ug_adaln_modulate_bwd_f32": "ug_adaln_modulate_bwd", "ug_qk_rmsnorm_rope_bwd_f32": "ug_qk_rmsnorm_rope_bwd",
               "ug_attn_prob_f32": "ug_attn_prob", "ug_attn_dscore_f32": "ug_attn_dscore", "ug_rowdot_f32": "ug_rowdot",
               "ug_gemm_f32": "ug_gemm_bf16", "ug_small_linear_f32": "ug_small_linear_bf16", "ug_adaln_modulate_f32": "ug_adaln_modulate",
-              "ug_qk_rmsnorm_rope_f32": "ug_qk_rmsnorm_rope", "ug_flash_attn_fwd_f32": "ug_flash_attn_fwd", "ug_timestep_embed_f32": "ug_timestep_embed",
+              "ug_qk_rmsnorm_rope_f32": "ug_qk_rmsnorm_rope", "ug_flash_attn_fwd_f32": "ug_flash_attn_fwd", "ug_flash_attn_fwd_wide_f32": "ug_flash_attn_fwd_wide", "ug_timestep_embed_f32": "ug_timestep_embed",
               "ug_euler_step_f32": "ug_euler_step", "ug_cfg_combine_f32": "ug_cfg_combine", "ug_add_f32": "ug_add_bf16",
               "ug_add_rowbcast_f32_f32": "ug_add_rowbcast_f32", "ug_gather_rows_f32": "ug_gather_rows", "ug_moe_gate_top1_f32": "ug_moe_gate_top1",
               "ug_moe_dispatch_modulate_f32": "ug_moe_dispatch_modulate", "ug_moe_combine_f32": "ug_moe_combine",

@@ -268,13 +268,20 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
                Lq: int, Lkv: int, q_strides, k_strides, v_strides, o_strides, scale: Optional[float] = None,
                lse: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q/k/v/out are base tensors (data_ptr = element [batch 0, row 0, head 0, 0]); *_strides = (row_stride, batch_stride).
-    lse (bf16 path only): fp32 [batches, heads, >= Lq], receives the rows' base-2 log-sum-exp for flash_attn_bwd."""
+    lse (bf16 path only): fp32 [batches, heads, >= Lq], receives the rows' base-2 log-sum-exp for flash_attn_bwd.
+    dh = 512 (the AutoencoderKL mid-block head) runs ug_flash_attn_fwd_wide: forward only, so it takes no lse."""
     dt = _act(q, "q")
     _chk(k, "k", dt); _chk(v, "v", dt); _chk(out, "out", dt)
     if scale is None:
         scale = dh ** -0.5
+    if dh == 512 and lse is not None:
+        raise L.UniGenHipError("flash_attn: lse= is not available at dh = 512 (ug_flash_attn_fwd_wide is forward only: there is no backward at this head width)")
     ev = _timer.begin("attn") if _timer is not None else None
-    if lse is not None:
+    if dh == 512:
+        L.check(_fn("ug_flash_attn_fwd_wide", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1],
+                                                v.data_ptr(), v_strides[0], v_strides[1], out.data_ptr(), o_strides[0], o_strides[1],
+                                                batches, heads, Lq, Lkv, dh, scale, _stream()), "ug_flash_attn_fwd_wide")
+    elif lse is not None:
         _chk(lse, "lse", torch.float32)
         assert dt == bf16 and lse.is_contiguous() and lse.shape[0] == batches and lse.shape[1] == heads and lse.shape[2] >= Lq
         L.check(L.load().ug_flash_attn_fwd_lse(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1],

@@ -215,6 +215,13 @@ class _VaeSwitchMixin:
     def disable_vae_slicing(self) -> None:
         self._vae_switch("disable_slicing")
 
+    def enable_vae_flash_attention(self) -> None:
+        """Run the VAE's mid-block attention on the flash kernels: no [HW, HW] score scratch (AutoencoderKL.enable_flash_attention)."""
+        self._vae_switch("enable_flash_attention")
+
+    def disable_vae_flash_attention(self) -> None:
+        self._vae_switch("disable_flash_attention")
+
 
 class UniGenFLUXPipeline(_LoraLoaderMixin, _VaeSwitchMixin):
     """Call-surface twin of the reference `UniGenFLUXPipeline(FluxPipeline)`: the denoise loop runs here; text encoding and the VAE are

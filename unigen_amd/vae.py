@@ -12,6 +12,9 @@ ug_conv2d_nhwc (implicit GEMM on MFMA; nearest-2x upsampling and Downsample2D's 
 (+ SiLU), ug_gemm_bf16 (1x1 shortcuts, attention projections, scores, P.V), ug_softmax_rows, ug_vae_sample, ug_nchw_to_nhwc / ug_nhwc_to_nchw.
 fp32 parameters select the verification twins, as for the transformer.
 
+enable_flash_attention() (off by default) runs the mid-block attention as q / k / v projections + ONE ug_flash_attn_fwd_wide launch over the batch (the 512-wide
+head; ug_flash_attn_fwd at the 128 / 64 of small configurations) + to_out: no [HW, HW] scores or probabilities, no v^T, any H*W.
+
 Tiling and slicing (diffusers 0.32.2 `enable_tiling` / `enable_slicing` / `tiled_decode` / `tiled_encode`, restated; parity unpinned like the rest): off by
 default, and then nothing below the routing functions changes. On, an input larger than the tile on either side is cut into overlapping tiles, each run through
 the untiled code on its own (torch only slices and concatenates), and ug_vae_tile_blend writes every tile's blended, cropped region into the canvas in one pass.
@@ -135,6 +138,8 @@ class AutoencoderKL(nn.Module):
         self.tile_sample_min_size = self.config.sample_size
         self.tile_latent_min_size = int(self.config.sample_size / (2 ** (len(self.config.block_out_channels) - 1)))
         self.tile_overlap_factor = 0.25
+        # mid-block attention on the flash kernels instead of the [HW, HW] score scratch (enable_flash_attention below): off by default
+        self.use_flash_attention = False
 
     # ------------------------------------------------------------------ construction ---------------------------------
     @classmethod
@@ -252,6 +257,8 @@ class AutoencoderKL(nn.Module):
     def _attention(self, p: str, x: torch.Tensor, B: int, HW: int, out_tag: str) -> torch.Tensor:
         """Attention(heads = 1, dim_head = C, group_norm, residual_connection): x + to_out(softmax(q k^T / sqrt(C)) v)."""
         Cc = x.shape[1]
+        if self.use_flash_attention:
+            return self._flash_attention(p, x, B, HW, out_tag)
         if HW % 64 != 0:
             raise L.UniGenHipError(f"VAE mid-block attention needs H*W at the latent resolution to be a multiple of 64 (got {HW})")
         h = self._gn(p + ".group_norm", x, B, HW, "at_n", False)
@@ -266,6 +273,26 @@ class AutoencoderKL(nn.Module):
             ops.softmax_rows(scores, probs, float(Cc) ** -0.5)
             ops.gemm(self._P(p + ".to_v.weight"), h[sl], None, vT, M=Cc)                                    # v^T = W_v h^T  [C, HW]
             ops.gemm(probs, vT, self._P(p + ".to_v.bias"), o[sl], M=HW)                                     # P v (+ b_v: rows of P sum to 1)
+        out = self._w(out_tag, tuple(x.shape))
+        ops.gemm(o, self._P(p + ".to_out.0.weight"), self._P(p + ".to_out.0.bias"), out, M=B * HW, epilogue=L.EPI_RES_SCALE, residual=x, alpha=1.0)
+        return out
+
+    _FLASH_WIDTHS = (512, 128, 64)       # ug_flash_attn_fwd_wide | ug_flash_attn_fwd
+
+    def _flash_attention(self, p: str, x: torch.Tensor, B: int, HW: int, out_tag: str) -> torch.Tensor:
+        """_attention with use_flash_attention: q, k, v projected for the whole batch, ONE flash-attention launch (batches = B, heads = 1, dh = C),
+        to_out with the fused residual. No [HW, HW] scores or probabilities, no v^T, no per-sample loop; both flash kernels mask ragged tails, so
+        HW need not be a multiple of 64."""
+        Cc = x.shape[1]
+        if Cc not in self._FLASH_WIDTHS:
+            raise L.UniGenHipError(f"VAE flash attention has kernels for a mid-block width (one head of dim C) of 512, 128 or 64, not {Cc}: "
+                                   "use the default route (disable_flash_attention())")
+        h = self._gn(p + ".group_norm", x, B, HW, "at_n", False)
+        q, k, v = self._w("at_q", (B * HW, Cc)), self._w("at_k", (B * HW, Cc)), self._w("at_v", (B * HW, Cc))
+        for n, t in (("to_q", q), ("to_k", k), ("to_v", v)):
+            ops.gemm(h, self._P(f"{p}.{n}.weight"), self._P(f"{p}.{n}.bias"), t, M=B * HW)
+        o, st = self._w("at_o", (B * HW, Cc)), (Cc, HW * Cc)
+        ops.flash_attn(q, k, v, o, batches=B, heads=1, dh=Cc, Lq=HW, Lkv=HW, q_strides=st, k_strides=st, v_strides=st, o_strides=st, scale=float(Cc) ** -0.5)
         out = self._w(out_tag, tuple(x.shape))
         ops.gemm(o, self._P(p + ".to_out.0.weight"), self._P(p + ".to_out.0.bias"), out, M=B * HW, epilogue=L.EPI_RES_SCALE, residual=x, alpha=1.0)
         return out
@@ -382,6 +409,15 @@ class AutoencoderKL(nn.Module):
     def disable_slicing(self) -> None:
         self.use_slicing = False
 
+    def enable_flash_attention(self) -> None:
+        """Mid-block attention as one flash-attention launch over the batch (ug_flash_attn_fwd_wide at the 512-wide head, ug_flash_attn_fwd at 128 / 64):
+        its scratch is q, k, v, o at [B*HW, C] instead of [HW, HW] fp32 scores + probabilities, and H*W need not be a multiple of 64. P is rounded
+        to bf16 as the P.V operand on both routes; the summation order differs, so the two routes agree to rounding, not to the bit."""
+        self.use_flash_attention = True
+
+    def disable_flash_attention(self) -> None:
+        self.use_flash_attention = False
+
     def _tile_plan(self, H: int, W: int, tile: int, out_tile: int, down: bool):
         """Tile starts, blend extent and crop of tiled_decode (tile = tile_latent_min_size, sizes grow by the scale factor) or tiled_encode
         (tile = tile_sample_min_size, sizes shrink by it), checked BEFORE any launch: the overlap factor, the sizes the one-pass blend needs, and
@@ -400,7 +436,7 @@ class AutoencoderKL(nn.Module):
         if to_out(tile) < 2 * extent or to_out(stride) < extent:
             raise ValueError(f"tile_sample_min_size {self.tile_sample_min_size} and tile_latent_min_size {self.tile_latent_min_size} do not fit each other: a tile's "
                              f"output ({to_out(tile)}) must be at least twice the blend extent ({extent}) and its stride ({to_out(stride)}) at least the extent")
-        if self.config.mid_block_add_attention:
+        if self.config.mid_block_add_attention and not self.use_flash_attention:      # the flash kernels take any H*W
             for th in [min(tile, H - i) for i in range(0, H, stride)]:           # row-major: the first tile that breaks the rule is the one named
                 for tw in [min(tile, W - j) for j in range(0, W, stride)]:
                     hw = (th // scale) * (tw // scale) if down else th * tw
