@@ -581,6 +581,63 @@ int ug_grad_scale(const ug_optim_tensor* table, int32_t n_tensors, const int32_t
 int ug_adamw_step(const ug_optim_tensor* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, const ug_adamw_group* groups_host,
                   int32_t n_groups, const float* coef, ug_stream_t stream);
 
+/* ---- AdamW without fp32 masters and / or with bf16 moments: what is kept in bf16 is written with STOCHASTIC rounding, so that an update far
+ * below a bf16 ulp still moves the value in expectation. The arithmetic before the rounding is ug_adamw_step's, operation for operation.
+ *
+ * Generator: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", Random123), counter-based and stateless.
+ *   key     = { seed & 0xffffffff, seed >> 32 }
+ *   counter = { j & 0xffffffff, j >> 32, param_index, step }   with j = element_index >> 1
+ * element_index is the element's index inside its TENSOR (not inside a chunk), param_index the parameter's ordinal in the optimizer (the id of
+ * torch's Optimizer.state_dict), step the parameter's step count after this step's increment (first step: 1). The four output words serve the
+ * two elements 2j and 2j + 1: element i takes the 16 bits at shift 16 * (i & 1) of word 0 for the parameter, of word 1 for exp_avg, of word 2
+ * for exp_avg_sq; word 3 is unused. A draw depends on (seed, param_index, step, element_index, word) and on nothing else: not on chunking,
+ * alignment, the vector or scalar path, or what else is in the launch.
+ *
+ * Rounding of an fp32 value with bits u and a draw r in [0, 65536): finite values give bf16 bits (u + r) >> 16 - symmetric about zero
+ * (sign-magnitude), a value on the bf16 grid never moves, a value goes to the neighbour away from zero with probability (u & 0xffff) / 65536
+ * exactly, the top half-ulp below the largest finite value can reach Inf (as round-to-nearest does); Inf stays Inf; NaN becomes the quiet NaN
+ * (u >> 16) | 0x0040. ---- */
+typedef struct ug_optim_tensor_lp {
+    void* param;           /* bf16 or fp32 (param_dtype) */
+    void* grad;            /* bf16 or fp32 (grad_dtype); only read */
+    float* master;         /* fp32 master of a bf16 param, or NULL: the bf16 param itself is then read, updated and rounded stochastically */
+    void* exp_avg;         /* first / second moments, bf16 or fp32 (state_dtype) */
+    void* exp_avg_sq;
+    int64_t numel;
+    int32_t param_dtype;   /* UG_DT_* */
+    int32_t grad_dtype;
+    int32_t state_dtype;
+    int32_t group;         /* index into the ug_adamw_group_lp array */
+    uint32_t param_index;  /* counter word 2 of this tensor's draws */
+    int32_t _pad;
+} ug_optim_tensor_lp;
+
+/* ug_adamw_group's hyperparameters, plus what the draws of the group's tensors need */
+typedef struct ug_adamw_group_lp {
+    float decay;
+    float lerp_w;
+    float beta2;
+    float one_minus_beta2;
+    float eps;
+    float step_size;
+    float inv_bc2_sqrt;
+    uint32_t step;           /* the step count after this step's increment, >= 1: counter word 3 */
+    uint64_t seed;           /* the Philox key */
+} ug_adamw_group_lp;
+
+/* host-side check of a HOST copy of the table: as ug_optim_check_table for an AdamW table (n_groups >= 1), with the arrangements of this entry point.
+ * bf16 param: (master NULL, bf16 state) p, m, v read as bf16, each written with its own draw; (master NULL, fp32 state) only p is drawn for;
+ * (master, bf16 state) the master stays fp32 and p is its RNE, m and v are drawn for; (master, fp32 state) and every fp32 param (no master, fp32
+ * state): ug_adamw_step's path, no draws. */
+int ug_optim_check_table_lowp(const ug_optim_tensor_lp* table_host, int32_t n_tensors, int32_t n_groups);
+/* ug_adamw_step on a table of ug_optim_tensor_lp: same chunk list, same fused clip coefficient, no atomics, no workspace. */
+int ug_adamw_step_lowp(const ug_optim_tensor_lp* table, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks,
+                       const ug_adamw_group_lp* groups_host, int32_t n_groups, const float* coef, ug_stream_t stream);
+/* out[i] (bf16) = the stochastic rounding of x[i] with the draw of element_index first_index + i, word in {0, 1, 2}. Any element alignment:
+ * 16-byte accesses on the body where x and out are 16-byte aligned at a common element, scalar head and tail. */
+int ug_sr_round_bf16(const float* x, void* out, int64_t n, int64_t first_index, uint64_t seed, uint32_t param_index, uint32_t step, int32_t word,
+                     ug_stream_t stream);
+
 /* ---- flow-matching training objective (csrc/objective.hip; reference train.py:589-613 noisy model input, :644-652 loss). Contiguous tensors;
  * `void*` tensors are bf16 (fp32 in the `_f32` twins), `float*` ones fp32 in both. 16-byte accesses where the base pointers are 16-byte aligned,
  * scalar accesses otherwise and on a sample's unaligned head and tail. No atomics: results are bitwise reproducible. ---- */

@@ -6,7 +6,10 @@ a model built on the meta device; params (bf16) and grads (bf16, random) are all
   (c) torch:  fp32 master params, grads cast to fp32 (_foreach_copy_), torch.nn.utils.clip_grad_norm_(foreach=True),
               torch.optim.AdamW(fused=True).step(), torch._foreach_copy_ back to the bf16 params
 Median ms over --steps after --warmup, and counted bytes / s from the bytes the route must move per element (BYTES below).
-usage: python tools/optim_bench.py [--sd3] [--steps 10] [--warmup 3]"""
+--lowp measures the optimizer's low-precision state instead: the default step (fp32 masters and moments) and the three arrangements of
+AdamW(master_weights=, state_dtype=) - no master + bf16 moments, no master + fp32 moments, master + bf16 moments - alternated in one process on
+the same params and grads (about 231 GiB of state in all for UniGenFlux), with and without the fused clip.
+usage: python tools/optim_bench.py [--sd3] [--lowp] [--steps 10] [--warmup 3]"""
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,11 +38,50 @@ def trainable_shapes(sd3: bool):
     return [tuple(p.shape) for p in m.parameters() if p.requires_grad]
 
 
+# --lowp: (master_weights, state_dtype) -> bytes per element of the update launch: grad 2 read; then read + written master 4 / bf16 param 2,
+# moments 4 or 2 each; a kept master also writes the bf16 param (2). The fused norm reads the grad once more (+ 2).
+LOWP = {
+    "default": (True, torch.float32, 2 + 8 + 2 + 8 + 8),
+    "nomaster_bf16": (False, torch.bfloat16, 2 + 4 + 4 + 4),
+    "nomaster_f32": (False, torch.float32, 2 + 4 + 8 + 8),
+    "master_bf16": (True, torch.bfloat16, 2 + 8 + 2 + 4 + 4),
+}
+
+
+def lowp_main(a, AdamW, params, shapes, n):
+    """The default step (the yardstick: ug_adamw_step, unchanged) and the three low-precision arrangements (ug_adamw_step_lowp), alternated in one
+    process on the same params and grads, each with the fused clip (three launches) and without (the update launch alone)."""
+    opts = {k: AdamW(params, lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, master_weights=m, state_dtype=sd, seed=1) for k, (m, sd, _) in LOWP.items()}
+    times = {(k, clip): [] for k in opts for clip in (True, False)}
+    for it in range(a.warmup + a.steps):
+        for (k, clip), ts in times.items():        # alternated: every arrangement sees the same machine state
+            opts[k].max_grad_norm = 1.0 if clip else None
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            opts[k].step()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= a.warmup:
+                ts.append(e0.elapsed_time(e1))
+    res = dict(model="UniGenSD3" if a.sd3 else "UniGenFlux", tensors=len(shapes), elements=n, steps=a.steps, peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1))
+    for k, o in opts.items():
+        state = sum(t.numel() * t.element_size() for st in o.state.values() for t in st.values() if t.is_cuda)
+        res[k] = dict(state_bytes_per_elem=round(state / n, 2))
+        for clip in (True, False):
+            ms, b = statistics.median(times[(k, clip)]), LOWP[k][2] + (2 if clip else 0)
+            res[k]["fused_clip" if clip else "update_only"] = dict(ms=round(ms, 2), min_ms=round(min(times[(k, clip)]), 2), bytes_per_elem=b, counted_tb_s=round(n * b / ms / 1e9, 2))
+    for k in list(LOWP)[1:]:
+        res[k]["vs_default"] = round(res["default"]["fused_clip"]["ms"] / res[k]["fused_clip"]["ms"], 2)
+    print("OPTIM_BENCH_LOWP", json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sd3", action="store_true")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--lowp", action="store_true", help="the default step and the three low-precision arrangements instead of the three routes")
     a = ap.parse_args()
     from unigen_amd.optim import AdamW, clip_grad_norm_
     shapes = trainable_shapes(a.sd3)
@@ -50,6 +92,8 @@ def main():
     grads = [(1e-3 * torch.randn(s, generator=g, device=dev)).to(BF) for s in shapes]
     for p, gr in zip(params, grads):
         p.grad = gr
+    if a.lowp:
+        return lowp_main(a, AdamW, params, shapes, n)
     ours = AdamW(params, lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0)
 
     def fused():

@@ -1,12 +1,14 @@
 """One training step (forward + backward of the control modules, reference train.py:622-662) at the FLUX-schnell geometry + canny control,
 random weights and inputs: seconds per step, samples/s, peak memory. Not the headline metric (BASELINE.json measures inference); the
 SURVEY 8(f) rank-4 row. --optim adds the optimizer step of train.py:658-660 (unigen_amd.optim.AdamW(max_grad_norm=1.0): clipping fused, fp32 masters)
-to each timed step. --lora R trains rank-R LoRA adapters on the attention projections of the control branch instead, everything else frozen
+to each timed step; --optim --lowp runs that optimizer without masters and with bf16 moments (master_weights=False, state_dtype=bf16: 4 B of state
+per trainable element instead of 12) and reports the state's bytes beside the step time and the peak, to be read against a run without --lowp.
+--lora R trains rank-R LoRA adapters on the attention projections of the control branch instead, everything else frozen
 (HipModule.set_lora_trainable; UniGenFlux only), and also times the same differentiable forward with the adapters switched off.
 --objective SCHEME runs every step through unigen_amd.objective.train_step (train.py:589-662: noisy input, timesteps and loss weighting from the
 HIP objective kernels, loss, backward, the --optim optimizer) instead of the inline MSE against a fixed target, times the whole step, and then
 times the objective's own launches (prepare + loss forward / backward, HIP events) beside the torch-eager restatement of the same lines.
-usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim] [--lora R] [--objective SCHEME]"""
+usage: python tools/train_bench.py [--batch 1] [--size 1024] [--ckpt] [--layers 19 38] [--optim [--lowp]] [--lora R] [--objective SCHEME]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,12 +25,15 @@ ap.add_argument("--sd3", action="store_true", help="UniGenSD3 (SD3.5-medium geom
 ap.add_argument("--no-gradnorm", action="store_true", help="skip the per-step gradient-norm diagnostic (hundreds of small torch kernels: keep it out of rocprofv3 kernel statistics)")
 ap.add_argument("--shapes", action="store_true", help="per-shape table of the last step's GEMM / attention launches (grouped by FLOPs per launch)")
 ap.add_argument("--optim", action="store_true", help="time unigen_amd.optim.AdamW(lr=1e-4, weight_decay=1e-2, max_grad_norm=1.0).step() after each backward")
+ap.add_argument("--lowp", action="store_true", help="with --optim: AdamW(master_weights=False, state_dtype=torch.bfloat16), stochastic rounding")
 ap.add_argument("--lora", type=int, default=0, metavar="R", help="train rank-R adapters on the control branch's attention projections, base and control modules frozen")
 ap.add_argument("--objective", default=None, metavar="SCHEME", help="run the step through unigen_amd.objective.train_step with this weighting scheme (none, sigma_sqrt, cosmap, "
                 "logit_normal, mode); implies --optim (same AdamW, clipping fused into its step)")
 a = ap.parse_args()
 if a.objective:
     a.optim = True
+if a.lowp and not a.optim:
+    ap.error("--lowp is an option of --optim (or --objective)")
 if a.lora and a.sd3:
     ap.error("--lora is implemented for UniGenFlux only")
 dev, BF = torch.device("cuda:0"), torch.bfloat16
@@ -82,7 +87,8 @@ from unigen_amd import ops
 opt = None
 if a.optim:
     from unigen_amd.optim import AdamW
-    opt = AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0)
+    opt = AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8, max_grad_norm=1.0,
+                **(dict(master_weights=False, state_dtype=BF, seed=0) if a.lowp else {}))
 times, opt_times = [], []
 objective = batch = None
 if a.objective:
@@ -142,7 +148,9 @@ fw, bw = min(x[0] for x in times), min(x[1] for x in times)
 extra = {}
 if opt is not None:
     op = min(opt_times)
-    extra = dict(optimizer_s=round(op, 4), step_s=round(fw + bw + op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5))
+    extra = dict(optimizer_s=round(op, 4), step_s=round(fw + bw + op, 4), step_samples_per_s=round(B / (fw + bw + op), 3), optimizer_grad_norm=round(float(opt.last_grad_norm), 5),
+                 optimizer_state="no masters, bf16 moments" if a.lowp else "fp32 masters and moments",
+                 optimizer_state_gb=round(sum(t.numel() * t.element_size() for st in opt.state.values() for t in st.values() if torch.is_tensor(t) and t.is_cuda) / 2 ** 30, 2))
 if objective is not None:              # the step is timed as a whole: forward_s holds it, backward_s / optimizer_s are 0
     extra.update(objective=a.objective, step_s=round(fw, 4))
     # the objective's own launches by HIP events, beside the torch-eager restatement of train.py:598-613 and :644-652 (without get_sigmas' host

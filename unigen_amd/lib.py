@@ -81,6 +81,20 @@ class AdamwGroup(C.Structure):
                 ("_pad", f32)]
 
 
+class OptimTensorLP(C.Structure):
+    """Mirror of struct ug_optim_tensor_lp (include/unigen_hip.h)."""
+
+    _fields_ = [("param", vp), ("grad", vp), ("master", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", i64),
+                ("param_dtype", i32), ("grad_dtype", i32), ("state_dtype", i32), ("group", i32), ("param_index", C.c_uint32), ("_pad", i32)]
+
+
+class AdamwGroupLP(C.Structure):
+    """Mirror of struct ug_adamw_group_lp (include/unigen_hip.h)."""
+
+    _fields_ = [("decay", f32), ("lerp_w", f32), ("beta2", f32), ("one_minus_beta2", f32), ("eps", f32), ("step_size", f32), ("inv_bc2_sqrt", f32),
+                ("step", C.c_uint32), ("seed", C.c_uint64)]
+
+
 def optim_tensor(*, grad: int, grad_dtype: int, numel: int, param: int = 0, param_dtype: int = UG_DT_F32, master: int = 0, exp_avg: int = 0,
                  exp_avg_sq: int = 0, group: int = 0) -> OptimTensor:
     """One ug_optim_tensor from raw device addresses (0 = NULL): any element alignment, any of the four (grad dtype, master) forms."""
@@ -154,6 +168,9 @@ SIGNATURES.update({
     "ug_grad_sumsq": (i32, [vp, i32, vp, i64, f32, vp, vp, i64, vp]),
     "ug_grad_scale": (i32, [vp, i32, vp, i64, vp, vp]),
     "ug_adamw_step": (i32, [vp, i32, vp, i64, vp, i32, vp, vp]),
+    "ug_optim_check_table_lowp": (i32, [vp, i32, i32]),
+    "ug_adamw_step_lowp": (i32, [vp, i32, vp, i64, vp, i32, vp, vp]),
+    "ug_sr_round_bf16": (i32, [vp, vp, i64, i64, C.c_uint64, C.c_uint32, C.c_uint32, i32, vp]),
 })
 # adapter gradients (csrc/lora_bwd.hip)
 SIGNATURES.update({
