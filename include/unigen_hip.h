@@ -136,7 +136,12 @@ int ug_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t batches, int64_t rows_per_
 
 /* O = softmax(Q K^T / sqrt(dh)) V, non-causal, no mask; Q rows [Lq], K/V rows [Lkv]; head h occupies
  * columns [h*dh, (h+1)*dh) of each row. Strides in elements. Replaces F.scaled_dot_product_attention
- * (src/UniGenUtils.py:601 and diffusers FluxAttnProcessor2_0). dh in {64, 128}. */
+ * (src/UniGenUtils.py:601 and diffusers FluxAttnProcessor2_0). dh in {64, 128}.
+ * Row strides: the bf16 kernels of this family (ug_flash_attn_fwd, ug_flash_attn_fwd_lse, ug_flash_attn_bwd, ug_flash_attn_fwd_wide) stream K / V
+ * (the backward: Q / dO too) with LDS-DMAs whose per-lane byte offsets over a 64-row tile are 32-bit, 2 (63 rs + 120) < 2^32. One rule for every
+ * row stride of the three narrow entry points - q, k, v, o and the backward's dout, dq, dk, dv -: 0 < rs < 2^24 elements, UG_ERR_UNSUPPORTED
+ * otherwise (the widest row of the package is 21 504). Batch strides are 64-bit everywhere: any multiple of 8 (o: 4). The fp32 twins
+ * (ug_flash_attn_fwd_f32, _wide_f32, _bias_f32) and ug_flash_attn_fwd_bias with a table or a mask index in 64 bits and take any row stride. */
 int ug_flash_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
                       const void* k, int64_t k_row_stride, int64_t k_batch_stride,
                       const void* v, int64_t v_row_stride, int64_t v_batch_stride,

@@ -352,6 +352,12 @@ CONV256_CASES = [
     _c256(3, 16, 16, 128, 3, 3, 1, 1, 1, 0, 16, 16, bias=False, res="separate", Cout=512),   # several tiles in M and N
     _c256(2, 8, 8, 256, 3, 3, 1, 1, 1, 1, 16, 8, res="separate"),               # Upsample2D geometry, Ho Wo = 128: a tile straddles the sample boundary
     _c256(2, 17, 31, 512, 3, 3, 2, 0, 0, 0, 8, 16),                               # Downsample2D geometry (smaller than the input allows), Cin / 64 = 8
+    # the high bits of the packed output pixel b << 24 | oy << 12 | ox and of the input coordinates (tests/index_range_cases.py: the last five rows)
+    _c256(1, 8, 2016, 128, 3, 3, 1, 1, 1, 1, 16, 4032),                           # Wo = 4032 through the folded upsampling: bits 5-11 of ox
+    _c256(1, 2016, 8, 128, 3, 3, 1, 1, 1, 1, 4032, 16),                           # Ho = 4032 the same way: bits 5-11 of oy
+    _c256(1, 32, 2040, 128, 3, 3, 1, 1, 1, 0, 32, 2040),                          # W = 2040, no upsampling
+    _c256(1, 33, 2047, 128, 3, 3, 2, 1, 1, 0, 16, 1024),                          # stride 2 from W = 2047 to Wo = 1024
+    _c256(252, 8, 8, 128, 3, 3, 1, 1, 1, 0, 8, 8),                                # batch indices up to 251 in the top byte
 ]
 
 GN_SEEDS = 40
@@ -477,10 +483,11 @@ def sample_data(c: dict, g: torch.Generator):
 
 
 def conv_data(c: dict, g: torch.Generator, cin: int, cout: int):
-    """x [B, H, W, cin], w [cout, KH, KW, cin], bias, R [B, Ho, Wo, cout]: bf16 values in float64. Samples differ in scale (1, 3, 9) so that a
-    pixel read from the wrong sample shows."""
+    """x [B, H, W, cin], w [cout, KH, KW, cin], bias, R [B, Ho, Wo, cout]: bf16 values in float64. Samples differ in scale (1, 3, 9, 27, 81, then
+    again from 1: 3^b leaves bf16 beyond b = 80, and a period of five shares no factor with a batch field cut to a power of two) so that a pixel
+    read from the wrong sample shows."""
     B, H, W, KH, KW = c["B"], c["H"], c["W"], c["KH"], c["KW"]
-    x = torch.randn(B, H, W, cin, generator=g, dtype=F64) * (3.0 ** torch.arange(B, dtype=F64))[:, None, None, None] + 0.25
+    x = torch.randn(B, H, W, cin, generator=g, dtype=F64) * (3.0 ** (torch.arange(B) % 5).to(F64))[:, None, None, None] + 0.25
     w = torch.randn(cout, KH, KW, cin, generator=g, dtype=F64) * (KH * KW * cin) ** -0.5
     b = 0.3 * torch.randn(cout, generator=g, dtype=F64)
     R = torch.randn(B, c["Ho"], c["Wo"], cout, generator=g, dtype=F64)

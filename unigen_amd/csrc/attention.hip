@@ -1115,6 +1115,10 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
                q_batch_stride % 8 == 0 && k_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && o_batch_stride % 4 == 0 &&
                ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 8),
                UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd: strides must be multiples of 8 elements and bases 16-byte aligned");
+    // the LDS-DMAs of K and V form 32-bit byte offsets over a 64-row tile from the row stride cut to int (63 rs + 120 < 2^31 is what they can hold);
+    // one rule for every row stride of the family, the one of ug_flash_attn_fwd_wide
+    for (int64_t rs : {q_row_stride, k_row_stride, v_row_stride, o_row_stride})
+        UG_REQUIRE(rs > 0 && rs < (1 << 24), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: q / k / v / o row strides must be within (0, 2^24) elements");
 #ifdef UG_PROBE_BUILD     // probe library: every forward form, the UG_ATTN_* environment switches select (tools/probe/csrc/attn_fwd_variants.hip)
     return ug_attn_fwd_variants(q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
                                 o_batch_stride, batches, heads, Lq, Lkv, dh, softmax_scale, lse_out, lse_ld, stream);
@@ -1236,6 +1240,9 @@ extern "C" int ug_flash_attn_bwd(const void* q, int64_t q_rs, int64_t q_bs, cons
     for (int64_t sgl : strides) UG_REQUIRE(sgl % 8 == 0, UG_ERR_BAD_ALIGN, "ug_flash_attn_bwd: strides must be multiples of 8 elements");
     UG_REQUIRE(ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16) && ug_aligned(dout, 16) && ug_aligned(dq, 8) &&
                ug_aligned(dk, 8) && ug_aligned(dv, 8), UG_ERR_BAD_ALIGN, "ug_flash_attn_bwd: bases must be 16-byte aligned");
+    // as the forward: the streamed operands' LDS-DMAs hold 32-bit byte offsets over a 64-row tile (63 rs + 120 < 2^31); one rule for all eight
+    for (int64_t rs : {q_rs, k_rs, v_rs, o_rs, do_rs, dq_rs, dk_rs, dv_rs})
+        UG_REQUIRE(rs > 0 && rs < (1 << 24), UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: q / k / v / o / dout / dq / dk / dv row strides must be within (0, 2^24) elements");
     const int64_t stat_ld = (Lq + 63) / 64 * 64;
     UG_REQUIRE(workspace && ug_aligned(workspace, 16) && workspace_bytes >= ug_flash_attn_bwd_workspace_bytes(batches, heads, Lq), UG_ERR_BAD_SHAPE,
                "ug_flash_attn_bwd: workspace of ug_flash_attn_bwd_workspace_bytes() needed");
