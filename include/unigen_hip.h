@@ -823,6 +823,33 @@ int ug_bicubic_f32(const float* x, int64_t B, int64_t H, int64_t W, float* out, 
 int64_t ug_minmax_workspace_bytes(int64_t B, int64_t HW);
 int ug_minmax_to_u8(const float* d, int64_t B, int64_t HW, uint8_t* out, int32_t channels, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 
+/* ---- Sana transformer block (csrc/sana.hip; unigen_amd/sana.py: diffusers' SanaTransformerBlock). The two kernel classes of that block which are
+ * neither a GEMM nor a softmax attention. Every bf16 entry has an `_f32` twin (fp32 storage, no intermediate rounding) declared beside it. ---- */
+/* SanaLinearAttnProcessor2_0: ReLU linear attention without a softmax. Head h occupies columns [h dh, (h + 1) dh) of each row, as in ug_flash_attn_fwd;
+ * with q' = relu(q), k' = relu(k), per (batch, head):
+ *   S[d][j] = sum_n v[n][d] k'[n][j]     z[j] = sum_n k'[n][j]     out[n][d] = sum_j S[d][j] q'[n][j] / (sum_j z[j] q'[n][j] + 1e-15)
+ * q, k, v are upcast, everything is fp32 (S and z included: they are never rounded to bf16), the output is rounded once. dh must be 32
+ * (UG_ERR_UNSUPPORTED otherwise); any N >= 1. q / k / v / o take a row stride and a batch stride each, in elements (the packed [q | k | v] output of
+ * one GEMM is read in place): multiples of 8 (fp32 twin: 4), bases 16-byte aligned, UG_ERR_BAD_ALIGN otherwise. The caller-owned, 16-byte aligned
+ * workspace of the size the query returns needs no initialisation: the per-chunk partial states are written, then summed in ascending chunk order, then
+ * applied - three launches, no atomics, nothing kept between calls, so two calls give the same bits and the call can be captured in a graph. */
+int64_t ug_linear_attn_workspace_bytes(int64_t batches, int64_t heads, int64_t N);
+int ug_linear_attn(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                   const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                   int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace, ug_stream_t stream);
+int ug_linear_attn_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                       const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                       int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace, ug_stream_t stream);
+/* The middle of GLUMBConv (norm_type None, no residual) between the conv_inverted and conv_point GEMMs. x NHWC [B][H][W] rows of 2C with row stride ldx:
+ * conv_inverted's output BEFORE its SiLU. w9: conv_depth.weight [2C][1][3][3] repacked as [9][2C] (tap ky 3 + kx major), bias [2C].
+ *   a = rnd(silu(x))     y = rnd(dwconv3x3(a, zero padding 1) + bias)  (fp32 accumulate)     out[..][c] = rnd(y[..][c] * rnd(silu(y[..][C + c])))
+ * out [B][H][W] rows of C with row stride ldo; columns [C, ldo) are written as zeros (the K padding of the conv_point GEMM). C must be a multiple
+ * of 8 (UG_ERR_UNSUPPORTED otherwise); ldx, ldo multiples of 8 elements and every base 16-byte aligned (UG_ERR_BAD_ALIGN). */
+int ug_glu_dwconv3x3(const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t C,
+                     ug_stream_t stream);
+int ug_glu_dwconv3x3_f32(const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t C,
+                         ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

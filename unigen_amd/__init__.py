@@ -4,10 +4,11 @@ Layout: csrc/ (HIP kernels + C ABI -> libunigen_hip.so), lib.py (ctypes binding)
 flux.py (UniGenFlux / MultiCondtionUniGenFlux host engine), pipeline.py (denoise loop / UniGenFLUXPipeline surface)."""
 __version__ = "0.1.0"
 
-# the training surface and the text encoders, imported on first use (importing the package itself needs neither torch nor the HIP library)
+# the training surface, the text encoders and the Sana transformer, imported on first use (importing the package itself needs neither torch nor the HIP library)
 _LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training_sigmas": "objective", "sample_density": "objective",
          "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text", "CLIPTextModelWithProjection": "text",
-         "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text"}
+         "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text",
+         "SanaTransformerBlock": "sana", "SanaTransformer2DModel": "sana"}
 __all__ = sorted(_LAZY)
 
 

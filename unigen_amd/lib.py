@@ -221,7 +221,13 @@ SIGNATURES.update({
     "ug_minmax_workspace_bytes": (i64, [i64, i64]),
     "ug_minmax_to_u8": (i32, [vp, i64, i64, vp, i32, vp, i64, vp]),
 })
-_F32_TWINS = {"ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32": "ug_relu", "ug_deconv_scatter_nhwc_f32": "ug_deconv_scatter_nhwc",
+# Sana transformer block (csrc/sana.hip)
+SIGNATURES.update({
+    "ug_linear_attn_workspace_bytes": (i64, [i64, i64, i64]),
+    "ug_linear_attn": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i32, vp, vp]),
+    "ug_glu_dwconv3x3": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
+})
+_F32_TWINS = {"ug_linear_attn_f32": "ug_linear_attn", "ug_glu_dwconv3x3_f32": "ug_glu_dwconv3x3", "ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32": "ug_relu", "ug_deconv_scatter_nhwc_f32": "ug_deconv_scatter_nhwc",
               "ug_bilinear_nhwc_f32": "ug_bilinear_nhwc", "ug_depth_head_out_f32": "ug_depth_head_out",
               "ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
               "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu", "ug_gelu_erf_f32": "ug_gelu_erf",

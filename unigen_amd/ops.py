@@ -1206,3 +1206,43 @@ def minmax_to_u8(d: torch.Tensor, channels: int = 1, workspace: Optional[torch.T
     out = torch.empty(B, H, W, channels, dtype=u8, device=d.device)
     L.check(L.load().ug_minmax_to_u8(d.data_ptr(), B, H * W, out.data_ptr(), channels, ws.data_ptr(), ws.numel(), _stream()), "ug_minmax_to_u8")
     return out
+
+
+# ---- Sana transformer block (csrc/sana.hip) ----
+def linear_attn_workspace_bytes(batches: int, heads: int, N: int) -> int:
+    return int(L.load().ug_linear_attn_workspace_bytes(batches, heads, N))
+
+
+def linear_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batches: int, heads: int, N: int, q_strides, k_strides,
+                v_strides, o_strides, dh: int = 32, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ReLU linear attention (SanaLinearAttnProcessor2_0). q/k/v/out are base tensors (data_ptr = element [batch 0, row 0, head 0, 0]) and
+    *_strides = (row_stride, batch_stride), as for flash_attn. `workspace`: a uint8 tensor of at least linear_attn_workspace_bytes(batches, heads, N),
+    contents irrelevant; allocated per call when omitted."""
+    dt = _act(q, "q")
+    _chk(k, "k", dt); _chk(v, "v", dt); _chk(out, "out", dt)
+    ws = torch.empty(linear_attn_workspace_bytes(batches, heads, N), dtype=u8, device=q.device) if workspace is None else workspace
+    _chk(ws, "workspace", u8)
+    if ws.numel() < linear_attn_workspace_bytes(batches, heads, N):
+        raise ValueError(f"linear_attn: the workspace has {ws.numel()} bytes, {linear_attn_workspace_bytes(batches, heads, N)} are needed")
+    ev = _timer.begin("linear_attn") if _timer is not None else None
+    L.check(_fn("ug_linear_attn", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+                                    v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, N, dh, ws.data_ptr(), _stream()),
+            "ug_linear_attn")
+    if ev is not None:
+        _timer.end("linear_attn", 4.0 * batches * heads * N * dh * (dh + 1), ev, tag=(batches, heads, N))
+    return out
+
+
+def glu_dwconv3x3(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, *, B: int, H: int, W: int, C: int,
+                  ldx: Optional[int] = None, ldo: Optional[int] = None) -> torch.Tensor:
+    """out[..., c] = y[..., c] * silu(y[..., C + c]), y = dwconv3x3(silu(x)) + bias (the middle of GLUMBConv). x: rows of 2C channels per pixel (NHWC),
+    w9 [9, 2C] (conv_depth.weight repacked tap-major), bias [2C]; out: rows of ldo >= C columns, the columns past C written as zeros."""
+    dt = _act(x, "x")
+    _chk(w9, "w9", dt); _chk(bias, "bias", dt); _chk(out, "out", dt)
+    assert w9.is_contiguous() and tuple(w9.shape) == (9, 2 * C) and bias.numel() == 2 * C, (w9.shape, bias.shape, C)
+    ev = _timer.begin("glu_dwconv") if _timer is not None else None
+    L.check(_fn("ug_glu_dwconv3x3", dt)(x.data_ptr(), ldx if ldx is not None else x.stride(-2), w9.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                      ldo if ldo is not None else out.stride(-2), B, H, W, C, _stream()), "ug_glu_dwconv3x3")
+    if ev is not None:
+        _timer.end("glu_dwconv", 2.0 * 9 * 2 * C * B * H * W, ev, tag=(B, H, W, C))
+    return out
