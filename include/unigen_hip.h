@@ -733,15 +733,15 @@ int ug_canny_nms(const int16_t* dx, const int16_t* dy, const int32_t* mag, int64
                  ug_stream_t stream);
 /* Stage 3: every candidate that is 8-connected to a strong pixel through candidates becomes strong (in place, in `map`); out = 255 there, else 0.
  * Runs as sweeps of one launch each - a workgroup takes its tile to a local fixed point, no workgroup waits on another - and reads the 4-byte device
- * word `flag` after each sweep (a stream synchronisation per sweep: this stage sits outside the denoise loop and cannot be graph-captured). *sweeps
- * (host, may be NULL) receives their number, at most the value returned by the bound function below, H * W + 1. */
+ * word `flag` after each sweep (a stream synchronisation per sweep: this stage sits outside the denoise loop and cannot be graph-captured). *sweeps_host
+ * (may be NULL) receives their number, at most the value returned by the bound function below, H * W + 1. */
 int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W, uint8_t* out, int64_t out_bstride, int64_t out_rstride, int32_t* flag,
-                        int32_t* sweeps, ug_stream_t stream);
+                        int32_t* sweeps_host, ug_stream_t stream);
 int64_t ug_canny_max_sweeps(int64_t H, int64_t W);
 /* The three stages in one call on a caller-owned, 16-byte aligned workspace of the size the query returns. */
 int64_t ug_canny_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int ug_canny_u8(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t low, int32_t high, uint8_t* out,
-                int64_t out_bstride, int64_t out_rstride, void* workspace, int64_t workspace_bytes, int32_t* sweeps, ug_stream_t stream);
+                int64_t out_bstride, int64_t out_rstride, void* workspace, int64_t workspace_bytes, int32_t* sweeps_host, ug_stream_t stream);
 /* PIL's Image.resize for 8-bit images (ImagingResample, 8bpc): horizontal pass, then vertical pass, a uint8 image between them; a pass whose size does
  * not change is skipped and needs no tables. Per output coordinate o of a pass: bounds[2 o] = first input coordinate, bounds[2 o + 1] = taps n <= k,
  * coef[o * k + i] = 22-bit fixed-point weights (device tables, built on the host: unigen_amd/image.py resample_tables). A value is
@@ -781,13 +781,13 @@ int ug_img_box_blur_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstr
  * beside it. Outputs are fully written, pad channels included; 16-byte aligned bases take the 8-channel paths, anything else single elements. ---- */
 /* uint8 NHWC [B, H, W, C] (byte strides as for the image front end; C = 3, or 1: gray replicated) -> rows [B (H/P) (W/P)][ld_out] of the
  * patch-embedding GEMM: column c P^2 + ky P + kx (the flattening of the conv weight [D][3][P][P]) of the row of patch (py, px) is
- *   ((float)((double)v * rescale) - mean[c]) / std[c]          v = img[b][py P + ky][px P + kx][c]
+ *   ((float)((double)v * rescale) - mean_host[c]) / std_host[c]          v = img[b][py P + ky][px P + kx][c]
  * with DPTImageProcessor's rounding points (rescale: a float64 product cast to float32; normalize: float32 subtraction and IEEE division);
- * columns [3 P^2, Kp) are zero. Kp a multiple of 64; H, W multiples of P <= 64. mean, std: 3 floats each on the HOST. bf16 rounds once, at the store. */
+ * columns [3 P^2, Kp) are zero. Kp a multiple of 64; H, W multiples of P <= 64. mean_host, std_host: 3 floats each. bf16 rounds once, at the store. */
 int ug_img_u8_to_patches(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
-                         const float* mean, const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
+                         const float* mean_host, const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
 int ug_img_u8_to_patches_f32(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
-                             const float* mean, const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
+                             const float* mean_host, const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
 /* y = max(x, 0) over n contiguous elements, n a multiple of 8; y may be x. */
 int ug_relu(const void* x, void* y, int64_t n, ug_stream_t stream);
 int ug_relu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);

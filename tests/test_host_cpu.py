@@ -21,19 +21,29 @@ def test_library_exports_every_declared_symbol(tmp_path):
     from unigen_amd import build, lib
     build.build()
     hdr = open(os.path.join(ROOT, "include", "unigen_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)                 # a `ug_x(` inside a comment declares nothing
     declared = set(re.findall(r"\b(ug_[a-z0-9_]+)\s*\(", hdr))
-    assert declared and declared == set(lib.SIGNATURES), declared ^ set(lib.SIGNATURES)
+    assert len(declared) >= 154 and declared == set(lib.SIGNATURES), declared ^ set(lib.SIGNATURES)
     cdll = lib.load()
     for name in declared:
         assert getattr(cdll, name) is not None
     assert cdll.ug_version() >= 100
-    # the ctypes mirror of ug_gemm_desc has the C layout (checked against a compile of the header)
-    src = '#include "unigen_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%zu %zu %zu %zu", sizeof(ug_gemm_desc), offsetof(ug_gemm_desc, alpha), offsetof(ug_gemm_desc, M), offsetof(ug_gemm_desc, lora_r));return 0;}'
+    # every generated ctypes.Structure has the C layout: size, and offset and size of every field, against a compile of the header
+    structs = sorted(set(re.findall(r"typedef struct (ug_\w+)", hdr)))
+    assert structs == sorted(lib.STRUCTS) and len(structs) >= 8
+    named = dict(GemmDesc="ug_gemm_desc", ConvDesc="ug_conv_desc", VaeTile="ug_vae_tile", VaeBlendDesc="ug_vae_blend_desc", OptimTensor="ug_optim_tensor",
+                 AdamwGroup="ug_adamw_group", OptimTensorLP="ug_optim_tensor_lp", AdamwGroupLP="ug_adamw_group_lp")
+    assert all(getattr(lib, py) is lib.STRUCTS[c] for py, c in named.items())
+    rows = [(s, f) for s in structs for f, _ in lib.STRUCTS[s]._fields_]
+    assert len(rows) >= 130 and [f for s, f in rows if s == "ug_gemm_desc"][:4] == ["A", "lda", "a_rpb", "a_bstride"]
+    src = '#include "unigen_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){\n'
+    src += "".join(f'printf("%zu\\n", sizeof({s}));\n' for s in structs)
+    src += "".join(f'printf("%zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));\n' for s, f in rows) + "return 0;}\n"
     exe = str(tmp_path / "ug_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
-    sizes = list(map(int, subprocess.run([exe], capture_output=True, check=True).stdout.split()))
-    D = lib.GemmDesc
-    assert sizes == [ctypes.sizeof(D), D.alpha.offset, D.M.offset, D.lora_r.offset]
+    got = [tuple(map(int, ln.split())) for ln in subprocess.run([exe], capture_output=True, check=True, text=True).stdout.splitlines()]
+    assert got[:len(structs)] == [(ctypes.sizeof(lib.STRUCTS[s]),) for s in structs]
+    assert got[len(structs):] == [(getattr(lib.STRUCTS[s], f).offset, getattr(lib.STRUCTS[s], f).size) for s, f in rows]
 
 
 def test_error_codes_without_gpu_compute():

@@ -19,10 +19,7 @@ if "UG_LIB_B" in os.environ:
     specs.append([os.environ.get("UG_LIB_B_LABEL", "base"), os.environ["UG_LIB_B"]])
 LIBS = [("product", lib_a)]
 for label, path in specs:
-    lb = C.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(lb, name); fn.restype = res; fn.argtypes = args
-    LIBS.append((label, lb))
+    LIBS.append((label, L.bind(C.CDLL(os.path.abspath(path)))))
 from unigen_amd import ops
 dev = torch.device("cuda:0")
 g = torch.Generator(device=dev).manual_seed(0)

@@ -18,16 +18,11 @@ if AB_ENV:
     LIBS = [(v, lib_a) for v in (vals.split(",") if vals else ["0", "1"])]
 else:
     path_b = os.environ.get("UG_LIB_B", os.path.join(ROOT, "tools", "probe", "bin", "libunigen_base.so"))
-    lib_b = C.CDLL(path_b)
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(lib_b, name); fn.restype = res; fn.argtypes = args
+    lib_b = L.bind(C.CDLL(path_b))
     LIBS = [(os.environ.get("UG_LIB_B_LABEL", "base"), lib_b), ("new", lib_a)]
     for kv in [x for x in os.environ.get("UG_LIBS", "").split(";") if x]:        # more builds: UG_LIBS="label=path;label=path" (tools/build_variant.py)
         lbl, pth = kv.split("=", 1)
-        lx = C.CDLL(os.path.abspath(pth))
-        for name, (res, args) in L.SIGNATURES.items():
-            fn = getattr(lx, name); fn.restype = res; fn.argtypes = args
-        LIBS.append((lbl, lx))
+        LIBS.append((lbl, L.bind(C.CDLL(os.path.abspath(pth)))))
 from unigen_amd import ops
 from unigen_amd.ops import QkRope, RowMap
 dev, BF = torch.device("cuda:0"), torch.bfloat16

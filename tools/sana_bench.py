@@ -85,7 +85,7 @@ def main():
                 y, x2 = torch.empty_like(x), torch.randn(B * N, 2 * C, generator=g, device=dev).to(BF)
                 us = timed(lambda: ops.add(x, x2, y), a.iters)
                 say(f"  ug_add_bf16 (size of x)   {name}  {B}  {N:5d}  {us:10.1f}  {6 * x.numel() / 1e6:10.1f}  {6 * x.numel() / 1e6 / us * 1e3:7.0f}")
-                us = timed(lambda: L.check(L.load().ug_gelu_tanh(x.data_ptr(), y.data_ptr(), x.numel(), ops._stream()), "ug_gelu_tanh"), a.iters)
+                us = timed(lambda: L.call("ug_gelu_tanh", x.data_ptr(), y.data_ptr(), x.numel(), ops._stream()), a.iters)
                 say(f"  ug_gelu_tanh (size of x)  {name}  {B}  {N:5d}  {us:10.1f}  {4 * x.numel() / 1e6:10.1f}  {4 * x.numel() / 1e6 / us * 1e3:7.0f}")
                 del qkv, o, ws, x, x2, out, y
 

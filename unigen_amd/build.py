@@ -19,6 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
+HEADER = os.path.join(ROOT, "include", "unigen_hip.h")      # the C ABI; unigen_amd/lib.py derives its ctypes binding from this file
 LIB = os.path.join(HERE, "libunigen_hip.so")
 PROBE_DIR = os.path.join(ROOT, "tools", "probe")
 PROBE_LIB = os.path.join(PROBE_DIR, "libunigen_hip_probe.so")
@@ -57,7 +58,7 @@ def build(force: bool = False, verbose: bool = False, probe: bool = False) -> st
 
 
 def _build_locked(force: bool, verbose: bool, probe: bool, objdir: str) -> str:
-    hdrs = [os.path.join(CSRC, "ug_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(ROOT, "include", "unigen_hip.h")]
+    hdrs = [os.path.join(CSRC, "ug_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "attn_common.h"), HEADER]
     sources = SOURCES + (PROBE_ONLY_SOURCES if probe else [])
     lib = PROBE_LIB if probe else LIB
     flags = (["-DUG_PROBE_BUILD", "-I", CSRC] if probe else []) + FLAGS

@@ -255,19 +255,19 @@ __global__ __launch_bounds__(256) void minmax_to_u8_kernel(const float* __restri
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------
 template <typename T>
 static int img_u8_to_patches_impl(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
-                                  const float* mean, const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream) {
-    UG_REQUIRE(img && out && mean && std && (C == 1 || C == 3) && P >= 1 && P <= 64 && B >= 1 && H >= P && W >= P && H < 65536 && W < 65536 && H % P == 0 &&
+                                  const float* mean_host, const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream) {
+    UG_REQUIRE(img && out && mean_host && std_host && (C == 1 || C == 3) && P >= 1 && P <= 64 && B >= 1 && H >= P && W >= P && H < 65536 && W < 65536 && H % P == 0 &&
                    W % P == 0 && rstride >= W * C && (B == 1 || bstride >= (H - 1) * rstride + W * C),
                UG_ERR_BAD_SHAPE, "ug_img_u8_to_patches: bad arguments (B=%lld H=%lld W=%lld C=%d P=%d; H and W are multiples of P, strides cover a row / a sample)",
                (long long)B, (long long)H, (long long)W, C, P);
     UG_REQUIRE(Kp >= 3 * P * P && Kp % 64 == 0 && ld_out >= Kp, UG_ERR_BAD_SHAPE, "ug_img_u8_to_patches: Kp=%lld must be a multiple of 64, >= 3 P^2 = %d and <= ld_out",
                (long long)Kp, 3 * P * P);
-    UG_REQUIRE(std[0] != 0.0f && std[1] != 0.0f && std[2] != 0.0f, UG_ERR_BAD_SHAPE, "ug_img_u8_to_patches: a zero std");
+    UG_REQUIRE(std_host[0] != 0.0f && std_host[1] != 0.0f && std_host[2] != 0.0f, UG_ERR_BAD_SHAPE, "ug_img_u8_to_patches: a zero std");
     const int64_t rows = B * (H / P) * (W / P);
     UG_REQUIRE(rows < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_img_u8_to_patches: %lld patch rows", (long long)rows);
     PatchNorm nm;
     nm.rescale = rescale;
-    for (int i = 0; i < 3; ++i) { nm.mean[i] = mean[i]; nm.std[i] = std[i]; }
+    for (int i = 0; i < 3; ++i) { nm.mean[i] = mean_host[i]; nm.std[i] = std_host[i]; }
     const int vec = ug_aligned(out, 16) && (ld_out * sizeof(T)) % 16 == 0;
     hipLaunchKernelGGL(u8_to_patches_kernel<T>, dim3((unsigned)rows), dim3(128), 0, (hipStream_t)stream, img, bstride, rstride, (int)C, (int)(H / P), (int)(W / P),
                        (int)P, nm, (T*)out, ld_out, (int)Kp, vec);
@@ -275,9 +275,9 @@ static int img_u8_to_patches_impl(const uint8_t* img, int64_t bstride, int64_t r
     return UG_OK;
 }
 UG_TWINS(ug_img_u8_to_patches, img_u8_to_patches_impl,
-         (const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale, const float* mean,
-          const float* std, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream),
-         (img, bstride, rstride, B, H, W, C, P, rescale, mean, std, out, ld_out, Kp, stream))
+         (const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale, const float* mean_host,
+          const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream),
+         (img, bstride, rstride, B, H, W, C, P, rescale, mean_host, std_host, out, ld_out, Kp, stream))
 
 template <typename T> static int relu_impl(const void* x, void* y, int64_t n, ug_stream_t stream) {
     UG_REQUIRE(x && y && n >= 0 && n % 8 == 0 && n / 8 < (1ll << 31) * 256, UG_ERR_BAD_SHAPE, "ug_relu: n=%lld must be a non-negative multiple of 8", (long long)n);

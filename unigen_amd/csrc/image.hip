@@ -577,7 +577,7 @@ extern "C" int ug_canny_nms(const int16_t* dx, const int16_t* dy, const int32_t*
 extern "C" int64_t ug_canny_max_sweeps(int64_t H, int64_t W) { return (H < 1 || W < 1) ? 0 : H * W + 1; }
 
 extern "C" int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W, uint8_t* out, int64_t out_bstride, int64_t out_rstride, int32_t* flag,
-                                   int32_t* sweeps, ug_stream_t stream) {
+                                   int32_t* sweeps_host, ug_stream_t stream) {
     UG_REQUIRE(map && flag && img_args_ok(out, out_bstride, out_rstride, B, H, W, 1), UG_ERR_BAD_SHAPE,
                "ug_canny_hysteresis: bad arguments (B=%lld H=%lld W=%lld)", (long long)B, (long long)H, (long long)W);
     hipStream_t s = (hipStream_t)stream;
@@ -601,7 +601,7 @@ extern "C" int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W
     hipLaunchKernelGGL(canny_final_kernel, fgrid, dim3(256), 0, s, map, (int)H, (int)W, out, out_bstride, out_rstride, (int)(W % 16 == 0 && ug_aligned(map, 16)),
                        (int)strided_aligned(out, out_bstride, out_rstride, 16));
     UG_CHECK_LAUNCH("ug_canny_hysteresis");
-    if (sweeps) *sweeps = (int32_t)(n > 0x7fffffff ? 0x7fffffff : n);
+    if (sweeps_host) *sweeps_host = (int32_t)(n > 0x7fffffff ? 0x7fffffff : n);
     return UG_OK;
 }
 
@@ -614,7 +614,7 @@ extern "C" int64_t ug_canny_workspace_bytes(int64_t B, int64_t H, int64_t W) {
 }
 
 extern "C" int ug_canny_u8(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t low, int32_t high,
-                           uint8_t* out, int64_t out_bstride, int64_t out_rstride, void* workspace, int64_t workspace_bytes, int32_t* sweeps,
+                           uint8_t* out, int64_t out_bstride, int64_t out_rstride, void* workspace, int64_t workspace_bytes, int32_t* sweeps_host,
                            ug_stream_t stream) {
     UG_REQUIRE(B >= 1 && H >= 1 && W >= 1 && workspace && workspace_bytes >= ug_canny_workspace_bytes(B, H, W) && ug_aligned(workspace, 16), UG_ERR_BAD_SHAPE,
                "ug_canny_u8: bad shape or a workspace smaller than ug_canny_workspace_bytes (B=%lld H=%lld W=%lld)", (long long)B, (long long)H, (long long)W);
@@ -629,7 +629,7 @@ extern "C" int ug_canny_u8(const uint8_t* img, int64_t bstride, int64_t rstride,
     if (rc != UG_OK) return rc;
     rc = ug_canny_nms(dx, dy, mag, B, H, W, low, high, map, stream);          // swaps low > high
     if (rc != UG_OK) return rc;
-    return ug_canny_hysteresis(map, B, H, W, out, out_bstride, out_rstride, flag, sweeps, stream);
+    return ug_canny_hysteresis(map, B, H, W, out, out_bstride, out_rstride, flag, sweeps_host, stream);
 }
 
 extern "C" int ug_img_resize_u8(const uint8_t* src, int64_t src_bstride, int64_t src_rstride, int64_t B, int64_t Hin, int64_t Win, int32_t C, uint8_t* dst,

@@ -1,98 +1,122 @@
-"""ctypes binding of libunigen_hip.so — the C ABI declared in include/unigen_hip.h.
+"""ctypes binding of libunigen_hip.so, derived at import from the C ABI's one declaration: include/unigen_hip.h.
 
-The product path has no fallback: if the shared library is missing or does not load, importing the ops raises.
+Constants, descriptor structs and prototypes are parsed from the header text (a closed C subset; anything else raises at import),
+so a symbol is declared in one place. The product path has no fallback: if the shared library is missing or does not load,
+importing the ops raises.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
+from . import build as _build
+
+HEADER = _build.HEADER
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UG_LIB_PATH") or os.path.join(_HERE, "libunigen_hip.so")      # UG_LIB_PATH: an alternative build (A/B tools only)
 
-UG_OK, UG_ERR_BAD_SHAPE, UG_ERR_BAD_ALIGN, UG_ERR_UNSUPPORTED, UG_ERR_HIP = 0, -1, -2, -3, -4
-EPI_BIAS, EPI_BIAS_GELU, EPI_RES_GATE, EPI_RES_SCALE, EPI_F32, EPI_QKV_ROPE = 0, 1, 2, 3, 4, 5
 
-i64, i32, f32, vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
-
-
-class GemmDesc(C.Structure):
-    """Mirror of struct ug_gemm_desc (include/unigen_hip.h)."""
-
-    _fields_ = [
-        ("A", vp), ("lda", i64), ("a_rpb", i64), ("a_bstride", i64),
-        ("W", vp), ("ldw", i64),
-        ("bias", vp),
-        ("C", vp), ("ldc", i64), ("c_rpb", i64), ("c_bstride", i64),
-        ("R", vp), ("ldr", i64), ("r_rpb", i64), ("r_bstride", i64),
-        ("gate", vp), ("gate_ld", i64), ("rows_per_sample", i64),
-        ("alpha", f32),
-        ("epilogue", i32),
-        ("M", i64), ("N", i64), ("K", i64),
-        ("groups", i32), ("_pad0", i32),
-        ("a_gstride", i64), ("w_gstride", i64), ("bias_gstride", i64), ("c_gstride", i64),
-        ("lora_T", vp), ("ldt", i64),
-        ("lora_B", vp), ("ldb", i64),
-        ("lora_r", i32), ("_pad1", i32),
-        ("r_gstride", i64), ("gate_gstride", i64),
-        ("workspace", vp), ("workspace_bytes", i64),
-        ("gelu_from_n", i64), ("c_shift_from_n", i64), ("c_shift", i64),
-        ("qk_wq", vp), ("qk_wk", vp), ("rope_cs", vp),
-        ("rope_rpb", i64), ("rope_pos0", i64), ("qk_until_n", i64),
-        ("qk_eps", f32), ("qk_dh", i32),
-    ]
+class UniGenHipError(RuntimeError):
+    pass
 
 
-class ConvDesc(C.Structure):
-    """Mirror of struct ug_conv_desc (include/unigen_hip.h)."""
-
-    _fields_ = [("x", vp), ("B", i64), ("H", i64), ("W", i64), ("Cin", i64), ("w", vp), ("bias", vp), ("R", vp), ("out", vp), ("Ho", i64), ("Wo", i64),
-                ("Cout", i64), ("KH", i32), ("KW", i32), ("stride", i32), ("pad_t", i32), ("pad_l", i32), ("up", i32), ("zero_page", vp), ("zero_page_bytes", i64)]
-
-
-class VaeTile(C.Structure):
-    """Mirror of struct ug_vae_tile (include/unigen_hip.h): element strides of a logical [B][C][H][W] tile."""
-
-    _fields_ = [("p", vp), ("H", i64), ("W", i64), ("sb", i64), ("sc", i64), ("sy", i64), ("sx", i64)]
+# the closed type map of the header; `void` and `char` occur only behind pointers, ug_stream_t joins through its typedef
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8,
+            "int16_t": C.c_int16, "float": C.c_float, "double": C.c_double}
+_TYPE_THEN_NAMES, _NAME = re.compile(r"(?:const\s+)?(\w+)\b\s*(.+)"), re.compile(r"\s*(\*?)\s*(?:const\s+)?(\w+)\s*")      # `const T` + `* a` or `a, b, c`
 
 
-class VaeBlendDesc(C.Structure):
-    """Mirror of struct ug_vae_blend_desc (include/unigen_hip.h)."""
-
-    _fields_ = [("T", VaeTile), ("U", VaeTile), ("Lf", VaeTile), ("UL", VaeTile), ("out", vp), ("ob", i64), ("oc", i64), ("oy", i64), ("ox", i64),
-                ("B", i64), ("C", i64), ("h", i64), ("w", i64), ("E", i64)]
+def _bad(what: str, decl: str):
+    raise UniGenHipError(f"unigen_hip.h: {what}: `{decl}`")
 
 
-UG_DT_BF16, UG_DT_F32 = 0, 1
-UG_OPTIM_CHUNK, UG_ADAMW_MAX_GROUPS = 65536, 32
+def _declarators(decl: str, types: dict, where: str) -> list:
+    """`const T* a` or `T a, b, c` -> [(name, ctype)]. Every pointer is a c_void_p: that argtype takes integer device addresses, None,
+    byref(struct), ctypes arrays and typed pointers."""
+    m = _TYPE_THEN_NAMES.fullmatch(decl)
+    names = [_NAME.fullmatch(d) for d in m.group(2).split(",")] if m else [None]
+    if not all(names):
+        _bad(f"cannot split `{decl}`", where)
+    base = m.group(1)
+    if base not in types and not (base in ("void", "char") and all(n.group(1) for n in names)):
+        _bad(f"unknown type `{base}`", where)
+    return [(n.group(2), C.c_void_p if n.group(1) else types[base]) for n in names]
 
 
-class OptimTensor(C.Structure):
-    """Mirror of struct ug_optim_tensor (include/unigen_hip.h)."""
+def parse_header(text: str):
+    """C header text -> (constants {name: int}, structs {C name: ctypes.Structure}, signatures {name: (restype, [argtypes])}, twins {twin: base}).
+    Understands `#define UG_X <int>`, anonymous enums, `typedef void* T;`, `typedef struct ug_x {...} ug_x;` and prototypes of `ug_*`; raises
+    UniGenHipError, quoting the declaration, on anything else."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts, structs, sigs, types = {}, {}, {}, dict(_SCALARS)
+    for line in re.findall(r"^[ \t]*#.*$", text, flags=re.M):
+        m = re.fullmatch(r"#\s*define\s+(UG_\w+)\s+(\S.*?)", line.strip())
+        if m:
+            if not re.fullmatch(r"-?(0x[0-9a-fA-F]+|\d+)", m.group(2)):
+                _bad("not an integer constant", line.strip())
+            consts[m.group(1)] = int(m.group(2), 0)
+    text, in_extern_c = re.subn(r'extern\s+"C"\s*\{', " ", re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M))
+    if in_extern_c:
+        text, closed = re.subn(r"\}\s*\Z", " ", text)
+        if not closed:
+            _bad('`extern "C" {` is not closed at the end', " ".join(text.split())[-80:])
+    decls, pos = [], 0
+    for m in re.finditer(r"\s*((?:[^;{}]|\{[^{}]*\})*);", text):      # a `;` inside a struct's braces (one level) does not end the declaration
+        if m.start() != pos:
+            break
+        decls.append(" ".join(m.group(1).split()))
+        pos = m.end()
+    if text[pos:].strip():
+        _bad("text after the last declaration", " ".join(text[pos:].split())[:200])
+    for decl in decls:
+        if m := re.fullmatch(r"enum \{(.*)\}", decl):
+            value = -1
+            for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+                im = re.fullmatch(r"(\w+)(?:\s*=\s*(-?\d+))?", item) or _bad("cannot read the enumerator", item)
+                consts[im.group(1)] = value = int(im.group(2)) if im.group(2) else value + 1
+        elif m := re.fullmatch(r"typedef void ?\* ?(\w+)", decl):
+            types[m.group(1)] = C.c_void_p
+        elif m := re.fullmatch(r"typedef struct (\w+) \{(.*)\} (\w+)", decl):
+            if m.group(1) != m.group(3):
+                _bad("struct tag and typedef name differ", decl)
+            fields = [f for d in m.group(2).split(";") if d.strip() for f in _declarators(d.strip(), types, decl)]
+            types[m.group(1)] = structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields, "__doc__": f"struct {m.group(1)} of include/unigen_hip.h"})
+        elif m := re.fullmatch(r"(?:const )?(\w+) ?(\*?) ?(ug_\w+) ?\(([^()]*)\)", decl):
+            ret, ptr, name, params = m.groups()
+            if (ret != "char") if ptr else (ret not in _SCALARS):
+                _bad(f"unknown return type `{ret}{ptr}`", decl)
+            args = [] if params.strip() == "void" else [_declarators(p.strip(), types, decl) for p in params.split(",")]
+            if name in sigs or any(len(a) != 1 for a in args):
+                _bad("declared twice" if name in sigs else "cannot split the parameters", decl)
+            sigs[name] = (C.c_char_p if ptr else _SCALARS[ret], [a[0][1] for a in args])
+        else:
+            _bad("not a declaration this binding understands", decl)
+    stray = set(re.findall(r"\b(ug_\w+)\s*\(", text)) - set(sigs)
+    if stray:
+        _bad("`ug_*(` outside a prototype", ", ".join(sorted(stray)))
+    # fp32 verification twins: `S_f32` mirrors `S` or `S_bf16` when that is declared too, and must have its signature
+    twins = {n: b for n in sigs if n.endswith("_f32") for b in (n[:-4] + "_bf16", n[:-4]) if b in sigs}
+    for twin, base in twins.items():
+        if sigs[twin] != sigs[base]:
+            _bad(f"the fp32 twin's prototype differs from that of {base}", twin)
+    return consts, structs, sigs, twins
 
-    _fields_ = [("param", vp), ("grad", vp), ("master", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", i64),
-                ("param_dtype", i32), ("grad_dtype", i32), ("group", i32), ("_pad", i32)]
+
+def _read_header() -> str:
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise UniGenHipError(f"{HEADER}: the C ABI's header is missing, and the binding is derived from it ({e})") from e
 
 
-class AdamwGroup(C.Structure):
-    """Mirror of struct ug_adamw_group (include/unigen_hip.h)."""
-
-    _fields_ = [("decay", f32), ("lerp_w", f32), ("beta2", f32), ("one_minus_beta2", f32), ("eps", f32), ("step_size", f32), ("inv_bc2_sqrt", f32),
-                ("_pad", f32)]
-
-
-class OptimTensorLP(C.Structure):
-    """Mirror of struct ug_optim_tensor_lp (include/unigen_hip.h)."""
-
-    _fields_ = [("param", vp), ("grad", vp), ("master", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", i64),
-                ("param_dtype", i32), ("grad_dtype", i32), ("state_dtype", i32), ("group", i32), ("param_index", C.c_uint32), ("_pad", i32)]
-
-
-class AdamwGroupLP(C.Structure):
-    """Mirror of struct ug_adamw_group_lp (include/unigen_hip.h)."""
-
-    _fields_ = [("decay", f32), ("lerp_w", f32), ("beta2", f32), ("one_minus_beta2", f32), ("eps", f32), ("step_size", f32), ("inv_bc2_sqrt", f32),
-                ("step", C.c_uint32), ("seed", C.c_uint64)]
+_CONSTANTS, STRUCTS, SIGNATURES, _F32_TWINS = parse_header(_read_header())
+globals().update(_CONSTANTS)                                                                          # UG_OK, UG_ERR_*, UG_EPI_*, UG_DT_*, UG_FLOW_*, UG_OPTIM_CHUNK, ...
+globals().update({k[3:]: v for k, v in _CONSTANTS.items() if k.startswith("UG_EPI_")})                 # EPI_BIAS, ...: the short names the callers use
+F32_TWIN_OF = {base: twin for twin, base in _F32_TWINS.items()}
+GemmDesc, ConvDesc, VaeTile, VaeBlendDesc = (STRUCTS[n] for n in ("ug_gemm_desc", "ug_conv_desc", "ug_vae_tile", "ug_vae_blend_desc"))
+OptimTensor, AdamwGroup, OptimTensorLP, AdamwGroupLP = (STRUCTS[n] for n in ("ug_optim_tensor", "ug_adamw_group", "ug_optim_tensor_lp", "ug_adamw_group_lp"))
 
 
 def optim_tensor(*, grad: int, grad_dtype: int, numel: int, param: int = 0, param_dtype: int = UG_DT_F32, master: int = 0, exp_avg: int = 0,
@@ -101,158 +125,16 @@ def optim_tensor(*, grad: int, grad_dtype: int, numel: int, param: int = 0, para
     return OptimTensor(param or None, grad or None, master or None, exp_avg or None, exp_avg_sq or None, numel, param_dtype, grad_dtype, group, 0)
 
 
-# name -> (restype, argtypes); must list every symbol declared in include/unigen_hip.h
-SIGNATURES = {
-    "ug_version": (i32, []),
-    "ug_last_error": (C.c_char_p, []),
-    "ug_gemm_workspace_bytes": (i64, []),
-    "ug_gemm_bf16": (i32, [C.POINTER(GemmDesc), vp]),
-    "ug_small_linear_bf16": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, i64, i32, vp]),
-    "ug_adaln_modulate": (i32, [vp, i64, i64, i64, vp, vp, i64, i64, vp, i64, i64, i64, f32, vp]),
-    "ug_qk_rmsnorm_rope": (i32, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, f32, vp]),
-    "ug_flash_attn_fwd": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp]),
-    "ug_flash_attn_fwd_wide": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp]),     # head width 512 (csrc/attn_wide.hip)
-    "ug_timestep_embed": (i32, [vp, vp, i64, i64, i32, vp]),
-    "ug_euler_step": (i32, [vp, vp, f32, i64, vp]),
-    "ug_cfg_combine": (i32, [vp, vp, f32, vp, i64, vp]),
-    "ug_add_bf16": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, vp]),
-    "ug_add_rowbcast_f32": (i32, [vp, i64, vp, i64, i64, i64, i64, vp]),
-    "ug_gather_rows": (i32, [vp, i64, vp, vp, i64, i64, i64, vp]),
-    "ug_moe_gate_top1": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, vp, vp]),
-    "ug_moe_capacity_rts": (i32, [vp, vp, vp, i64, i32, i64, vp, vp, vp, vp, vp]),
-    "ug_moe_gate_top2": (i32, [vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
-    "ug_moe_capacity_top2": (i32, [vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]),
-    "ug_moe_gate_topk": (i32, [vp, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp]),
-    "ug_moe_capacity_topk": (i32, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
-    "ug_moe_combine_topk": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i64, vp, vp, i64, i64, i64, vp, i64, i64, i64, i32, vp]),
-    "ug_moe_dispatch_modulate": (i32, [vp, i64, vp, vp, i64, i64, vp, i32, i64, i64, i64, vp, vp]),
-    "ug_moe_combine": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, vp, i64, i64, i64, vp, i64, i64, i64, i32, vp]),
-    "ug_conv2d_nhwc": (i32, [C.POINTER(ConvDesc), vp]),
-    "ug_groupnorm_workspace_bytes": (i64, [i64, i64, i32]),
-    "ug_groupnorm_nhwc": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, i32, vp]),
-    "ug_softmax_rows": (i32, [vp, i64, vp, i64, i64, i64, f32, vp]),
-    "ug_nchw_to_nhwc": (i32, [vp, vp, i64, i64, i64, i64, f32, f32, vp]),
-    "ug_nhwc_to_nchw": (i32, [vp, vp, i64, i64, i64, i64, vp]),
-    "ug_vae_sample": (i32, [vp, i64, vp, vp, i64, i64, i64, f32, f32, vp]),
-    "ug_vae_tile_blend": (i32, [C.POINTER(VaeBlendDesc), vp]),
-    "ug_probe_mfma_bf16": (i32, [i32, i64, i64, vp, C.POINTER(C.c_double), vp]),
-    "ug_pack_latents": (i32, [vp, vp, i64, i64, i64, i64, vp]),
-    "ug_unpack_latents": (i32, [vp, vp, i64, i64, i64, i64, vp]),
-}
-# fp32 verification twins: `<name>_f32` has the signature of the function it mirrors (include/unigen_hip.h, last section)
-SIGNATURES.update({
-    "ug_transpose": (i32, [vp, i64, i64, vp, i64, i64, i64, i64, i64, i64, vp]),
-    "ug_colsum": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64, vp]),
-    "ug_colsum_workspace_bytes": (i64, [i64, i64, i64]),
-    "ug_gate_residual": (i32, [vp, i64, vp, i64, vp, i64, i64, vp, i64, i64, i64, vp]),
-    "ug_moe_gate_bwd": (i32, [vp, vp, vp, vp, i64, vp, i64, i64, i32, vp, i64, vp, vp]),
-    "ug_moe_gate_bwd_slices": (i64, [i64]),
-    "ug_gelu_tanh": (i32, [vp, vp, i64, vp]),
-    "ug_gelu_tanh_bwd": (i32, [vp, vp, vp, i64, vp]),
-    "ug_adaln_modulate_bwd": (i32, [vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, f32, vp]),
-    "ug_adaln_modulate_bwd_partials": (i64, [i64, i64]),
-    "ug_qk_rmsnorm_rope_bwd": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, i64, i32, i32, f32, vp]),
-    "ug_qk_rmsnorm_rope_bwd_partials": (i64, [i64, i32]),
-    "ug_row_lse": (i32, [vp, i64, vp, i64, i64, f32, vp]),
-    "ug_attn_prob": (i32, [vp, i64, vp, vp, i64, i64, i64, i64, f32, vp]),
-    "ug_attn_dscore": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, f32, vp]),
-    "ug_rowdot": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, vp]),
-    "ug_flash_attn_bwd_workspace_bytes": (i64, [i64, i32, i64]),
-    "ug_flash_attn_bwd": (i32, [vp, i64, i64] * 8 + [i64, i32, i64, i64, i32, f32, vp, vp, i64, vp]),
-    "ug_flash_attn_fwd_lse": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp, i64, vp]),
-})
-# optimizer step (csrc/optim.hip); the table / chunk list are device pointers, ug_optim_check_table and ug_adamw_step's groups read host memory
-SIGNATURES.update({
-    "ug_optim_check_table": (i32, [vp, i32, i32]),
-    "ug_grad_sumsq_workspace_bytes": (i64, [i64]),
-    "ug_grad_sumsq": (i32, [vp, i32, vp, i64, f32, vp, vp, i64, vp]),
-    "ug_grad_scale": (i32, [vp, i32, vp, i64, vp, vp]),
-    "ug_adamw_step": (i32, [vp, i32, vp, i64, vp, i32, vp, vp]),
-    "ug_optim_check_table_lowp": (i32, [vp, i32, i32]),
-    "ug_adamw_step_lowp": (i32, [vp, i32, vp, i64, vp, i32, vp, vp]),
-    "ug_sr_round_bf16": (i32, [vp, vp, i64, i64, C.c_uint64, C.c_uint32, C.c_uint32, i32, vp]),
-})
-# adapter gradients (csrc/lora_bwd.hip)
-SIGNATURES.update({
-    "ug_lora_wgrad_bf16": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64, vp]),
-    "ug_lora_wgrad_workspace_bytes": (i64, [i64, i64, i64]),
-})
-# flow-matching training objective (csrc/objective.hip)
-UG_FLOW_NONE, UG_FLOW_SIGMA_SQRT, UG_FLOW_COSMAP, UG_FLOW_LOGIT_NORMAL, UG_FLOW_MODE = 0, 1, 2, 3, 4
-SIGNATURES.update({
-    "ug_flow_noise": (i32, [vp, vp, vp, vp, i64, i32, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
-    "ug_flow_loss_workspace_bytes": (i64, [i64, i64]),
-    "ug_flow_loss": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
-    "ug_flow_loss_bwd": (i32, [vp, vp, vp, vp, i64, i64, vp, vp]),
-})
-# text encoders (csrc/text.hip)
-SIGNATURES.update({
-    "ug_flash_attn_fwd_bias": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i64, i32, f32, vp, i64, i32, vp]),
-    "ug_t5_rel_table": (i32, [vp, i32, i32, i32, i64, vp, vp]),
-    "ug_rmsnorm_rows": (i32, [vp, i64, vp, vp, i64, i64, i64, f32, vp]),
-    "ug_layernorm_rows": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, f32, vp]),
-    "ug_gated_gelu": (i32, [vp, i64, vp, i64, i64, i64, vp]),
-    "ug_quick_gelu": (i32, [vp, vp, i64, vp]),
-    "ug_gelu_erf": (i32, [vp, vp, i64, vp]),
-})
-# image front end (csrc/image.hip): integer / exactly specified fp32 arithmetic, no fp32 twins
-SIGNATURES.update({
-    "ug_canny_grad": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),
-    "ug_canny_nms": (i32, [vp, vp, vp, i64, i64, i64, i32, i32, vp, vp]),
-    "ug_canny_hysteresis": (i32, [vp, i64, i64, i64, vp, i64, i64, vp, C.POINTER(i32), vp]),
-    "ug_canny_max_sweeps": (i64, [i64, i64]),
-    "ug_canny_workspace_bytes": (i64, [i64, i64, i64]),
-    "ug_canny_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, i32, i32, vp, i64, i64, vp, i64, C.POINTER(i32), vp]),
-    "ug_img_resize_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, i32, vp, vp]),
-    "ug_img_rgb_to_l": (i32, [vp, i64, i64, i64, i64, i64, vp, i64, i64, vp]),
-    "ug_img_u8_to_chw": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i32, i32, i32, vp]),
-    "ug_img_chw_to_u8": (i32, [vp, i32, i64, i32, i64, i64, vp, i64, i64, i32, vp]),
-    "ug_img_blur_workspace_bytes": (i64, [i64, i64, i64, i32]),
-    "ug_img_box_blur_u8": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
-})
-# depth condition (csrc/depth.hip); mean / std of ug_img_u8_to_patches are host arrays of 3 floats
-SIGNATURES.update({
-    "ug_img_u8_to_patches": (i32, [vp, i64, i64, i64, i64, i64, i32, i32, C.c_double, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, vp]),
-    "ug_relu": (i32, [vp, vp, i64, vp]),
-    "ug_deconv_scatter_nhwc": (i32, [vp, i64, vp, vp, i64, i64, i64, i32, i64, i64, vp]),
-    "ug_bilinear_nhwc": (i32, [vp, i64, i64, i64, i64, vp, i64, i64, i32, vp]),
-    "ug_depth_head_out": (i32, [vp, i64, i64, i64, vp, vp, f32, i32, vp, vp]),
-    "ug_bicubic_f32": (i32, [vp, i64, i64, i64, vp, i64, i64, vp]),
-    "ug_minmax_workspace_bytes": (i64, [i64, i64]),
-    "ug_minmax_to_u8": (i32, [vp, i64, i64, vp, i32, vp, i64, vp]),
-})
-# Sana transformer block (csrc/sana.hip)
-SIGNATURES.update({
-    "ug_linear_attn_workspace_bytes": (i64, [i64, i64, i64]),
-    "ug_linear_attn": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i32, i64, i32, vp, vp]),
-    "ug_glu_dwconv3x3": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
-})
-_F32_TWINS = {"ug_linear_attn_f32": "ug_linear_attn", "ug_glu_dwconv3x3_f32": "ug_glu_dwconv3x3", "ug_img_u8_to_patches_f32": "ug_img_u8_to_patches", "ug_relu_f32": "ug_relu", "ug_deconv_scatter_nhwc_f32": "ug_deconv_scatter_nhwc",
-              "ug_bilinear_nhwc_f32": "ug_bilinear_nhwc", "ug_depth_head_out_f32": "ug_depth_head_out",
-              "ug_flash_attn_fwd_bias_f32": "ug_flash_attn_fwd_bias", "ug_t5_rel_table_f32": "ug_t5_rel_table", "ug_rmsnorm_rows_f32": "ug_rmsnorm_rows",
-              "ug_layernorm_rows_f32": "ug_layernorm_rows", "ug_gated_gelu_f32": "ug_gated_gelu", "ug_quick_gelu_f32": "ug_quick_gelu", "ug_gelu_erf_f32": "ug_gelu_erf",
-              "ug_flow_noise_f32": "ug_flow_noise", "ug_flow_loss_f32": "ug_flow_loss", "ug_flow_loss_bwd_f32": "ug_flow_loss_bwd",
-              "ug_lora_wgrad_f32": "ug_lora_wgrad_bf16","ug_gate_residual_f32": "ug_gate_residual", "ug_moe_gate_bwd_f32": "ug_moe_gate_bwd", "ug_transpose_f32": "ug_transpose", "ug_colsum_f32": "ug_colsum", "ug_gelu_tanh_f32": "ug_gelu_tanh", "ug_gelu_tanh_bwd_f32": "ug_gelu_tanh_bwd",
-              "ug_adaln_modulate_bwd_f32": "ug_adaln_modulate_bwd", "ug_qk_rmsnorm_rope_bwd_f32": "ug_qk_rmsnorm_rope_bwd",
-              "ug_attn_prob_f32": "ug_attn_prob", "ug_attn_dscore_f32": "ug_attn_dscore", "ug_rowdot_f32": "ug_rowdot",
-              "ug_gemm_f32": "ug_gemm_bf16", "ug_small_linear_f32": "ug_small_linear_bf16", "ug_adaln_modulate_f32": "ug_adaln_modulate",
-              "ug_qk_rmsnorm_rope_f32": "ug_qk_rmsnorm_rope", "ug_flash_attn_fwd_f32": "ug_flash_attn_fwd", "ug_flash_attn_fwd_wide_f32": "ug_flash_attn_fwd_wide", "ug_timestep_embed_f32": "ug_timestep_embed",
-              "ug_euler_step_f32": "ug_euler_step", "ug_cfg_combine_f32": "ug_cfg_combine", "ug_add_f32": "ug_add_bf16",
-              "ug_add_rowbcast_f32_f32": "ug_add_rowbcast_f32", "ug_gather_rows_f32": "ug_gather_rows", "ug_moe_gate_top1_f32": "ug_moe_gate_top1",
-              "ug_moe_dispatch_modulate_f32": "ug_moe_dispatch_modulate", "ug_moe_combine_f32": "ug_moe_combine",
-              "ug_moe_gate_top2_f32": "ug_moe_gate_top2", "ug_moe_gate_topk_f32": "ug_moe_gate_topk", "ug_moe_combine_topk_f32": "ug_moe_combine_topk",
-              "ug_pack_latents_f32": "ug_pack_latents", "ug_unpack_latents_f32": "ug_unpack_latents",
-              "ug_conv2d_nhwc_f32": "ug_conv2d_nhwc", "ug_groupnorm_nhwc_f32": "ug_groupnorm_nhwc", "ug_softmax_rows_f32": "ug_softmax_rows",
-              "ug_nchw_to_nhwc_f32": "ug_nchw_to_nhwc", "ug_nhwc_to_nchw_f32": "ug_nhwc_to_nchw", "ug_vae_sample_f32": "ug_vae_sample",
-              "ug_vae_tile_blend_f32": "ug_vae_tile_blend"}
-for _twin, _base in _F32_TWINS.items():
-    SIGNATURES[_twin] = SIGNATURES[_base]
+def bind(cdll: C.CDLL) -> C.CDLL:
+    """Give every entry point of a build of the library its restype / argtypes."""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(cdll, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    return cdll
+
 
 _lib = None
-
-
-class UniGenHipError(RuntimeError):
-    pass
 
 
 def load() -> C.CDLL:
@@ -265,7 +147,6 @@ def load() -> C.CDLL:
         if os.environ.get("UG_LIB_PATH"):
             raise UniGenHipError(f"UG_LIB_PATH={LIB_PATH} not found (probe library: `python -m unigen_amd.build --probe`)")
         try:
-            from . import build as _build
             _build.build()          # serialised across processes by a file lock; outputs appear atomically (os.replace)
         except Exception as e:      # no hipcc, compile error: fail loudly, never fall back
             raise UniGenHipError(f"{LIB_PATH} not found and `python -m unigen_amd.build` (hipcc --offload-arch=gfx950) failed: {e}. "
@@ -274,16 +155,18 @@ def load() -> C.CDLL:
     # that both resolve to ONE runtime (loaded the other way round, the system runtime and torch's each keep their own device state and
     # launches fail with "no ROCm-capable device is detected").
     import torch  # noqa: F401
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    _lib = bind(C.CDLL(LIB_PATH))
+    return _lib
 
 
 def check(rc: int, what: str) -> None:
     if rc != UG_OK:
         msg = load().ug_last_error()
         raise UniGenHipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+
+
+def call(name: str, *args) -> None:
+    """Call the entry point `name` of the loaded library; a status other than UG_OK raises with the library's message."""
+    rc = getattr(load(), name)(*args)
+    if rc:
+        check(rc, name)

@@ -92,11 +92,15 @@ def _act(t: torch.Tensor, name: str):
 
 def _fn(base: str, dt):
     """The C-ABI function for activation dtype `dt`: `base` itself for bf16, its `_f32` twin otherwise."""
-    lib = L.load()
-    return getattr(lib, base) if dt == bf16 else getattr(lib, _TWIN[base])
+    return getattr(L.load(), base if dt == bf16 else L.F32_TWIN_OF[base])
 
 
-_TWIN = {v: k for k, v in L._F32_TWINS.items()}
+def _call(base: str, dt, *args) -> None:
+    """Call `base` (bf16) or its `_f32` twin (any other dtype); a failure raises under the name of the symbol that was called."""
+    name = base if dt == bf16 else L.F32_TWIN_OF[base]
+    rc = getattr(L.load(), name)(*args)         # not through L.call: one Python frame per launch matters to the launch-bound batch-1 forwards
+    if rc:
+        L.check(rc, name)
 
 
 class RowMap:
@@ -207,7 +211,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: to
         _chk(lora_t, "lora_t", dt); _chk(lora_b, "lora_b", dt)
         d.lora_T, d.ldt, d.lora_B, d.ldb, d.lora_r = lora_t.data_ptr(), lora_t.stride(-2), lora_b.data_ptr(), lora_b.stride(-2), lora_b.shape[-1]
     ev = _timer.begin("gemm") if _timer is not None else None
-    L.check(_fn("ug_gemm_bf16", dt)(C.byref(d), stream), "ug_gemm_bf16")
+    _call("ug_gemm_bf16", dt, C.byref(d), stream)
     if ev is not None:
         _timer.end("gemm", 2.0 * M * N * (K + (d.lora_r or 0)) * max(groups, 1), ev, tag=(M, N, K, max(groups, 1), epilogue))
     return out
@@ -224,14 +228,12 @@ def small_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
         _chk(residual, "residual", dt)
     M, K = x.shape
     N = w.shape[0]
-    fn = _fn("ug_small_linear_bf16", dt)
     step = 16 if dt == bf16 else 64     # the bf16 kernel keeps up to 16 rows of x in LDS; more rows re-stream the weights
     for m0 in range(0, M, step):
         mm = min(step, M - m0)
         r = residual[m0:] if residual is not None else None
-        L.check(fn(x[m0:].data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _p(bias), _p(r),
-                   residual.stride(0) if residual is not None else 0, out[m0:].data_ptr(), out.stride(0),
-                   mm, N, K, 1 if silu_in else 0, _stream()), "ug_small_linear_bf16")
+        _call("ug_small_linear_bf16", dt, x[m0:].data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _p(bias), _p(r),
+              residual.stride(0) if residual is not None else 0, out[m0:].data_ptr(), out.stride(0), mm, N, K, 1 if silu_in else 0, _stream())
     return out
 
 
@@ -239,9 +241,8 @@ def adaln_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, ou
                    rows_per_sample: int, mod_ld: int, ldx: Optional[int] = None, x_map: RowMap = IDENT, eps: float = 1e-6) -> torch.Tensor:
     dt = _act(x, "x")
     _chk(shift, "shift", dt); _chk(scale, "scale", dt); _chk(out, "out", dt)
-    L.check(_fn("ug_adaln_modulate", dt)(x.data_ptr(), ldx if ldx is not None else x.stride(-2), x_map.rpb, x_map.bstride,
-                                       shift.data_ptr(), scale.data_ptr(), mod_ld, rows_per_sample, out.data_ptr(),
-                                       out.stride(-2), rows, D, eps, _stream()), "ug_adaln_modulate")
+    _call("ug_adaln_modulate", dt, x.data_ptr(), ldx if ldx is not None else x.stride(-2), x_map.rpb, x_map.bstride, shift.data_ptr(), scale.data_ptr(), mod_ld,
+          rows_per_sample, out.data_ptr(), out.stride(-2), rows, D, eps, _stream())
     return out
 
 
@@ -259,8 +260,8 @@ def qk_rmsnorm_rope(buf: torch.Tensor, *, batches: int, rows_per_batch: int, ld:
         _chk(cos, "cos", torch.float32); _chk(sin, "sin", torch.float32)
         assert cos.shape[0] >= pos_offset + rows_per_batch and cos.shape[1] == dh and cos.is_contiguous() and sin.is_contiguous(), \
             (cos.shape, pos_offset, rows_per_batch, dh)
-    L.check(_fn("ug_qk_rmsnorm_rope", dt)(buf.data_ptr(), ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh,
-                                        _p(wq_a), _p(wk_a), _p(wq_b), _p(wk_b), split, _p(cos), _p(sin), eps, _stream()), "ug_qk_rmsnorm_rope")
+    _call("ug_qk_rmsnorm_rope", dt, buf.data_ptr(), ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh, _p(wq_a), _p(wk_a),
+          _p(wq_b), _p(wk_b), split, _p(cos), _p(sin), eps, _stream())
     return buf
 
 
@@ -278,19 +279,16 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
         raise L.UniGenHipError("flash_attn: lse= is not available at dh = 512 (ug_flash_attn_fwd_wide is forward only: there is no backward at this head width)")
     ev = _timer.begin("attn") if _timer is not None else None
     if dh == 512:
-        L.check(_fn("ug_flash_attn_fwd_wide", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1],
-                                                v.data_ptr(), v_strides[0], v_strides[1], out.data_ptr(), o_strides[0], o_strides[1],
-                                                batches, heads, Lq, Lkv, dh, scale, _stream()), "ug_flash_attn_fwd_wide")
+        _call("ug_flash_attn_fwd_wide", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+              v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, _stream())
     elif lse is not None:
         _chk(lse, "lse", torch.float32)
         assert dt == bf16 and lse.is_contiguous() and lse.shape[0] == batches and lse.shape[1] == heads and lse.shape[2] >= Lq
-        L.check(L.load().ug_flash_attn_fwd_lse(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1],
-                                               v.data_ptr(), v_strides[0], v_strides[1], out.data_ptr(), o_strides[0], o_strides[1],
-                                               batches, heads, Lq, Lkv, dh, scale, lse.data_ptr(), lse.shape[2], _stream()), "ug_flash_attn_fwd_lse")
+        L.call("ug_flash_attn_fwd_lse", q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+               v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, lse.data_ptr(), lse.shape[2], _stream())
     else:
-        L.check(_fn("ug_flash_attn_fwd", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1],
-                                           v.data_ptr(), v_strides[0], v_strides[1], out.data_ptr(), o_strides[0], o_strides[1],
-                                           batches, heads, Lq, Lkv, dh, scale, _stream()), "ug_flash_attn_fwd")
+        _call("ug_flash_attn_fwd", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+              v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, _stream())
     if ev is not None:
         _timer.end("attn", 4.0 * batches * heads * Lq * Lkv * dh, ev, tag=(batches, heads, Lq, Lkv, dh))
     return out
@@ -299,7 +297,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Ten
 def timestep_embed(t: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     _chk(t, "t", torch.float32)
     dt = _act(out, "out")
-    L.check(_fn("ug_timestep_embed", dt)(t.data_ptr(), out.data_ptr(), out.stride(0), t.shape[0], out.shape[1], _stream()), "ug_timestep_embed")
+    _call("ug_timestep_embed", dt, t.data_ptr(), out.data_ptr(), out.stride(0), t.shape[0], out.shape[1], _stream())
     return out
 
 
@@ -307,7 +305,7 @@ def euler_step(x: torch.Tensor, v: torch.Tensor, dt: float) -> torch.Tensor:
     adt = _act(x, "x")
     _chk(v, "v", adt)
     assert x.is_contiguous() and v.is_contiguous() and x.numel() == v.numel()
-    L.check(_fn("ug_euler_step", adt)(x.data_ptr(), v.data_ptr(), dt, x.numel(), _stream()), "ug_euler_step")
+    _call("ug_euler_step", adt, x.data_ptr(), v.data_ptr(), dt, x.numel(), _stream())
     return x
 
 
@@ -315,7 +313,7 @@ def cfg_combine(uncond: torch.Tensor, text: torch.Tensor, guidance_scale: float,
     dt = _act(uncond, "uncond")
     _chk(text, "text", dt); _chk(out, "out", dt)
     assert uncond.is_contiguous() and text.is_contiguous() and out.is_contiguous() and uncond.numel() == text.numel() == out.numel()
-    L.check(_fn("ug_cfg_combine", dt)(uncond.data_ptr(), text.data_ptr(), guidance_scale, out.data_ptr(), out.numel(), _stream()), "ug_cfg_combine")
+    _call("ug_cfg_combine", dt, uncond.data_ptr(), text.data_ptr(), guidance_scale, out.data_ptr(), out.numel(), _stream())
     return out
 
 
@@ -325,7 +323,7 @@ def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     D = a.shape[-1]
     rows = a.numel() // D
     a2, b2, o2 = a.reshape(rows, D), b.reshape(rows, D), out.view(rows, D)
-    L.check(_fn("ug_add_bf16", dt)(a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), o2.data_ptr(), o2.stride(0), rows, D, _stream()), "ug_add_bf16")
+    _call("ug_add_bf16", dt, a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), o2.data_ptr(), o2.stride(0), rows, D, _stream())
     return out
 
 
@@ -335,7 +333,7 @@ def add_rowbcast_f32(x: torch.Tensor, table: torch.Tensor, rows_per_batch: int) 
     _chk(table, "table", torch.float32)
     rows, D = x.shape
     assert table.shape == (rows_per_batch, D)
-    L.check(_fn("ug_add_rowbcast_f32", dt)(x.data_ptr(), x.stride(0), table.data_ptr(), table.stride(0), rows, rows_per_batch, D, _stream()), "ug_add_rowbcast_f32")
+    _call("ug_add_rowbcast_f32", dt, x.data_ptr(), x.stride(0), table.data_ptr(), table.stride(0), rows, rows_per_batch, D, _stream())
     return x
 
 
@@ -345,7 +343,7 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torc
     _chk(idx, "idx", torch.int32); _chk(out, "out", dt)
     n, W = out.shape
     assert idx.numel() == n and src.shape[1] == W and idx.is_contiguous()
-    L.check(_fn("ug_gather_rows", dt)(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), n, W, _stream()), "ug_gather_rows")
+    _call("ug_gather_rows", dt, src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), n, W, _stream())
     return out
 
 
@@ -355,8 +353,7 @@ def moe_gate_top1(x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor, gates: tor
     S, D = x.shape
     E = wg.shape[0]
     assert x.stride(0) == c.stride(0) and wg.is_contiguous() and gates.is_contiguous()
-    L.check(_fn("ug_moe_gate_top1", dt)(x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, gates.data_ptr(), idx.data_ptr(), _stream()),
-            "ug_moe_gate_top1")
+    _call("ug_moe_gate_top1", dt, x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, gates.data_ptr(), idx.data_ptr(), _stream())
 
 
 def moe_gate_bwd(gates: torch.Tensor, dgates: torch.Tensor, x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor):
@@ -368,8 +365,8 @@ def moe_gate_bwd(gates: torch.Tensor, dgates: torch.Tensor, x: torch.Tensor, c: 
     assert x.stride(0) == c.stride(0) and wg.is_contiguous() and gates.is_contiguous() and dgates.is_contiguous() and gates.shape == dgates.shape == (S, E)
     dx = torch.empty(S, D, device=x.device, dtype=dt)
     part = torch.empty(int(L.load().ug_moe_gate_bwd_slices(S)), E, D, device=x.device, dtype=torch.float32)
-    L.check(_fn("ug_moe_gate_bwd", dt)(gates.data_ptr(), dgates.data_ptr(), x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, dx.data_ptr(), D,
-                                     part.data_ptr(), _stream()), "ug_moe_gate_bwd")
+    _call("ug_moe_gate_bwd", dt, gates.data_ptr(), dgates.data_ptr(), x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, dx.data_ptr(), D,
+          part.data_ptr(), _stream())
     return dx, part.sum(0).to(dt)          # the kernel's per-slice fp32 partials, added in a fixed order
 
 
@@ -379,8 +376,8 @@ def moe_capacity_rts(gates, idx, uniform, capacity: int, slot, token_of_slot, ex
     _chk(exp_counts, "exp_counts", torch.int64); _chk(l_aux, "l_aux", torch.float32)
     S, E = gates.shape
     assert uniform.shape == (S, E) and uniform.is_contiguous() and token_of_slot.numel() == E * capacity
-    L.check(L.load().ug_moe_capacity_rts(gates.data_ptr(), idx.data_ptr(), uniform.data_ptr(), S, E, capacity, slot.data_ptr(),
-                                         token_of_slot.data_ptr(), exp_counts.data_ptr(), l_aux.data_ptr(), _stream()), "ug_moe_capacity_rts")
+    L.call("ug_moe_capacity_rts", gates.data_ptr(), idx.data_ptr(), uniform.data_ptr(), S, E, capacity, slot.data_ptr(), token_of_slot.data_ptr(),
+           exp_counts.data_ptr(), l_aux.data_ptr(), _stream())
 
 
 def moe_gate_top2(x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor, noise: Optional[torch.Tensor], gates: torch.Tensor, idx: torch.Tensor) -> None:
@@ -392,8 +389,7 @@ def moe_gate_top2(x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor, noise: Opt
     assert x.stride(0) == c.stride(0) and wg.is_contiguous() and gates.is_contiguous() and idx.is_contiguous() and idx.shape == (2, S)
     if noise is not None:
         _chk(noise, "noise", torch.float32); assert noise.shape == (S, E) and noise.is_contiguous()
-    L.check(_fn("ug_moe_gate_top2", dt)(x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, _p(noise), gates.data_ptr(), idx.data_ptr(), _stream()),
-            "ug_moe_gate_top2")
+    _call("ug_moe_gate_top2", dt, x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, _p(noise), gates.data_ptr(), idx.data_ptr(), _stream())
 
 
 def moe_capacity_top2(gates, idx, capacity: int, slot, token_of_slot, weights, exp_counts, l_aux) -> None:
@@ -402,8 +398,8 @@ def moe_capacity_top2(gates, idx, capacity: int, slot, token_of_slot, weights, e
     S, E = gates.shape
     assert idx.shape == slot.shape == weights.shape == (2, S) and idx.is_contiguous() and slot.is_contiguous() and weights.is_contiguous()
     assert token_of_slot.numel() == E * capacity and token_of_slot.is_contiguous() and gates.is_contiguous()
-    L.check(L.load().ug_moe_capacity_top2(gates.data_ptr(), idx.data_ptr(), S, E, capacity, slot.data_ptr(), token_of_slot.data_ptr(), weights.data_ptr(),
-                                          exp_counts.data_ptr(), l_aux.data_ptr(), _stream()), "ug_moe_capacity_top2")
+    L.call("ug_moe_capacity_top2", gates.data_ptr(), idx.data_ptr(), S, E, capacity, slot.data_ptr(), token_of_slot.data_ptr(), weights.data_ptr(),
+           exp_counts.data_ptr(), l_aux.data_ptr(), _stream())
 
 
 def moe_gate_topk(x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor, K: int, gates: torch.Tensor, logits: torch.Tensor, idx: torch.Tensor) -> None:
@@ -414,8 +410,8 @@ def moe_gate_topk(x: torch.Tensor, c: torch.Tensor, wg: torch.Tensor, K: int, ga
     E = wg.shape[0]
     assert c.shape == x.shape and wg.shape[1] == D and gates.shape == (S, E) and logits.shape == (S, E) and idx.shape == (K, S) and idx.is_contiguous()
     assert x.stride(0) == c.stride(0) and gates.is_contiguous() and logits.is_contiguous()
-    L.check(_fn("ug_moe_gate_topk", dt)(x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, K, gates.data_ptr(), logits.data_ptr(), idx.data_ptr(),
-                                        _stream()), "ug_moe_gate_topk")
+    _call("ug_moe_gate_topk", dt, x.data_ptr(), c.data_ptr(), x.stride(0), wg.data_ptr(), S, D, E, K, gates.data_ptr(), logits.data_ptr(), idx.data_ptr(),
+          _stream())
 
 
 def moe_capacity_topk(gates, logits, idx, capacity: int, slot, token_of_slot, weights, exp_counts, l_aux) -> None:
@@ -426,8 +422,8 @@ def moe_capacity_topk(gates, logits, idx, capacity: int, slot, token_of_slot, we
                   (exp_counts, torch.int64), (l_aux, torch.float32)):
         assert t.is_cuda and t.dtype == dt and t.is_contiguous()
     assert logits.shape == (S, E) and idx.shape == (K, S) and slot.shape == (K, S) and weights.shape == (K, S) and token_of_slot.shape == (E, capacity)
-    L.check(L.load().ug_moe_capacity_topk(gates.data_ptr(), logits.data_ptr(), idx.data_ptr(), S, E, K, capacity, slot.data_ptr(), token_of_slot.data_ptr(),
-                                          weights.data_ptr(), exp_counts.data_ptr(), l_aux.data_ptr(), _stream()), "ug_moe_capacity_topk")
+    L.call("ug_moe_capacity_topk", gates.data_ptr(), logits.data_ptr(), idx.data_ptr(), S, E, K, capacity, slot.data_ptr(), token_of_slot.data_ptr(),
+           weights.data_ptr(), exp_counts.data_ptr(), l_aux.data_ptr(), _stream())
 
 
 def moe_combine_topk(yh, yc, weights, idx, slot, out, *, E: int, capacity: int, xs=None, cs=None, s_map: RowMap = IDENT, accumulate: bool = False) -> torch.Tensor:
@@ -441,9 +437,8 @@ def moe_combine_topk(yh, yc, weights, idx, slot, out, *, E: int, capacity: int, 
     assert K == 1 or (idx.stride(0) == ks and slot.stride(0) == ks)
     if xs is not None:
         _chk(xs, "xs", dt); _chk(cs, "cs", dt); assert xs.stride(-2) == cs.stride(-2)
-    L.check(_fn("ug_moe_combine_topk", dt)(yh.data_ptr(), yc.data_ptr(), weights.data_ptr(), idx.data_ptr(), slot.data_ptr(), K, ks, E, capacity, _p(xs), _p(cs),
-                                            xs.stride(-2) if xs is not None else 0, s_map.rpb, s_map.bstride, out.data_ptr(), out.stride(-2), S, D,
-                                            1 if accumulate else 0, _stream()), "ug_moe_combine_topk")
+    _call("ug_moe_combine_topk", dt, yh.data_ptr(), yc.data_ptr(), weights.data_ptr(), idx.data_ptr(), slot.data_ptr(), K, ks, E, capacity, _p(xs), _p(cs),
+          xs.stride(-2) if xs is not None else 0, s_map.rpb, s_map.bstride, out.data_ptr(), out.stride(-2), S, D, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -458,8 +453,8 @@ def moe_dispatch_modulate(x, add_, mod, token_of_slot, out, *, E: int, capacity:
         _chk(mod, "mod", dt)
     if add_ is not None:
         _chk(add_, "add", dt); assert add_.is_contiguous()
-    L.check(_fn("ug_moe_dispatch_modulate", dt)(x.data_ptr(), x.stride(-2), _p(add_), _p(mod), mod_estride, mod_bstride, token_of_slot.data_ptr(),
-                                                 E, capacity, tokens_per_sample, D, out.data_ptr(), _stream()), "ug_moe_dispatch_modulate")
+    _call("ug_moe_dispatch_modulate", dt, x.data_ptr(), x.stride(-2), _p(add_), _p(mod), mod_estride, mod_bstride, token_of_slot.data_ptr(), E, capacity,
+          tokens_per_sample, D, out.data_ptr(), _stream())
     return out
 
 
@@ -470,9 +465,8 @@ def moe_combine(yh, yc, gates, idx, slot, out, *, E: int, capacity: int, xs=None
     S, D = out.shape[-2], out.shape[-1]
     if xs is not None:
         _chk(xs, "xs", dt); _chk(cs, "cs", dt); assert xs.stride(-2) == cs.stride(-2)
-    L.check(_fn("ug_moe_combine", dt)(yh.data_ptr(), yc.data_ptr(), gates.data_ptr(), idx.data_ptr(), slot.data_ptr(), E, capacity, _p(xs), _p(cs),
-                                       xs.stride(-2) if xs is not None else 0, s_map.rpb, s_map.bstride, out.data_ptr(), out.stride(-2), S, D,
-                                       1 if accumulate else 0, _stream()), "ug_moe_combine")
+    _call("ug_moe_combine", dt, yh.data_ptr(), yc.data_ptr(), gates.data_ptr(), idx.data_ptr(), slot.data_ptr(), E, capacity, _p(xs), _p(cs),
+          xs.stride(-2) if xs is not None else 0, s_map.rpb, s_map.bstride, out.data_ptr(), out.stride(-2), S, D, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -484,7 +478,7 @@ def pack_latents(latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> t
     if out is None:
         out = torch.empty(B, (H // 2) * (W // 2), Cc * 4, device=latents.device, dtype=dt)
     _chk(out, "out", dt); assert out.is_contiguous() and out.numel() == latents.numel()
-    L.check(_fn("ug_pack_latents", dt)(latents.data_ptr(), out.data_ptr(), B, Cc, H, W, _stream()), "ug_pack_latents")
+    _call("ug_pack_latents", dt, latents.data_ptr(), out.data_ptr(), B, Cc, H, W, _stream())
     return out
 
 
@@ -497,7 +491,7 @@ def unpack_latents(packed: torch.Tensor, H: int, W: int, out: Optional[torch.Ten
     if out is None:
         out = torch.empty(B, ch // 4, H, W, device=packed.device, dtype=dt)
     _chk(out, "out", dt); assert out.is_contiguous()
-    L.check(_fn("ug_unpack_latents", dt)(packed.data_ptr(), out.data_ptr(), B, ch // 4, H, W, _stream()), "ug_unpack_latents")
+    _call("ug_unpack_latents", dt, packed.data_ptr(), out.data_ptr(), B, ch // 4, H, W, _stream())
     return out
 
 
@@ -510,8 +504,7 @@ def probe_mfma_peak(device, shape: int = 1, seconds: float = 0.4) -> float:
     scratch = torch.empty(blocks * 256, dtype=torch.float32, device=device)
     fl = C.c_double(0.0)
     iters = 100_000
-    lib = L.load()
-    launch = lambda: L.check(lib.ug_probe_mfma_bf16(shape, blocks, iters, scratch.data_ptr(), C.byref(fl), _stream()), "ug_probe_mfma_bf16")
+    launch = lambda: L.call("ug_probe_mfma_bf16", shape, blocks, iters, scratch.data_ptr(), C.byref(fl), _stream())
     launch()
     torch.cuda.synchronize(device)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -560,7 +553,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
     d.KH, d.KW, d.stride, d.pad_t, d.pad_l, d.up = KH, KW, stride, pad_t, pad_l, up
     zp = _zero_page(x.device)
     d.zero_page, d.zero_page_bytes = zp.data_ptr(), zp.numel()
-    L.check(_fn("ug_conv2d_nhwc", dt)(C.byref(d), _stream()), "ug_conv2d_nhwc")
+    _call("ug_conv2d_nhwc", dt, C.byref(d), _stream())
     return out
 
 
@@ -579,8 +572,8 @@ def groupnorm_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         _gn_ws[key] = ws
-    L.check(_fn("ug_groupnorm_nhwc", dt)(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, HW, Cc, groups, eps,
-                                          1 if silu else 0, _stream()), "ug_groupnorm_nhwc")
+    _call("ug_groupnorm_nhwc", dt, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, HW, Cc, groups, eps,
+          1 if silu else 0, _stream())
     return out
 
 
@@ -589,7 +582,7 @@ def softmax_rows(scores: torch.Tensor, probs: torch.Tensor, scale: float) -> tor
     _chk(scores, "scores", torch.float32)
     dt = _act(probs, "probs")
     rows, cols = scores.shape
-    L.check(_fn("ug_softmax_rows", dt)(scores.data_ptr(), scores.stride(0), probs.data_ptr(), probs.stride(0), rows, cols, scale, _stream()), "ug_softmax_rows")
+    _call("ug_softmax_rows", dt, scores.data_ptr(), scores.stride(0), probs.data_ptr(), probs.stride(0), rows, cols, scale, _stream())
     return probs
 
 
@@ -599,7 +592,7 @@ def nchw_to_nhwc(x: torch.Tensor, Cp: int, div: float = 0.0, add: float = 0.0) -
     B, Cc, H, W = x.shape
     x = x.contiguous()
     out = torch.empty(B * H * W, Cp, device=x.device, dtype=dt)
-    L.check(_fn("ug_nchw_to_nhwc", dt)(x.data_ptr(), out.data_ptr(), B, Cc, H * W, Cp, div, add, _stream()), "ug_nchw_to_nhwc")
+    _call("ug_nchw_to_nhwc", dt, x.data_ptr(), out.data_ptr(), B, Cc, H * W, Cp, div, add, _stream())
     return out
 
 
@@ -608,7 +601,7 @@ def nhwc_to_nchw(x: torch.Tensor, B: int, Cc: int, H: int, W: int) -> torch.Tens
     dt = _act(x, "x")
     assert x.is_contiguous() and x.shape[0] == B * H * W and x.shape[1] >= Cc
     out = torch.empty(B, Cc, H, W, device=x.device, dtype=dt)
-    L.check(_fn("ug_nhwc_to_nchw", dt)(x.data_ptr(), out.data_ptr(), B, Cc, H * W, x.shape[1], _stream()), "ug_nhwc_to_nchw")
+    _call("ug_nhwc_to_nchw", dt, x.data_ptr(), out.data_ptr(), B, Cc, H * W, x.shape[1], _stream())
     return out
 
 
@@ -618,7 +611,7 @@ def vae_sample(moments: torch.Tensor, noise: torch.Tensor, *, B: int, latent: in
     _chk(noise, "noise", dt)
     assert moments.is_contiguous() and noise.is_contiguous() and noise.numel() == B * latent * H * W
     z = torch.empty(B, latent, H, W, device=moments.device, dtype=dt)
-    L.check(_fn("ug_vae_sample", dt)(moments.data_ptr(), moments.shape[1], noise.data_ptr(), z.data_ptr(), B, latent, H * W, shift, scale, _stream()), "ug_vae_sample")
+    _call("ug_vae_sample", dt, moments.data_ptr(), moments.shape[1], noise.data_ptr(), z.data_ptr(), B, latent, H * W, shift, scale, _stream())
     return z
 
 
@@ -655,7 +648,7 @@ def vae_tile_blend(tile: torch.Tensor, upper: Optional[torch.Tensor], left: Opti
     d.out = out.data_ptr()
     d.ob, d.oc, d.oy, d.ox = out.stride()
     d.B, d.C, d.h, d.w, d.E = B, Cc, h, w, int(extent)
-    L.check(_fn("ug_vae_tile_blend", dt)(C.byref(d), _stream()), "ug_vae_tile_blend")
+    _call("ug_vae_tile_blend", dt, C.byref(d), _stream())
     return out
 
 
@@ -675,8 +668,7 @@ def transpose(src: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor
         raise ValueError("transpose: at most one batch dimension")
     bstride = src.stride(0) if lead else 0
     out = torch.empty(*lead, cols, rows_pad, device=src.device, dtype=dt)
-    L.check(_fn("ug_transpose", dt)(src.data_ptr(), src.stride(-2), bstride, out.data_ptr(), rows_pad, cols * rows_pad, batch, rows, cols, rows_pad, _stream()),
-            "ug_transpose")
+    _call("ug_transpose", dt, src.data_ptr(), src.stride(-2), bstride, out.data_ptr(), rows_pad, cols * rows_pad, batch, rows, cols, rows_pad, _stream())
     return out
 
 
@@ -689,8 +681,8 @@ def colsum(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, rows_per_group:
         _chk(b, "b", dt)
     out = torch.empty(rows // g, cols, device=a.device, dtype=dt)
     ws = torch.empty(int(L.load().ug_colsum_workspace_bytes(rows, cols, g)), device=a.device, dtype=torch.uint8)
-    L.check(_fn("ug_colsum", dt)(a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0, out.data_ptr(), cols, rows, cols, g, alpha,
-                                 ws.data_ptr(), ws.numel(), _stream()), "ug_colsum")
+    _call("ug_colsum", dt, a.data_ptr(), a.stride(0), _p(b), b.stride(0) if b is not None else 0, out.data_ptr(), cols, rows, cols, g, alpha, ws.data_ptr(),
+          ws.numel(), _stream())
     return out
 
 
@@ -709,8 +701,8 @@ def lora_wgrad(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = N
     if tuple(out.shape) != (R, J):
         raise ValueError(f"lora_wgrad: out must be [{R}, {J}], got {tuple(out.shape)}")
     ws = torch.empty(int(L.load().ug_lora_wgrad_workspace_bytes(M, R, J)), device=p.device, dtype=torch.uint8)
-    L.check(_fn("ug_lora_wgrad_bf16", dt)(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0), M, R, J, alpha,
-                                          ws.data_ptr(), ws.numel(), _stream()), "ug_lora_wgrad_bf16")
+    _call("ug_lora_wgrad_bf16", dt, p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0), M, R, J, alpha, ws.data_ptr(),
+          ws.numel(), _stream())
     return out
 
 
@@ -718,7 +710,7 @@ def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
     dt = _act(x, "x")
     x = x.contiguous()
     out = torch.empty_like(x)
-    L.check(_fn("ug_gelu_tanh", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_gelu_tanh")
+    _call("ug_gelu_tanh", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -727,7 +719,7 @@ def gelu_tanh_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     x, dy = x.contiguous(), dy.contiguous()
     _chk(dy, "dy", dt)
     out = torch.empty_like(x)
-    L.check(_fn("ug_gelu_tanh_bwd", dt)(x.data_ptr(), dy.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_gelu_tanh_bwd")
+    _call("ug_gelu_tanh_bwd", dt, x.data_ptr(), dy.data_ptr(), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -739,8 +731,8 @@ def adaln_modulate_bwd(x: torch.Tensor, dy: torch.Tensor, scale: torch.Tensor, *
     samples = rows // rows_per_sample
     dx = torch.empty(rows, D, device=x.device, dtype=dt)
     part = torch.empty(samples, int(L.load().ug_adaln_modulate_bwd_partials(rows, rows_per_sample)), 2, D, device=x.device, dtype=torch.float32)
-    L.check(_fn("ug_adaln_modulate_bwd", dt)(x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), scale.data_ptr(), scale.stride(0), rows_per_sample,
-                                           dx.data_ptr(), D, part.data_ptr(), rows, D, eps, _stream()), "ug_adaln_modulate_bwd")
+    _call("ug_adaln_modulate_bwd", dt, x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), scale.data_ptr(), scale.stride(0), rows_per_sample,
+          dx.data_ptr(), D, part.data_ptr(), rows, D, eps, _stream())
     sums = part.sum(1).to(dt) if part.shape[1] > 1 else part[:, 0].to(dt)         # the kernel's per-sample partials, added in a fixed order
     return dx, sums[:, 0], sums[:, 1]
 
@@ -756,8 +748,8 @@ def qk_rmsnorm_rope_bwd(x: torch.Tensor, dy: torch.Tensor, w: Optional[torch.Ten
     if cos is not None:
         _chk(cos, "cos", torch.float32); _chk(sin, "sin", torch.float32)
         assert cos.shape[0] >= pos_offset + rows_per_batch and cos.shape[1] == dh and cos.is_contiguous() and sin.is_contiguous()
-    L.check(_fn("ug_qk_rmsnorm_rope_bwd", dt)(x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), dx.data_ptr(), heads * dh, _p(dwx), _p(w), _p(cos),
-                                            _p(sin), rows, rows_per_batch, pos_offset, heads, dh, eps, _stream()), "ug_qk_rmsnorm_rope_bwd")
+    _call("ug_qk_rmsnorm_rope_bwd", dt, x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), dx.data_ptr(), heads * dh, _p(dwx), _p(w), _p(cos), _p(sin),
+          rows, rows_per_batch, pos_offset, heads, dh, eps, _stream())
     return dx, (dwx.sum(0).to(dt) if dwx is not None else None)       # <= 2048 fp32 partial rows of the kernel, added in a fixed order
 
 
@@ -765,15 +757,14 @@ def row_lse(S: torch.Tensor, scale: float, valid_cols: Optional[int] = None) -> 
     _chk(S, "S", torch.float32)
     rows, cols = S.shape
     out = torch.empty(rows, device=S.device, dtype=torch.float32)
-    L.check(L.load().ug_row_lse(S.data_ptr(), S.stride(0), out.data_ptr(), rows, valid_cols or cols, scale, _stream()), "ug_row_lse")
+    L.call("ug_row_lse", S.data_ptr(), S.stride(0), out.data_ptr(), rows, valid_cols or cols, scale, _stream())
     return out
 
 
 def attn_prob(S: torch.Tensor, lse: torch.Tensor, scale: float, dtype, valid_cols: Optional[int] = None) -> torch.Tensor:
     rows, cols = S.shape
     P = torch.empty(rows, cols, device=S.device, dtype=dtype)
-    L.check(_fn("ug_attn_prob", dtype)(S.data_ptr(), S.stride(0), lse.data_ptr(), P.data_ptr(), cols, rows, cols, valid_cols or cols, scale, _stream()),
-            "ug_attn_prob")
+    _call("ug_attn_prob", dtype, S.data_ptr(), S.stride(0), lse.data_ptr(), P.data_ptr(), cols, rows, cols, valid_cols or cols, scale, _stream())
     return P
 
 
@@ -781,8 +772,7 @@ def attn_dscore(P: torch.Tensor, dP: torch.Tensor, delta: torch.Tensor, scale: f
     dt = _act(P, "P")
     rows, cols = P.shape
     dS = torch.empty_like(P)
-    L.check(_fn("ug_attn_dscore", dt)(P.data_ptr(), P.stride(0), dP.data_ptr(), dP.stride(0), delta.data_ptr(), dS.data_ptr(), cols, rows, cols, scale, _stream()),
-            "ug_attn_dscore")
+    _call("ug_attn_dscore", dt, P.data_ptr(), P.stride(0), dP.data_ptr(), dP.stride(0), delta.data_ptr(), dS.data_ptr(), cols, rows, cols, scale, _stream())
     return dS
 
 
@@ -793,7 +783,7 @@ def rowdot(a: torch.Tensor, b: torch.Tensor, groups: int) -> torch.Tensor:
     rows = a.shape[0]
     cols = a.shape[1] // groups
     out = torch.empty(groups, rows, device=a.device, dtype=torch.float32)
-    L.check(_fn("ug_rowdot", dt)(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), rows, groups, cols, _stream()), "ug_rowdot")
+    _call("ug_rowdot", dt, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), rows, groups, cols, _stream())
     return out
 
 
@@ -810,8 +800,8 @@ def flash_attn_bwd(q, k, v, o, do, *, heads: int, lse: Optional[torch.Tensor] = 
     ev = _timer.begin("attn_bwd") if _timer is not None else None
     if lse is not None:
         assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, heads, (Lq + 63) // 64 * 64), lse.shape
-    L.check(lib.ug_flash_attn_bwd(*st(q), *st(k), *st(v), *st(o), *st(do), *st(dq), *st(dk), *st(dv), B, heads, Lq, Lkv, dh, dh ** -0.5, _p(lse),
-                                  ws.data_ptr(), ws.numel(), _stream()), "ug_flash_attn_bwd")
+    L.call("ug_flash_attn_bwd", *st(q), *st(k), *st(v), *st(o), *st(do), *st(dq), *st(dk), *st(dv), B, heads, Lq, Lkv, dh, dh ** -0.5, _p(lse), ws.data_ptr(),
+           ws.numel(), _stream())
     if ev is not None:
         _timer.end("attn_bwd", 10.0 * B * heads * Lq * Lkv * dh, ev)
     return dq, dk, dv
@@ -825,8 +815,8 @@ def gate_residual(x: Optional[torch.Tensor], a: torch.Tensor, gate: torch.Tensor
         _chk(x, "x", dt)
     rows, D = a.shape
     y = torch.empty(rows, D, device=a.device, dtype=dt)
-    L.check(_fn("ug_gate_residual", dt)(_p(x), x.stride(0) if x is not None else 0, a.data_ptr(), a.stride(0), gate.data_ptr(), gate.stride(0), rows_per_sample,
-                                        y.data_ptr(), D, rows, D, _stream()), "ug_gate_residual")
+    _call("ug_gate_residual", dt, _p(x), x.stride(0) if x is not None else 0, a.data_ptr(), a.stride(0), gate.data_ptr(), gate.stride(0), rows_per_sample,
+          y.data_ptr(), D, rows, D, _stream())
     return y
 
 
@@ -858,9 +848,8 @@ def flow_noise(x: torch.Tensor, noise: torch.Tensor, u: torch.Tensor, sigma_tabl
     shape = (B, (H // 2) * (W // 2), Cc * 4) if pack else (B, Cc, H, W)
     noisy, target = torch.empty(shape, device=x.device, dtype=dt), torch.empty(shape, device=x.device, dtype=dt)
     svw = torch.empty(3, B, device=x.device, dtype=f32)
-    L.check(_fn("ug_flow_noise", dt)(x.data_ptr(), noise.data_ptr(), u.data_ptr(), sigma_table.data_ptr(), sigma_table.numel(), FLOW_SCHEMES[scheme],
-                                     1 if pack else 0, B, Cc, H, W, noisy.data_ptr(), target.data_ptr(), svw[0].data_ptr(), svw[1].data_ptr(),
-                                     svw[2].data_ptr(), _stream()), "ug_flow_noise")
+    _call("ug_flow_noise", dt, x.data_ptr(), noise.data_ptr(), u.data_ptr(), sigma_table.data_ptr(), sigma_table.numel(), FLOW_SCHEMES[scheme],
+          1 if pack else 0, B, Cc, H, W, noisy.data_ptr(), target.data_ptr(), svw[0].data_ptr(), svw[1].data_ptr(), svw[2].data_ptr(), _stream())
     return noisy, target, svw[0], svw[1], svw[2]
 
 
@@ -882,8 +871,8 @@ def flow_loss(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, wo
     if workspace is None:
         workspace = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
     per_sample, loss = torch.empty(B, device=pred.device, dtype=f32), torch.empty((), device=pred.device, dtype=f32)
-    L.check(_fn("ug_flow_loss", dt)(pred.data_ptr(), target.data_ptr(), weight.data_ptr(), B, n, per_sample.data_ptr(), loss.data_ptr(), workspace.data_ptr(),
-                                    workspace.numel() * workspace.element_size(), _stream()), "ug_flow_loss")
+    _call("ug_flow_loss", dt, pred.data_ptr(), target.data_ptr(), weight.data_ptr(), B, n, per_sample.data_ptr(), loss.data_ptr(), workspace.data_ptr(),
+          workspace.numel() * workspace.element_size(), _stream())
     return per_sample, loss
 
 
@@ -892,8 +881,7 @@ def flow_loss_bwd(pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor
     dt, B, n, pred, target = _flow_pair(pred, target, weight, "flow_loss_bwd")
     _chk_f32_vec(gout, "gout", 1)
     grad = torch.empty_like(pred)
-    L.check(_fn("ug_flow_loss_bwd", dt)(pred.data_ptr(), target.data_ptr(), weight.data_ptr(), gout.data_ptr(), B, n, grad.data_ptr(), _stream()),
-            "ug_flow_loss_bwd")
+    _call("ug_flow_loss_bwd", dt, pred.data_ptr(), target.data_ptr(), weight.data_ptr(), gout.data_ptr(), B, n, grad.data_ptr(), _stream())
     return grad
 
 
@@ -910,9 +898,8 @@ def flash_attn_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
             raise ValueError(f"rel_table: expected a contiguous [heads = {heads}, 2 * rel_len - 1] table, got {tuple(rel_table.shape)}")
         rel_len = (rel_table.shape[1] + 1) // 2
     ev = _timer.begin("attn") if _timer is not None else None
-    L.check(_fn("ug_flash_attn_fwd_bias", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
-                                            v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, _p(rel_table),
-                                            rel_len, 1 if causal else 0, _stream()), "ug_flash_attn_fwd_bias")
+    _call("ug_flash_attn_fwd_bias", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+          v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, Lq, Lkv, dh, scale, _p(rel_table), rel_len, 1 if causal else 0, _stream())
     if ev is not None:
         _timer.end("attn", 4.0 * batches * heads * Lq * Lkv * dh * (0.5 if causal else 1.0), ev, tag=(batches, heads, Lq, Lkv, dh))
     return out
@@ -925,7 +912,7 @@ def t5_rel_table(weight: torch.Tensor, L_: int, *, num_buckets: int, max_distanc
         raise ValueError(f"weight: expected a contiguous [num_buckets = {num_buckets}, heads] tensor, got {tuple(weight.shape)}")
     heads = weight.shape[1]
     table = torch.empty(heads, 2 * L_ - 1, dtype=torch.float32, device=weight.device)
-    L.check(_fn("ug_t5_rel_table", dt)(weight.data_ptr(), num_buckets, max_distance, heads, L_, table.data_ptr(), _stream()), "ug_t5_rel_table")
+    _call("ug_t5_rel_table", dt, weight.data_ptr(), num_buckets, max_distance, heads, L_, table.data_ptr(), _stream())
     return table
 
 
@@ -937,7 +924,7 @@ def rmsnorm_rows(x: torch.Tensor, w: torch.Tensor, eps: float, out: Optional[tor
     out = torch.empty(rows, D, dtype=dt, device=x.device) if out is None else out
     _chk(out, "out", dt)
     assert w.numel() == D and out.shape == x.shape
-    L.check(_fn("ug_rmsnorm_rows", dt)(x.data_ptr(), x.stride(0), w.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream()), "ug_rmsnorm_rows")
+    _call("ug_rmsnorm_rows", dt, x.data_ptr(), x.stride(0), w.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream())
     return out
 
 
@@ -949,8 +936,7 @@ def layernorm_rows(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float
     out = torch.empty(rows, D, dtype=dt, device=x.device) if out is None else out
     _chk(out, "out", dt)
     assert w.numel() == D and b.numel() == D and out.shape == x.shape
-    L.check(_fn("ug_layernorm_rows", dt)(x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream()),
-            "ug_layernorm_rows")
+    _call("ug_layernorm_rows", dt, x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), out.data_ptr(), out.stride(0), rows, D, eps, _stream())
     return out
 
 
@@ -961,7 +947,7 @@ def gated_gelu(ab: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     out = torch.empty(M, F2 // 2, dtype=dt, device=ab.device) if out is None else out
     _chk(out, "out", dt)
     assert F2 % 2 == 0 and out.shape == (M, F2 // 2)
-    L.check(_fn("ug_gated_gelu", dt)(ab.data_ptr(), ab.stride(0), out.data_ptr(), out.stride(0), M, F2 // 2, _stream()), "ug_gated_gelu")
+    _call("ug_gated_gelu", dt, ab.data_ptr(), ab.stride(0), out.data_ptr(), out.stride(0), M, F2 // 2, _stream())
     return out
 
 
@@ -971,7 +957,7 @@ def quick_gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     out = torch.empty_like(x) if out is None else out
     _chk(out, "out", dt)
     assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
-    L.check(_fn("ug_quick_gelu", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_quick_gelu")
+    _call("ug_quick_gelu", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -981,7 +967,7 @@ def gelu_erf(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tenso
     out = torch.empty_like(x) if out is None else out
     _chk(out, "out", dt)
     assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
-    L.check(_fn("ug_gelu_erf", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_gelu_erf")
+    _call("ug_gelu_erf", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -1008,7 +994,7 @@ def canny_grad(x: torch.Tensor):
     B, H, W, Cc, sb, sr = _img(x, "x")
     dx, dy = torch.empty(B, H, W, dtype=torch.int16, device=x.device), torch.empty(B, H, W, dtype=torch.int16, device=x.device)
     mag = torch.empty(B, H, W, dtype=torch.int32, device=x.device)
-    L.check(L.load().ug_canny_grad(x.data_ptr(), sb, sr, B, H, W, Cc, dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), _stream()), "ug_canny_grad")
+    L.call("ug_canny_grad", x.data_ptr(), sb, sr, B, H, W, Cc, dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), _stream())
     return dx, dy, mag
 
 
@@ -1018,7 +1004,7 @@ def canny_nms(dx: torch.Tensor, dy: torch.Tensor, mag: torch.Tensor, low: int, h
     assert dx.is_contiguous() and dy.is_contiguous() and mag.is_contiguous() and dx.shape == dy.shape == mag.shape and dx.dim() == 3
     B, H, W = dx.shape
     out = torch.empty(B, H, W, dtype=u8, device=dx.device)
-    L.check(L.load().ug_canny_nms(dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), B, H, W, low, high, out.data_ptr(), _stream()), "ug_canny_nms")
+    L.call("ug_canny_nms", dx.data_ptr(), dy.data_ptr(), mag.data_ptr(), B, H, W, low, high, out.data_ptr(), _stream())
     return out
 
 
@@ -1035,7 +1021,7 @@ def canny_hysteresis(emap: torch.Tensor):
     out = torch.empty(B, H, W, dtype=u8, device=emap.device)
     flag = torch.zeros(1, dtype=torch.int32, device=emap.device)
     sweeps = C.c_int32(0)
-    L.check(L.load().ug_canny_hysteresis(work.data_ptr(), B, H, W, out.data_ptr(), H * W, W, flag.data_ptr(), C.byref(sweeps), _stream()), "ug_canny_hysteresis")
+    L.call("ug_canny_hysteresis", work.data_ptr(), B, H, W, out.data_ptr(), H * W, W, flag.data_ptr(), C.byref(sweeps), _stream())
     return out, sweeps.value
 
 
@@ -1046,8 +1032,7 @@ def canny_u8(x: torch.Tensor, low: int = 100, high: int = 200):
     ws = torch.empty(int(lib.ug_canny_workspace_bytes(B, H, W)), dtype=u8, device=x.device)
     out = torch.empty(B, H, W, dtype=u8, device=x.device)
     sweeps = C.c_int32(0)
-    L.check(lib.ug_canny_u8(x.data_ptr(), sb, sr, B, H, W, Cc, low, high, out.data_ptr(), H * W, W, ws.data_ptr(), ws.numel(), C.byref(sweeps), _stream()),
-            "ug_canny_u8")
+    L.call("ug_canny_u8", x.data_ptr(), sb, sr, B, H, W, Cc, low, high, out.data_ptr(), H * W, W, ws.data_ptr(), ws.numel(), C.byref(sweeps), _stream())
     return out, sweeps.value
 
 
@@ -1065,8 +1050,8 @@ def img_resize_u8(x: torch.Tensor, height: int, width: int, xtables=None, ytable
     tmp = torch.empty(B, H, width, Cc, dtype=u8, device=x.device) if (xtables is not None and ytables is not None) else None
     xb, xc, xk = (xtables[0].data_ptr(), xtables[1].data_ptr(), xtables[2]) if xtables is not None else (None, None, 0)
     yb, yc, yk = (ytables[0].data_ptr(), ytables[1].data_ptr(), ytables[2]) if ytables is not None else (None, None, 0)
-    L.check(L.load().ug_img_resize_u8(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), height * width * Cc, width * Cc, height, width, xb, xc, xk, yb, yc, yk,
-                                      _p(tmp), _stream()), "ug_img_resize_u8")
+    L.call("ug_img_resize_u8", x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), height * width * Cc, width * Cc, height, width, xb, xc, xk, yb, yc, yk,
+           _p(tmp), _stream())
     return out
 
 
@@ -1074,7 +1059,7 @@ def img_rgb_to_l(x: torch.Tensor) -> torch.Tensor:
     """PIL's convert("L"): [B, H, W, 3] -> [B, H, W, 1]."""
     B, H, W, Cc, sb, sr = _img(x, "x", channels=(3,))
     out = torch.empty(B, H, W, 1, dtype=u8, device=x.device)
-    L.check(L.load().ug_img_rgb_to_l(x.data_ptr(), sb, sr, B, H, W, out.data_ptr(), H * W, W, _stream()), "ug_img_rgb_to_l")
+    L.call("ug_img_rgb_to_l", x.data_ptr(), sb, sr, B, H, W, out.data_ptr(), H * W, W, _stream())
     return out
 
 
@@ -1089,7 +1074,7 @@ def img_u8_to_chw(x: torch.Tensor, normalize: bool = True, dtype=f32, replicate:
     B, H, W, Cc, sb, sr = _img(x, "x")
     cout = 3 if (replicate and Cc == 1) else Cc
     out = torch.empty(B, cout, H, W, dtype=dtype, device=x.device)
-    L.check(L.load().ug_img_u8_to_chw(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), _img_dt(dtype), cout, int(bool(normalize)), _stream()), "ug_img_u8_to_chw")
+    L.call("ug_img_u8_to_chw", x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), _img_dt(dtype), cout, int(bool(normalize)), _stream())
     return out
 
 
@@ -1103,7 +1088,7 @@ def img_chw_to_u8(x: torch.Tensor, denormalize: bool = True) -> torch.Tensor:
     x = x.contiguous()
     B, Cc, H, W = x.shape
     out = torch.empty(B, H, W, Cc, dtype=u8, device=x.device)
-    L.check(L.load().ug_img_chw_to_u8(x.data_ptr(), dt, B, Cc, H, W, out.data_ptr(), H * W * Cc, W * Cc, int(bool(denormalize)), _stream()), "ug_img_chw_to_u8")
+    L.call("ug_img_chw_to_u8", x.data_ptr(), dt, B, Cc, H, W, out.data_ptr(), H * W * Cc, W * Cc, int(bool(denormalize)), _stream())
     return out
 
 
@@ -1115,8 +1100,8 @@ def img_box_blur_u8(x: torch.Tensor, cx, cy, passes: int = 1, fuse: bool = True)
     lib = L.load()
     ws = torch.empty(int(lib.ug_img_blur_workspace_bytes(B, H, W, Cc)), dtype=u8, device=x.device)
     out = torch.empty(B, H, W, Cc, dtype=u8, device=x.device)
-    L.check(lib.ug_img_box_blur_u8(x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), H * W * Cc, W * Cc, *(int(v) for v in cx), *(int(v) for v in cy), int(passes),
-                                   int(bool(fuse)), ws.data_ptr(), ws.numel(), _stream()), "ug_img_box_blur_u8")
+    L.call("ug_img_box_blur_u8", x.data_ptr(), sb, sr, B, H, W, Cc, out.data_ptr(), H * W * Cc, W * Cc, *(int(v) for v in cx), *(int(v) for v in cy),
+           int(passes), int(bool(fuse)), ws.data_ptr(), ws.numel(), _stream())
     return out
 
 
@@ -1132,8 +1117,7 @@ def img_u8_to_patches(x: torch.Tensor, patch: int, mean, std, rescale: float = 1
         raise ValueError(f"image {H}x{W} is not a multiple of the patch size {patch}")
     out = torch.empty(B * (H // patch) * (W // patch), Kp, dtype=dtype, device=x.device)
     m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
-    L.check(_fn("ug_img_u8_to_patches", dtype)(x.data_ptr(), sb, sr, B, H, W, Cc, patch, float(rescale), m3, s3, out.data_ptr(), Kp, Kp, _stream()),
-            "ug_img_u8_to_patches")
+    _call("ug_img_u8_to_patches", dtype, x.data_ptr(), sb, sr, B, H, W, Cc, patch, float(rescale), m3, s3, out.data_ptr(), Kp, Kp, _stream())
     return out
 
 
@@ -1143,7 +1127,7 @@ def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = torch.empty_like(x) if out is None else out
     _chk(out, "out", dt)
     assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
-    L.check(_fn("ug_relu", dt)(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "ug_relu")
+    _call("ug_relu", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -1154,8 +1138,7 @@ def deconv_scatter_nhwc(prod: torch.Tensor, bias: torch.Tensor, *, B: int, h: in
     dt = _act(bias, "bias")
     assert prod.dim() == 2 and prod.shape[0] == B * h * w and prod.shape[1] >= f * f * Cout and bias.numel() == Cout and bias.is_contiguous()
     out = torch.empty(B, h * f, w * f, Cp, dtype=dt, device=prod.device)
-    L.check(_fn("ug_deconv_scatter_nhwc", dt)(prod.data_ptr(), prod.stride(0), bias.data_ptr(), out.data_ptr(), B, h, w, f, Cout, Cp, _stream()),
-            "ug_deconv_scatter_nhwc")
+    _call("ug_deconv_scatter_nhwc", dt, prod.data_ptr(), prod.stride(0), bias.data_ptr(), out.data_ptr(), B, h, w, f, Cout, Cp, _stream())
     return out
 
 
@@ -1165,7 +1148,7 @@ def bilinear_nhwc(x: torch.Tensor, Ho: int, Wo: int, align_corners: bool) -> tor
     assert x.dim() == 4 and x.is_contiguous(), x.shape
     B, H, W, Cc = x.shape
     out = torch.empty(B, Ho, Wo, Cc, dtype=dt, device=x.device)
-    L.check(_fn("ug_bilinear_nhwc", dt)(x.data_ptr(), B, H, W, Cc, out.data_ptr(), Ho, Wo, int(bool(align_corners)), _stream()), "ug_bilinear_nhwc")
+    _call("ug_bilinear_nhwc", dt, x.data_ptr(), B, H, W, Cc, out.data_ptr(), Ho, Wo, int(bool(align_corners)), _stream())
     return out
 
 
@@ -1176,8 +1159,8 @@ def depth_head_out(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, C_: 
     assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.numel() == C_ and bias.numel() == 1 and C_ <= x.shape[-1]
     B, H, W, Cp = x.shape
     out = torch.empty(B, H, W, dtype=f32, device=x.device)
-    L.check(_fn("ug_depth_head_out", dt)(x.data_ptr(), B * H * W, C_, Cp, w.data_ptr(), bias.data_ptr(), float(max_depth), int(bool(metric)), out.data_ptr(),
-                                       _stream()), "ug_depth_head_out")
+    _call("ug_depth_head_out", dt, x.data_ptr(), B * H * W, C_, Cp, w.data_ptr(), bias.data_ptr(), float(max_depth), int(bool(metric)), out.data_ptr(),
+          _stream())
     return out
 
 
@@ -1187,7 +1170,7 @@ def bicubic_f32(x: torch.Tensor, Ho: int, Wo: int) -> torch.Tensor:
     assert x.dim() == 3 and x.is_contiguous(), x.shape
     B, H, W = x.shape
     out = torch.empty(B, Ho, Wo, dtype=f32, device=x.device)
-    L.check(L.load().ug_bicubic_f32(x.data_ptr(), B, H, W, out.data_ptr(), Ho, Wo, _stream()), "ug_bicubic_f32")
+    L.call("ug_bicubic_f32", x.data_ptr(), B, H, W, out.data_ptr(), Ho, Wo, _stream())
     return out
 
 
@@ -1204,7 +1187,7 @@ def minmax_to_u8(d: torch.Tensor, channels: int = 1, workspace: Optional[torch.T
     ws = torch.empty(minmax_workspace_bytes(B, H * W), dtype=u8, device=d.device) if workspace is None else workspace
     _chk(ws, "workspace", u8)
     out = torch.empty(B, H, W, channels, dtype=u8, device=d.device)
-    L.check(L.load().ug_minmax_to_u8(d.data_ptr(), B, H * W, out.data_ptr(), channels, ws.data_ptr(), ws.numel(), _stream()), "ug_minmax_to_u8")
+    L.call("ug_minmax_to_u8", d.data_ptr(), B, H * W, out.data_ptr(), channels, ws.data_ptr(), ws.numel(), _stream())
     return out
 
 
@@ -1225,9 +1208,8 @@ def linear_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Te
     if ws.numel() < linear_attn_workspace_bytes(batches, heads, N):
         raise ValueError(f"linear_attn: the workspace has {ws.numel()} bytes, {linear_attn_workspace_bytes(batches, heads, N)} are needed")
     ev = _timer.begin("linear_attn") if _timer is not None else None
-    L.check(_fn("ug_linear_attn", dt)(q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
-                                    v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, N, dh, ws.data_ptr(), _stream()),
-            "ug_linear_attn")
+    _call("ug_linear_attn", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0], v_strides[1],
+          out.data_ptr(), o_strides[0], o_strides[1], batches, heads, N, dh, ws.data_ptr(), _stream())
     if ev is not None:
         _timer.end("linear_attn", 4.0 * batches * heads * N * dh * (dh + 1), ev, tag=(batches, heads, N))
     return out
@@ -1241,8 +1223,8 @@ def glu_dwconv3x3(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, out: to
     _chk(w9, "w9", dt); _chk(bias, "bias", dt); _chk(out, "out", dt)
     assert w9.is_contiguous() and tuple(w9.shape) == (9, 2 * C) and bias.numel() == 2 * C, (w9.shape, bias.shape, C)
     ev = _timer.begin("glu_dwconv") if _timer is not None else None
-    L.check(_fn("ug_glu_dwconv3x3", dt)(x.data_ptr(), ldx if ldx is not None else x.stride(-2), w9.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                      ldo if ldo is not None else out.stride(-2), B, H, W, C, _stream()), "ug_glu_dwconv3x3")
+    _call("ug_glu_dwconv3x3", dt, x.data_ptr(), ldx if ldx is not None else x.stride(-2), w9.data_ptr(), bias.data_ptr(), out.data_ptr(),
+          ldo if ldo is not None else out.stride(-2), B, H, W, C, _stream())
     if ev is not None:
         _timer.end("glu_dwconv", 2.0 * 9 * 2 * C * B * H * W, ev, tag=(B, H, W, C))
     return out

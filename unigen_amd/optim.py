@@ -60,7 +60,7 @@ class _WorkList:
                 d.param, d.param_dtype = p.data_ptr(), _DT[p.dtype]
                 d.master = master.data_ptr() if master is not None else None
                 d.exp_avg, d.exp_avg_sq, d.group = m.data_ptr(), v.data_ptr(), group
-        L.check(L.load().ug_optim_check_table(C.addressof(table), n, n_groups), "ug_optim_check_table")
+        L.call("ug_optim_check_table", C.addressof(table), n, n_groups)
         self.n_tensors = n
         self.table = _upload(torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8), device)
         chunks = chunk_list([r[1].numel() for r in rows])
@@ -73,8 +73,8 @@ class _WorkList:
         cdll = L.load()
         nbytes = cdll.ug_grad_sumsq_workspace_bytes(self.n_chunks)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        L.check(cdll.ug_grad_sumsq(self.table.data_ptr(), self.n_tensors, self.chunks.data_ptr(), self.n_chunks, float(max_norm), out.data_ptr(),
-                                   ws.data_ptr(), nbytes, stream), "ug_grad_sumsq")
+        L.call("ug_grad_sumsq", self.table.data_ptr(), self.n_tensors, self.chunks.data_ptr(), self.n_chunks, float(max_norm), out.data_ptr(), ws.data_ptr(),
+               nbytes, stream)
         return out
 
 
@@ -90,7 +90,7 @@ class _WorkListLP(_WorkList):
             d.param, d.param_dtype = p.data_ptr(), _DT[p.dtype]
             d.master = master.data_ptr() if master is not None else None
             d.exp_avg, d.exp_avg_sq, d.state_dtype, d.group, d.param_index = m.data_ptr(), v.data_ptr(), _DT[m.dtype], group, index
-        L.check(L.load().ug_optim_check_table_lowp(C.addressof(table), n, n_groups), "ug_optim_check_table_lowp")
+        L.call("ug_optim_check_table_lowp", C.addressof(table), n, n_groups)
         self.n_tensors = n
         self.table = _upload(torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8), device)
         chunks = chunk_list([r[1].numel() for r in rows])
@@ -158,7 +158,7 @@ def clip_grad_norm_(parameters: Union[torch.Tensor, Iterable[torch.Tensor]], max
     if error_if_nonfinite and torch.logical_or(total.isnan(), total.isinf()):
         raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped. "
                            "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
-    L.check(L.load().ug_grad_scale(wl.table.data_ptr(), wl.n_tensors, wl.chunks.data_ptr(), wl.n_chunks, out[1:].data_ptr(), stream), "ug_grad_scale")
+    L.call("ug_grad_scale", wl.table.data_ptr(), wl.n_tensors, wl.chunks.data_ptr(), wl.n_chunks, out[1:].data_ptr(), stream)
     torch.autograd.graph.increment_version(grads)
     return total
 
@@ -292,10 +292,8 @@ class AdamW(torch.optim.Optimizer):
         if self.max_grad_norm is not None:
             out = wl.sumsq(self.max_grad_norm, dev, stream)
             self.last_grad_norm, coef = out[0], out[1:]
-        cdll = L.load()
-        fn = "ug_adamw_step_lowp" if lowp else "ug_adamw_step"
-        L.check(getattr(cdll, fn)(wl.table.data_ptr(), wl.n_tensors, wl.chunks.data_ptr(), wl.n_chunks, C.addressof(hp), len(slots),
-                                  None if coef is None else coef.data_ptr(), stream), fn)
+        L.call("ug_adamw_step_lowp" if lowp else "ug_adamw_step", wl.table.data_ptr(), wl.n_tensors, wl.chunks.data_ptr(), wl.n_chunks, C.addressof(hp),
+               len(slots), None if coef is None else coef.data_ptr(), stream)
         torch.autograd.graph.increment_version(self._written)
         return loss
 

@@ -279,7 +279,7 @@ class SanaTransformerBlock(_Params):
         g = lambda name, *shape, **kw: self._get(bufs, name, shape, **kw)
         h0 = hidden_states.view(M, D)
         mod = g("blk_mod", B, 6 * D)
-        L.check(ops._fn("ug_add_bf16", dt)(timestep.data_ptr(), 6 * D, p["table"].data_ptr(), 0, mod.data_ptr(), 6 * D, B, 6 * D, ops._stream()), "ug_add_bf16")
+        ops._call("ug_add_bf16", dt, timestep.data_ptr(), 6 * D, p["table"].data_ptr(), 0, mod.data_ptr(), 6 * D, B, 6 * D, ops._stream())
         chunk = lambda i: mod[0, i * D:]                 # base of modulation chunk i: sample b's row is 6 D further per sample
         # --- self attention: ReLU linear attention ---
         n1 = ops.adaln_modulate(h0, chunk(0), chunk(1), g("n", M, D), rows=M, D=D, rows_per_sample=N, mod_ld=6 * D, eps=self.norm_eps)
@@ -464,9 +464,8 @@ class SanaTransformer2DModel(_Params):
             hb, other = other, hb
         # SanaModulatedNorm: (scale_shift_table[None] + embedded_timestep[:, None]).chunk(2, 1) = shift, scale
         fm = g("fmod", B, 2 * D)
-        add = ops._fn("ug_add_bf16", dt)
         for i in range(2):
-            L.check(add(et.data_ptr(), D, s["scale_shift_table"][i].data_ptr(), 0, fm[:, i * D:].data_ptr(), 2 * D, B, D, ops._stream()), "ug_add_bf16")
+            ops._call("ug_add_bf16", dt, et.data_ptr(), D, s["scale_shift_table"][i].data_ptr(), 0, fm[:, i * D:].data_ptr(), 2 * D, B, D, ops._stream())
         nf = ops.adaln_modulate(hb.view(M, D), fm[0], fm[0, D:], g("nf", M, D), rows=M, D=D, rows_per_sample=N, mod_ld=2 * D, eps=c["norm_eps"])
         y = ops.gemm(nf, p["out_w"], p["out_b"], g("y", M, self.Pout), M=M)
         return ops.nhwc_to_nchw(y, B, c["out_channels"], H, W)          # unpatchify at patch_size 1: NHWC -> NCHW
