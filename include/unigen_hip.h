@@ -832,7 +832,9 @@ int ug_minmax_to_u8(const float* d, int64_t B, int64_t HW, uint8_t* out, int32_t
  * (UG_ERR_UNSUPPORTED otherwise); any N >= 1. q / k / v / o take a row stride and a batch stride each, in elements (the packed [q | k | v] output of
  * one GEMM is read in place): multiples of 8 (fp32 twin: 4), bases 16-byte aligned, UG_ERR_BAD_ALIGN otherwise. The caller-owned, 16-byte aligned
  * workspace of the size the query returns needs no initialisation: the per-chunk partial states are written, then summed in ascending chunk order, then
- * applied - three launches, no atomics, nothing kept between calls, so two calls give the same bits and the call can be captured in a graph. */
+ * applied - three launches, no atomics, nothing kept between calls, so two calls give the same bits and the call can be captured in a graph.
+ * GUARANTEE for the backward: on return the first batches * heads * 1056 floats of the workspace hold the state, per (batch, head) S^T[j][d]
+ * (1024 floats) then z[j] (32): this is the `state` operand of ug_linear_attn_bwd. */
 int64_t ug_linear_attn_workspace_bytes(int64_t batches, int64_t heads, int64_t N);
 int ug_linear_attn(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
                    const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
@@ -849,6 +851,41 @@ int ug_glu_dwconv3x3(const void* x, int64_t ldx, const void* w9, const void* bia
                      ug_stream_t stream);
 int ug_glu_dwconv3x3_f32(const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t C,
                          ug_stream_t stream);
+/* Backward of ug_linear_attn (csrc/sana_bwd.hip). q, k, v as in the forward; dout [batch][N][heads * 32] the gradient of its output; state: the
+ * batches * heads * 1056 floats (S^T[j][d] | z[j]) that ug_linear_attn leaves at the start of its workspace - REQUIRED (NULL: UG_ERR_BAD_SHAPE), there
+ * is no recompute path, and the forward's rounded output is not an input: o = S q' / den is recomputed in fp32. With g = dout / den,
+ * c = -(dout . o) / den:  dq' = g S + c z,  dS = g^T q',  dz = c^T q',  dk' = v dS + dz,  dv = k' dS^T,  dq = dq' [q > 0],  dk = dk' [k > 0].
+ * dS and dz stay fp32; dq, dk, dv are rounded once, at the store; each takes a row and a batch stride (the three may be the column blocks of one
+ * [M][3 D] buffer: the dY of the fused QKV projection). Strides, alignment and limits as in the forward (state 16-byte aligned too); dh = 32 only, any
+ * N >= 1. The caller-owned, 16-byte aligned workspace of ug_linear_attn_bwd_workspace_bytes() needs no initialisation (smaller: UG_ERR_BAD_SHAPE): the
+ * query pass writes dq and one partial dS | dz per 128 query rows, the partials are summed in ascending order, the key pass writes dk and dv - three
+ * launches, no atomics, nothing kept between calls: two calls give the same bits, and the call can be captured in a graph. */
+int64_t ug_linear_attn_bwd_workspace_bytes(int64_t batches, int64_t heads, int64_t N);
+int ug_linear_attn_bwd(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                       const void* v, int64_t v_row_stride, int64_t v_batch_stride, const void* dout, int64_t do_row_stride, int64_t do_batch_stride,
+                       const float* state, void* dq, int64_t dq_row_stride, int64_t dq_batch_stride, void* dk, int64_t dk_row_stride, int64_t dk_batch_stride,
+                       void* dv, int64_t dv_row_stride, int64_t dv_batch_stride, int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace,
+                       int64_t workspace_bytes, ug_stream_t stream);
+int ug_linear_attn_bwd_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                           const void* v, int64_t v_row_stride, int64_t v_batch_stride, const void* dout, int64_t do_row_stride, int64_t do_batch_stride,
+                           const float* state, void* dq, int64_t dq_row_stride, int64_t dq_batch_stride, void* dk, int64_t dk_row_stride, int64_t dk_batch_stride,
+                           void* dv, int64_t dv_row_stride, int64_t dv_batch_stride, int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace,
+                           int64_t workspace_bytes, ug_stream_t stream);
+/* Backward of ug_glu_dwconv3x3 (csrc/sana_bwd.hip). x, w9, bias: what the forward read; dout [B][H][W] rows of C with row stride lddo (its pad columns
+ * are not read); dx rows of 2C with row stride lddx (columns past 2C are not written). a = rnd(silu(x)), y = rnd(dwconv(a) + bias) and
+ * s = rnd(silu(y_gate)) are recomputed as the forward rounds them; the gradient is that of the function as evaluated (roundings straight-through):
+ *   dy_val = rnd(dout s)   dy_gate = rnd(dout y_val silu'(y_gate))   da[p] = sum_t w9[t] dy[p - t]   dx = rnd(da silu'(x))
+ *   dw9[t][c] = sum_p dy[p][c] a[p + t][c]   dbias[c] = sum_p dy[p][c]
+ * fp32 accumulation throughout; dy is rounded once (it passes through the workspace), dx once. dw9 [9][2C] and dbias [2C] leave as fully reduced
+ * fp32 (partials per 256 pixels, added in ascending order, no atomics); both may be NULL (frozen convolution weights: no reduction is launched), one
+ * alone is UG_ERR_BAD_SHAPE. C a multiple of 8; ldx, lddo, lddx multiples of 8 elements, every base 16-byte aligned. workspace: caller-owned, 16-byte
+ * aligned, ug_glu_dwconv3x3_bwd_workspace_bytes(B, H, W, C, elem_bytes) bytes with elem_bytes 2 (bf16) or 4 (the fp32 twin), no initialisation
+ * needed (smaller: UG_ERR_BAD_SHAPE). Two calls give the same bits; the call can be captured in a graph. */
+int64_t ug_glu_dwconv3x3_bwd_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int32_t elem_bytes);
+int ug_glu_dwconv3x3_bwd(const void* x, int64_t ldx, const void* w9, const void* bias, const void* dout, int64_t lddo, void* dx, int64_t lddx, float* dw9,
+                         float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+int ug_glu_dwconv3x3_bwd_f32(const void* x, int64_t ldx, const void* w9, const void* bias, const void* dout, int64_t lddo, void* dx, int64_t lddx, float* dw9,
+                             float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 
 int ug_version(void);
 const char* ug_last_error(void);

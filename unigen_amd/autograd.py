@@ -37,6 +37,16 @@ def _w_transposed(w: torch.Tensor) -> torch.Tensor:
     return hit[0]
 
 
+def evict_weight(w: torch.Tensor) -> None:
+    """Drop the cached transposes of every frozen weight that lives in w's storage: for a buffer that is rewritten in place (unigen_amd/sana.py
+    rebuilds a packed copy into its buffer after an optimizer step). The new version counter would miss the old entries, which would stay and
+    pin a dead transpose each."""
+    st = w.untyped_storage()
+    lo, hi = st.data_ptr(), st.data_ptr() + st.nbytes()
+    for k in [k for k in _wt_cache if lo <= k[0] < hi]:
+        del _wt_cache[k]
+
+
 def clear_caches() -> None:
     """Drop EVERY cached transpose (frozen weights and recent activations). Only for when parameters are re-pointed at new storage
     (engine._pack / _pack_stack / _apply call it); a training loop must NOT call this per step - every frozen weight would be re-transposed
@@ -109,6 +119,8 @@ def _adjacent(ts) -> bool:
         if a is None or b is None or not a.is_contiguous() or not b.is_contiguous() or a.dtype != b.dtype:
             return False
         if b.data_ptr() != a.data_ptr() + a.numel() * a.element_size() or a.shape[1:] != b.shape[1:]:
+            return False
+        if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():      # neighbours by the allocator's choice, not views of one buffer
             return False
     return ts[0] is not None and ts[0].is_contiguous()
 
@@ -406,7 +418,7 @@ class FlashAttention(torch.autograd.Function):
     P = 0, padded queries carry dO = 0)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads):
+    def forward(ctx, q, k, v, heads, scale=None):
         B, Lq, HD = q.shape
         Lkv = k.shape[1]
         dh = HD // heads
@@ -416,9 +428,9 @@ class FlashAttention(torch.autograd.Function):
         if q.dtype == torch.bfloat16 and os.environ.get("UG_ATTN_BWD", "flash") != "gemm":
             lse = torch.zeros(B, heads, _pad64(Lq), device=q.device, dtype=torch.float32)
         ops.flash_attn(q, k, v, o, batches=B, heads=heads, dh=dh, Lq=Lq, Lkv=Lkv, q_strides=(q.stride(1), q.stride(0)), k_strides=(k.stride(1), k.stride(0)),
-                       v_strides=(v.stride(1), v.stride(0)), o_strides=(HD, Lq * HD), lse=lse)
+                       v_strides=(v.stride(1), v.stride(0)), o_strides=(HD, Lq * HD), lse=lse, **({} if scale is None else dict(scale=float(scale))))
         ctx.save_for_backward(q, k, v, o)
-        ctx.heads, ctx.lse = heads, lse
+        ctx.heads, ctx.lse, ctx.scale = heads, lse, scale
         return o
 
     @staticmethod
@@ -429,12 +441,12 @@ class FlashAttention(torch.autograd.Function):
         Lkv = k.shape[1]
         dh = HD // H
         dt, dev = q.dtype, q.device
-        scale = dh ** -0.5
+        scale = dh ** -0.5 if ctx.scale is None else float(ctx.scale)
         do = do.contiguous()
         if dt == torch.bfloat16 and os.environ.get("UG_ATTN_BWD", "flash") != "gemm":
             # product path: the tiled backward kernels (csrc/attention.hip); UG_ATTN_BWD=gemm keeps the GEMM formulation below (A/B, and what fp32 runs)
-            dq, dk, dv = ops.flash_attn_bwd(q, k, v, o, do, heads=H, lse=ctx.lse)
-            return dq, dk, dv, None
+            dq, dk, dv = ops.flash_attn_bwd(q, k, v, o, do, heads=H, lse=ctx.lse, **({} if ctx.scale is None else dict(scale=scale)))
+            return dq, dk, dv, None, None
         Lq0, Lkv0 = Lq, Lkv
         if Lq % 64 or Lkv % 64:
             Lq, Lkv = _pad64(Lq), _pad64(Lkv)
@@ -459,8 +471,75 @@ class FlashAttention(torch.autograd.Function):
             ops.gemm(PT, dOT, None, dv[b], M=Lkv, a_gstride=Lkv * Lq, w_gstride=dh * Lq, **g)
             ops.gemm(dST, QT, None, dk[b], M=Lkv, a_gstride=Lkv * Lq, w_gstride=dh * Lq, **g)
             ops.gemm(dS3, KT, None, dq[b], M=Lq, a_gstride=Lq * Lkv, w_gstride=dh * Lkv, **g)
-        return dq[:, :Lq0], dk[:, :Lkv0], dv[:, :Lkv0], None
+        return dq[:, :Lq0], dk[:, :Lkv0], dv[:, :Lkv0], None, None
 
 
-def attention(q, k, v, heads: int):
-    return FlashAttention.apply(q, k, v, heads)
+def attention(q, k, v, heads: int, scale: Optional[float] = None):
+    """scale: the softmax scale (None: dh ** -0.5, the default path, unchanged) - the padded cross-attention heads of unigen_amd/sana.py run at the
+    slot width with the true head width's scale."""
+    return FlashAttention.apply(q, k, v, heads) if scale is None else FlashAttention.apply(q, k, v, heads, scale)
+
+
+class LinearAttention(torch.autograd.Function):
+    """SanaLinearAttnProcessor2_0 at head width 32 over heads packed as [B, N, H * 32]: ug_linear_attn forward, ug_linear_attn_bwd backward.
+    q, k, v are typically the column blocks of one fused projection output and are saved as those views (any row stride); the forward's fp32 state
+    (B H 1056 floats, the start of its workspace) is cloned for the backward, which recomputes the output from it - the rounded output is not
+    saved. dq | dk | dv come back as the column blocks of one [B, N, 3 H 32] buffer: the dY of a fused projection."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads):
+        B, N, D = q.shape
+        o = torch.empty(B, N, D, device=q.device, dtype=q.dtype)
+        ws = torch.empty(ops.linear_attn_workspace_bytes(B, heads, N), device=q.device, dtype=torch.uint8)
+        st = lambda t: (t.stride(1), t.stride(0))
+        ops.linear_attn(q, k, v, o, batches=B, heads=heads, N=N, q_strides=st(q), k_strides=st(k), v_strides=st(v), o_strides=(D, N * D), workspace=ws)
+        state = ws[:B * heads * 1056 * 4].view(torch.float32).clone()
+        ctx.save_for_backward(q, k, v, state)
+        ctx.heads = heads
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, state = ctx.saved_tensors
+        B, N, D = q.shape
+        do = do.contiguous()
+        dqkv = torch.empty(B, N, 3 * D, device=q.device, dtype=q.dtype)
+        st = lambda t: (t.stride(1), t.stride(0))
+        s3 = (3 * D, N * 3 * D)
+        ops.linear_attn_bwd(q, k, v, do, state, dqkv, dqkv[0, 0, D:], dqkv[0, 0, 2 * D:], batches=B, heads=ctx.heads, N=N, q_strides=st(q), k_strides=st(k),
+                            v_strides=st(v), do_strides=st(do), dq_strides=s3, dk_strides=s3, dv_strides=s3)
+        return dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:], None
+
+
+def linear_attention(q, k, v, heads: int):
+    return LinearAttention.apply(q, k, v, heads)
+
+
+class GluDwConv(torch.autograd.Function):
+    """The middle of GLUMBConv: x [B H W, 2C] (conv_inverted's output before its SiLU), conv_depth's weight [2C, 1, 3, 3] and bias [2C] ->
+    [B H W, Cp] with the columns past C zero (the K padding of the conv_point GEMM). ug_glu_dwconv3x3 forward; backward ug_glu_dwconv3x3_bwd from the
+    saved x: dx, and - only when the convolution's parameters take gradients - fp32 dw9 / dbias, rounded once into the parameter's dtype and layout."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, B, H, W, C, Cp):
+        w9 = w.reshape(2 * C, 9).t().contiguous()
+        b = b.contiguous()
+        out = torch.empty(B * H * W, Cp, device=x.device, dtype=x.dtype)
+        ops.glu_dwconv3x3(x, w9, b, out, B=B, H=H, W=W, C=C)
+        ctx.save_for_backward(x, w9, b)
+        ctx.geom = (B, H, W, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w9, b = ctx.saved_tensors
+        B, H, W, C = ctx.geom
+        dout = dout.contiguous()
+        dx = torch.empty(B * H * W, 2 * C, device=x.device, dtype=x.dtype)
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dw9 = torch.empty(9, 2 * C, device=x.device, dtype=torch.float32) if need_w else None
+        dbias = torch.empty(2 * C, device=x.device, dtype=torch.float32) if need_w else None
+        ops.glu_dwconv3x3_bwd(x, w9, b, dout, dx, B=B, H=H, W=W, C=C, dw9=dw9, dbias=dbias)
+        dw = dw9.t().reshape(2 * C, 1, 3, 3).to(x.dtype) if ctx.needs_input_grad[1] else None
+        db = dbias.to(x.dtype) if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None, None, None, None

@@ -787,9 +787,10 @@ def rowdot(a: torch.Tensor, b: torch.Tensor, groups: int) -> torch.Tensor:
     return out
 
 
-def flash_attn_bwd(q, k, v, o, do, *, heads: int, lse: Optional[torch.Tensor] = None):
+def flash_attn_bwd(q, k, v, o, do, *, heads: int, lse: Optional[torch.Tensor] = None, scale: Optional[float] = None):
     """q, o, do [B, Lq, H * dh], k, v [B, Lkv, H * dh] (any row / batch strides, bf16) -> (dq, dk, dv) contiguous.
-    lse: what flash_attn(..., lse=) wrote, fp32 [B, H, Lq rounded up to 64] with zero padding (None: recomputed)."""
+    lse: what flash_attn(..., lse=) wrote, fp32 [B, H, Lq rounded up to 64] with zero padding (None: recomputed).
+    scale: the softmax scale of the forward (None: dh ** -0.5)."""
     _chk(q, "q"); _chk(k, "k"); _chk(v, "v"); _chk(o, "o"); _chk(do, "do")
     B, Lq, HD = q.shape
     Lkv, dh = k.shape[1], HD // heads
@@ -800,7 +801,8 @@ def flash_attn_bwd(q, k, v, o, do, *, heads: int, lse: Optional[torch.Tensor] = 
     ev = _timer.begin("attn_bwd") if _timer is not None else None
     if lse is not None:
         assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, heads, (Lq + 63) // 64 * 64), lse.shape
-    L.call("ug_flash_attn_bwd", *st(q), *st(k), *st(v), *st(o), *st(do), *st(dq), *st(dk), *st(dv), B, heads, Lq, Lkv, dh, dh ** -0.5, _p(lse), ws.data_ptr(),
+    L.call("ug_flash_attn_bwd", *st(q), *st(k), *st(v), *st(o), *st(do), *st(dq), *st(dk), *st(dv), B, heads, Lq, Lkv, dh, dh ** -0.5 if scale is None else float(scale), _p(lse),
+           ws.data_ptr(),
            ws.numel(), _stream())
     if ev is not None:
         _timer.end("attn_bwd", 10.0 * B * heads * Lq * Lkv * dh, ev)
@@ -1228,3 +1230,64 @@ def glu_dwconv3x3(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, out: to
     if ev is not None:
         _timer.end("glu_dwconv", 2.0 * 9 * 2 * C * B * H * W, ev, tag=(B, H, W, C))
     return out
+
+
+# ---- Sana backward (csrc/sana_bwd.hip) ----
+def linear_attn_bwd_workspace_bytes(batches: int, heads: int, N: int) -> int:
+    return int(L.load().ug_linear_attn_bwd_workspace_bytes(batches, heads, N))
+
+
+def linear_attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dout: torch.Tensor, state: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor,
+                    dv: torch.Tensor, *, batches: int, heads: int, N: int, q_strides, k_strides, v_strides, do_strides, dq_strides, dk_strides, dv_strides,
+                    dh: int = 32, workspace: Optional[torch.Tensor] = None):
+    """Backward of linear_attn. Base tensors and (row_stride, batch_stride) pairs as in the forward; `state`: the fp32 [batches * heads * 1056] values
+    the forward left at the start of its workspace; dq / dk / dv may be the column blocks of one [M, 3 D] buffer. Returns (dq, dk, dv)."""
+    dt = _act(q, "q")
+    for t, n in ((k, "k"), (v, "v"), (dout, "dout"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
+        _chk(t, n, dt)
+    _chk(state, "state", f32)
+    if state.numel() < batches * heads * 1056 or not state.is_contiguous():
+        raise ValueError(f"linear_attn_bwd: state has {state.numel()} floats, {batches * heads * 1056} contiguous ones are needed")
+    need = linear_attn_bwd_workspace_bytes(batches, heads, N)
+    ws = torch.empty(need, dtype=u8, device=q.device) if workspace is None else workspace
+    _chk(ws, "workspace", u8)
+    if ws.numel() < need:
+        raise ValueError(f"linear_attn_bwd: the workspace has {ws.numel()} bytes, {need} are needed")
+    ev = _timer.begin("linear_attn_bwd") if _timer is not None else None
+    _call("ug_linear_attn_bwd", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0], v_strides[1],
+          dout.data_ptr(), do_strides[0], do_strides[1], state.data_ptr(), dq.data_ptr(), dq_strides[0], dq_strides[1], dk.data_ptr(), dk_strides[0],
+          dk_strides[1], dv.data_ptr(), dv_strides[0], dv_strides[1], batches, heads, N, dh, ws.data_ptr(), ws.numel(), _stream())
+    if ev is not None:
+        _timer.end("linear_attn_bwd", 12.0 * batches * heads * N * dh * (dh + 1), ev, tag=(batches, heads, N))
+    return dq, dk, dv
+
+
+def glu_dwconv3x3_bwd_workspace_bytes(B: int, H: int, W: int, C: int, dtype=bf16) -> int:
+    return int(L.load().ug_glu_dwconv3x3_bwd_workspace_bytes(B, H, W, C, 2 if dtype == bf16 else 4))
+
+
+def glu_dwconv3x3_bwd(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, dout: torch.Tensor, dx: torch.Tensor, *, B: int, H: int, W: int, C: int,
+                      dw9: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None, ldx: Optional[int] = None, lddo: Optional[int] = None,
+                      lddx: Optional[int] = None, workspace: Optional[torch.Tensor] = None):
+    """Backward of glu_dwconv3x3: x, w9, bias as in the forward, dout rows of lddo >= C columns -> dx rows of 2C (row stride lddx), and, when given,
+    dw9 [9, 2C] / dbias [2C] fp32, fully reduced (both or neither). Returns (dx, dw9, dbias)."""
+    dt = _act(x, "x")
+    _chk(w9, "w9", dt); _chk(bias, "bias", dt); _chk(dout, "dout", dt); _chk(dx, "dx", dt)
+    assert w9.is_contiguous() and tuple(w9.shape) == (9, 2 * C) and bias.numel() == 2 * C, (w9.shape, bias.shape, C)
+    if (dw9 is None) != (dbias is None):
+        raise ValueError("glu_dwconv3x3_bwd: dw9 and dbias are both given or both None")
+    if dw9 is not None:
+        _chk(dw9, "dw9", f32); _chk(dbias, "dbias", f32)
+        assert dw9.is_contiguous() and tuple(dw9.shape) == (9, 2 * C) and dbias.is_contiguous() and dbias.numel() == 2 * C, (dw9.shape, dbias.shape)
+    need = glu_dwconv3x3_bwd_workspace_bytes(B, H, W, C, dt)
+    ws = torch.empty(need, dtype=u8, device=x.device) if workspace is None else workspace
+    _chk(ws, "workspace", u8)
+    if ws.numel() < need:
+        raise ValueError(f"glu_dwconv3x3_bwd: the workspace has {ws.numel()} bytes, {need} are needed")
+    ev = _timer.begin("glu_dwconv_bwd") if _timer is not None else None
+    _call("ug_glu_dwconv3x3_bwd", dt, x.data_ptr(), ldx if ldx is not None else x.stride(-2), w9.data_ptr(), bias.data_ptr(), dout.data_ptr(),
+          lddo if lddo is not None else dout.stride(-2), dx.data_ptr(), lddx if lddx is not None else dx.stride(-2), _p(dw9), _p(dbias), B, H, W, C,
+          ws.data_ptr(), ws.numel(), _stream())
+    if ev is not None:
+        _timer.end("glu_dwconv_bwd", 2.0 * 9 * 2 * C * B * H * W * (3 if dw9 is not None else 2), ev, tag=(B, H, W, C))
+    return dx, dw9, dbias

@@ -23,7 +23,14 @@ to_q / to_k / to_v rows head by head into 64- or 128-wide slots, the spare rows 
 padded width with the TRUE softmax scale cross_attention_head_dim ** -0.5. Zero rows add nothing to a score and produce zero outputs, which meet zero
 columns. THE NAMED PARAMETERS (state_dict()) ARE NOT VIEWS OF THE PACK: after changing one, call load_state_dict again.
 
-Inference only: there is no backward, and a call with autograd recording on an input that requires grad raises.
+Inference by default: a call with autograd recording on an input that requires grad raises. Training is an opt-in on both classes:
+    set_trainable(patterns=True)        marks the named parameters that match as leaves that take gradients (True: all; an iterable of fnmatch patterns)
+    trainable_parameters()              name -> leaf tensor, for unigen_amd.optim.AdamW
+    enable_gradient_checkpointing()     recompute each block in the backward
+After set_trainable(), forward on inputs or parameters that require grad runs unigen_amd/training.py's sana_block_forward / sana_forward: the same
+kernels on the autograd Functions of unigen_amd/autograd.py (ug_linear_attn_bwd, ug_glu_dwconv3x3_bwd, ug_flash_attn_bwd, the GEMMs). Gradients arrive at
+the NAMED parameters; a packed copy is rebuilt, into its own buffer, when a version counter of one of its named tensors has moved (an in-place optimizer
+step), so the next forward, training or inference, sees the new values. A load_state_dict() after the opt-in selects the same parameters again.
 """
 from __future__ import annotations
 
@@ -102,6 +109,11 @@ class _Params:
         self._device, self._dtype = torch.device(device) if device is not None else torch.device("cpu"), dtype
         self._sd: Dict[str, torch.Tensor] = {}
         self._buf: Dict[tuple, Dict[str, torch.Tensor]] = {}
+        self._trainable_on = False                       # set_trainable() was called: forward may take the differentiable path
+        self._grad_checkpoint = False
+        self._patterns = None                            # what set_trainable() was last given (re-applied by a later load_state_dict)
+        self._owned = False                              # a block of a model: the model's set_trainable() hands it its leaf tensors
+        self._pv: Dict[str, tuple] = {}                  # packed copy -> its sources' version counters when it was built
 
     dtype = property(lambda self: self._dtype)
     device = property(lambda self: self._device)
@@ -122,6 +134,8 @@ class _Params:
                 self._sd[k] = sd[k].detach().to(device=self._device, dtype=self._dtype).contiguous()
         if not missing:
             self._pack()
+            if self._trainable_on and not self._owned:   # the leaves were replaced: select them again (a model re-shares them with its blocks)
+                self.set_trainable(self._patterns)
         return missing, unexpected
 
     def init_synthetic_(self, seed: int = 0):
@@ -139,6 +153,69 @@ class _Params:
             sd[k] = t.to(self._dtype)
         self.load_state_dict(sd)
         return self
+
+    # ---- training opt-in ----
+    def set_trainable(self, patterns=True):
+        """Opt in to the differentiable forward. patterns: True - every named parameter takes gradients; False / None / () - none does (gradients
+        still reach the inputs); else an iterable of fnmatch patterns over the state-dict keys ("transformer_blocks.1.*", "*.attn2.to_q.weight")."""
+        import fnmatch
+        if not self._p:
+            raise RuntimeError(f"{type(self).__name__}: load_state_dict first")
+        pats = [patterns] if isinstance(patterns, str) else (None if patterns is True else list(patterns or ()))
+        for k, t in self._sd.items():
+            t.requires_grad_(pats is None or any(fnmatch.fnmatchcase(k, p) for p in pats))
+            if not t.requires_grad:
+                t.grad = None
+        self._trainable_on, self._patterns = True, patterns
+        self._share_leaves()
+        return self
+
+    def trainable_parameters(self) -> Dict[str, torch.Tensor]:
+        """name -> leaf tensor of every parameter set_trainable() selected (their .grad is filled by backward())"""
+        return {k: t for k, t in self._sd.items() if t.requires_grad}
+
+    def enable_gradient_checkpointing(self):
+        """recompute each block in the backward instead of keeping its activations (torch.utils.checkpoint around the block)"""
+        self._grad_checkpoint = True
+
+    def disable_gradient_checkpointing(self):
+        self._grad_checkpoint = False
+
+    def _share_leaves(self) -> None:
+        pass
+
+    def _builders(self) -> Dict[str, tuple]:
+        """packed copy -> (the named tensors it is built from, a function that builds it); no sources: a view of a named tensor, always current"""
+        raise NotImplementedError
+
+    def _pack(self) -> None:
+        with torch.no_grad():
+            b = self._builders()
+            self._p = {n: build() for n, (_, build) in b.items()}
+        self._pv = {n: tuple(self._sd[k]._version for k in srcs) for n, (srcs, _) in b.items()}
+
+    def _sync(self, training: bool = False) -> None:
+        """After the opt-in the named tensors may change in place (an optimizer step) and the packed copies are not views of them. A copy whose
+        sources' version counters have moved is rebuilt INTO ITS BUFFER (no new storage), and the transposes autograd cached of it are dropped.
+        Copies of frozen parameters never move, so their cached transposes stay. The differentiable path (training=True) reads a copy only where a
+        source is frozen, so it skips the copies of trainable parameters: those are brought up to date by the next inference forward.
+        Before the opt-in this is one attribute test."""
+        if not self._trainable_on:
+            return
+        for n, (srcs, build) in self._builders().items():
+            if not srcs or self._p.get(n) is None or (training and all(self._sd[k].requires_grad for k in srcs)):
+                continue
+            v = tuple(self._sd[k]._version for k in srcs)
+            if v != self._pv.get(n):
+                from . import autograd
+                with torch.no_grad():
+                    self._p[n].copy_(build())
+                autograd.evict_weight(self._p[n])
+                self._pv[n] = v
+
+    def _wants_grad(self, *tensors) -> bool:
+        return self._trainable_on and torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors) or
+                                                                   any(t.requires_grad for t in self._sd.values()))
 
     def _buffers(self, key: tuple) -> Dict[str, torch.Tensor]:
         """the activations and workspaces of one input shape: allocated at the first call with that shape, reused afterwards"""
@@ -168,7 +245,7 @@ class SanaTransformerBlock(_Params):
         if qk_norm is not None:
             raise NotImplementedError(f"SanaTransformerBlock: qk_norm = {qk_norm!r} is not implemented (Sana 1.5's rms_norm_across_heads is {FOLLOW_UP})")
         if dropout != 0:
-            raise NotImplementedError(f"SanaTransformerBlock: dropout = {dropout} is not implemented (inference only; training is {FOLLOW_UP})")
+            raise NotImplementedError(f"SanaTransformerBlock: dropout = {dropout} is not implemented (dropout in training is {FOLLOW_UP})")
         if norm_elementwise_affine or not attention_out_bias:
             raise NotImplementedError(f"SanaTransformerBlock: norm_elementwise_affine = True / attention_out_bias = False are not implemented ({FOLLOW_UP})")
         if attention_head_dim != 32 or num_attention_heads * attention_head_dim != dim:
@@ -207,13 +284,11 @@ class SanaTransformerBlock(_Params):
         e["ff.conv_point.weight"] = (D, C, 1, 1)
         return e
 
-    def _pack(self) -> None:
-        s, p = self._sd, {}
+    def _builders(self) -> Dict[str, tuple]:
+        s = self._sd
         D, C, Cp, Hc, dc, dp = self.dim, self.C, self.Cp, self.cross_heads, self.cross_dh, self.cross_dp
         z = lambda *shape: torch.zeros(*shape, dtype=self._dtype, device=self._device)
-        p["table"] = s["scale_shift_table"].reshape(1, 6 * D).contiguous()
-        p["qkv_w"] = torch.cat([s[f"attn1.{n}.weight"] for n in ("to_q", "to_k", "to_v")], 0).contiguous()
-        p["qkv_b"] = torch.cat([s[f"attn1.{n}.bias"] for n in ("to_q", "to_k", "to_v")], 0).contiguous() if self.attention_bias else None
+        qkv = ("to_q", "to_k", "to_v")
 
         def slots_w(w):                                  # [Hc dc, K] -> [Hc dp, K], zero rows behind each head
             out = z(Hc, dp, w.shape[1])
@@ -224,18 +299,30 @@ class SanaTransformerBlock(_Params):
             out = z(Hc, dp)
             out[:, :dc] = b.reshape(Hc, dc)
             return out.reshape(-1)
-        p["q2_w"], p["q2_b"] = slots_w(s["attn2.to_q.weight"]), slots_b(s["attn2.to_q.bias"])
-        p["kv2_w"] = torch.cat([slots_w(s["attn2.to_k.weight"]), slots_w(s["attn2.to_v.weight"])], 0).contiguous()
-        p["kv2_b"] = torch.cat([slots_b(s["attn2.to_k.bias"]), slots_b(s["attn2.to_v.bias"])], 0).contiguous()
-        o2 = z(D, Hc, dp)
-        o2[:, :, :dc] = s["attn2.to_out.0.weight"].reshape(D, Hc, dc)
-        p["o2_w"] = o2.reshape(D, Hc * dp)
-        p["inv_w"] = s["ff.conv_inverted.weight"].reshape(2 * C, D)
-        p["dw_w"] = s["ff.conv_depth.weight"].reshape(2 * C, 9).t().contiguous()                  # [9][2C], tap ky 3 + kx major
-        pt = z(D, Cp)
-        pt[:, :C] = s["ff.conv_point.weight"].reshape(D, C)
-        p["pt_w"] = pt
-        self._p = p
+
+        def o2():
+            out = z(D, Hc, dp)
+            out[:, :, :dc] = s["attn2.to_out.0.weight"].reshape(D, Hc, dc)
+            return out.reshape(D, Hc * dp)
+
+        def pt():
+            out = z(D, Cp)
+            out[:, :C] = s["ff.conv_point.weight"].reshape(D, C)
+            return out
+        wn, bn = [f"attn1.{n}.weight" for n in qkv], [f"attn1.{n}.bias" for n in qkv]
+        return {
+            "table": ([], lambda: s["scale_shift_table"].reshape(1, 6 * D)),                        # a view
+            "qkv_w": (wn, lambda: torch.cat([s[k] for k in wn], 0).contiguous()),
+            "qkv_b": (bn if self.attention_bias else [], lambda: torch.cat([s[k] for k in bn], 0).contiguous() if self.attention_bias else None),
+            "q2_w": (["attn2.to_q.weight"], lambda: slots_w(s["attn2.to_q.weight"])),
+            "q2_b": (["attn2.to_q.bias"], lambda: slots_b(s["attn2.to_q.bias"])),
+            "kv2_w": (["attn2.to_k.weight", "attn2.to_v.weight"], lambda: torch.cat([slots_w(s["attn2.to_k.weight"]), slots_w(s["attn2.to_v.weight"])], 0)),
+            "kv2_b": (["attn2.to_k.bias", "attn2.to_v.bias"], lambda: torch.cat([slots_b(s["attn2.to_k.bias"]), slots_b(s["attn2.to_v.bias"])], 0)),
+            "o2_w": (["attn2.to_out.0.weight"], o2),
+            "inv_w": ([], lambda: s["ff.conv_inverted.weight"].reshape(2 * C, D)),              # a view
+            "dw_w": (["ff.conv_depth.weight"], lambda: s["ff.conv_depth.weight"].reshape(2 * C, 9).t().contiguous()),     # [9][2C], tap ky 3 + kx major
+            "pt_w": (["ff.conv_point.weight"], pt),
+        }
 
     def _mask_runs(self, mask: Optional[torch.Tensor], B: int, T: int):
         """mask_runs() of a mask, read on the host once per mask tensor. An entry holds the tensor ITSELF and its version counter: an address is no
@@ -260,7 +347,11 @@ class SanaTransformerBlock(_Params):
             raise ValueError("SanaTransformerBlock.forward needs encoder_hidden_states, timestep, height and width")
         if not self._p:
             raise RuntimeError("SanaTransformerBlock: load_state_dict first")
-        _no_autograd(hidden_states, encoder_hidden_states, timestep)
+        train = self._wants_grad(hidden_states, encoder_hidden_states, timestep)
+        if not train:
+            _no_autograd(hidden_states, encoder_hidden_states, timestep)
+        if _bufs is None:                                # (a model has brought its blocks up to date)
+            self._sync(train)
         dt, D, H1 = self._dtype, self.dim, self.heads
         B, N, _ = hidden_states.shape
         T = encoder_hidden_states.shape[1]
@@ -272,6 +363,10 @@ class SanaTransformerBlock(_Params):
             if t.dtype != dt or not t.is_contiguous():
                 raise TypeError(f"SanaTransformerBlock.forward: {n} must be a contiguous {dt} tensor")
         runs = _runs if _runs is not None else self._mask_runs(encoder_attention_mask, B, T)
+        if train:
+            from . import training
+            return training._sana_ckpt(self, lambda h_, e_, t_: training.sana_block_forward(self, h_, e_, t_, height, width, runs), hidden_states,
+                                       encoder_hidden_states, timestep)
         p, M = self._p, B * N
         Hc, dp, C, Cp = self.cross_heads, self.cross_dp, self.C, self.Cp
         W2 = Hc * dp
@@ -373,20 +468,46 @@ class SanaTransformer2DModel(_Params):
         return e
 
     def _pack(self) -> None:
-        c, D, s, p = self.config, self.D, self._sd, {}
         for i, b in enumerate(self.blocks):
             pre = f"transformer_blocks.{i}."
-            b.load_state_dict({k[len(pre):]: v for k, v in s.items() if k.startswith(pre)})
-        w = torch.zeros(D, self.Kin, dtype=self._dtype, device=self._device)
-        w[:, :c["in_channels"]] = s["patch_embed.proj.weight"].reshape(D, -1)
-        p["patch_w"] = w
-        w = torch.zeros(self.Pout, D, dtype=self._dtype, device=self._device)
-        w[:c["out_channels"]] = s["proj_out.weight"]
-        b = torch.zeros(self.Pout, dtype=self._dtype, device=self._device)
-        b[:c["out_channels"]] = s["proj_out.bias"]
-        p["out_w"], p["out_b"] = w, b
-        self._p = p
+            b.load_state_dict({k[len(pre):]: v for k, v in self._sd.items() if k.startswith(pre)})
+        super()._pack()
         self._pos.clear()
+
+    def _share_leaves(self) -> None:
+        """the blocks hold aliases of the model's tensors (load_state_dict detaches): hand them the leaf objects themselves, so that a block's
+        gradient arrives at the tensor trainable_parameters() returns (same storage and version counter: the blocks' packed copies stay valid)"""
+        for i, b in enumerate(self.blocks):
+            pre = f"transformer_blocks.{i}."
+            for k, t in self._sd.items():
+                if k.startswith(pre):
+                    b._sd[k[len(pre):]] = t
+            b._trainable_on = b._owned = True
+
+    def _sync(self, training: bool = False) -> None:
+        if self._trainable_on:
+            super()._sync(training)
+            for b in self.blocks:                        # each block looks at its own copies
+                b._sync(training)
+
+    def _builders(self) -> Dict[str, tuple]:
+        c, D, s = self.config, self.D, self._sd
+        z = lambda *shape: torch.zeros(*shape, dtype=self._dtype, device=self._device)
+        oc = c["out_channels"]
+
+        def rows(name, n):                               # proj_out's weight / bias, zero rows up to n
+            out = z(n, *s[name].shape[1:])
+            out[:oc] = s[name]
+            return out
+
+        def patch():
+            w = z(D, self.Kin)
+            w[:, :c["in_channels"]] = s["patch_embed.proj.weight"].reshape(D, -1)
+            return w
+        return {"patch_w": (["patch_embed.proj.weight"], patch),
+                "out_w": (["proj_out.weight"], lambda: rows("proj_out.weight", self.Pout)), "out_b": (["proj_out.bias"], lambda: rows("proj_out.bias", self.Pout)),
+                # the differentiable path: out_features is the contraction length of dX = dY W, a multiple of 64
+                "out_w64": (["proj_out.weight"], lambda: rows("proj_out.weight", _pad(oc, 64))), "out_b64": (["proj_out.bias"], lambda: rows("proj_out.bias", _pad(oc, 64)))}
 
     def position_table(self, H: int, W: int) -> Optional[torch.Tensor]:
         """fp32 [H W, D] on the device, built once per (H, W) on the host in float64; None when interpolation_scale is None (no table is added)"""
@@ -429,7 +550,10 @@ class SanaTransformer2DModel(_Params):
             raise NotImplementedError(f"SanaTransformer2DModel: attention_mask is not implemented (the linear attention takes none; it is {FOLLOW_UP})")
         if not self._p:
             raise RuntimeError("SanaTransformer2DModel: load_state_dict first")
-        _no_autograd(hidden_states, encoder_hidden_states, timestep)
+        train = self._wants_grad(hidden_states, encoder_hidden_states, timestep)
+        if not train:
+            _no_autograd(hidden_states, encoder_hidden_states, timestep)
+        self._sync(train)
         c, D, dt, s, p = self.config, self.D, self._dtype, self._sd, self._p
         B, Cin, H, W = hidden_states.shape
         T = encoder_hidden_states.shape[1]
@@ -437,6 +561,9 @@ class SanaTransformer2DModel(_Params):
             raise ValueError(f"SanaTransformer2DModel.forward: shapes {tuple(hidden_states.shape)}, {tuple(encoder_hidden_states.shape)}, {tuple(timestep.shape)}")
         if hidden_states.dtype != dt or encoder_hidden_states.dtype != dt:
             raise TypeError(f"SanaTransformer2DModel.forward: hidden_states and encoder_hidden_states must be {dt}")
+        if train:
+            from . import training
+            return training.sana_forward(self, hidden_states, encoder_hidden_states, timestep, encoder_attention_mask)
         N, M = H * W, B * H * W
         runs = self.blocks[0]._mask_runs(encoder_attention_mask, B, T) if self.blocks else None
         bufs = self._buffers((B, H, W, T))

@@ -487,3 +487,110 @@ def sd3_forward(model, hidden_states, condition_hidden_states=None, conditioning
     out = _lin(model, "proj_out", A.adaln_modulate(x.contiguous(), e[1], e[0]))
     out = out.view(B, h, w, p, p, model.out_channels).permute(0, 5, 1, 3, 2, 4).reshape(B, model.out_channels, h * p, w * p)
     return out, dict(moe_loss=moe["l_aux"] * 0.1), dict(expert_counts=moe["exp_counts"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Sana (unigen_amd/sana.py: diffusers' SanaTransformerBlock / SanaTransformer2DModel)
+# ---------------------------------------------------------------------------------------------------------------------
+def _pad_rows(w, groups: int, have: int, want: int):
+    """[groups * have, K] (or [groups * have]) -> [groups * want, ...] with zero rows behind each group: the padded cross-attention head slots of
+    sana._pack, as differentiable torch glue on the named parameter (its gradient is the slots' live rows)."""
+    if have == want:
+        return w
+    t = w.reshape(groups, have, -1)
+    t = F.pad(t, (0, 0, 0, want - have))
+    return t.reshape(groups * want, -1) if w.dim() == 2 else t.reshape(groups * want)
+
+
+def _sana_w(blk, name: str, packed: str, make):
+    """A weight in the layout the kernels want: the load-time copy of sana._pack when the named parameter is frozen (current: the caller has run
+    _sync()), else built from the named leaf by differentiable torch glue, so that its gradient arrives at the named parameter."""
+    w = blk._sd[name]
+    return make(w) if w.requires_grad else blk._p[packed]
+
+
+def sana_block_forward(blk, hidden_states, encoder_hidden_states, timestep, height: int, width: int, runs):
+    """SanaTransformerBlock.forward under autograd: the kernels and rounding points of the inference forward (unigen_amd/sana.py) on the autograd
+    Functions of unigen_amd/autograd.py. hidden_states [B, N, D], encoder_hidden_states [B, T, cross_attention_dim], timestep [B, 6 D];
+    runs: sana.mask_runs() of the encoder attention mask."""
+    s, D, H1, Hc, dc, dp, C, Cp = blk._sd, blk.dim, blk.heads, blk.cross_heads, blk.cross_dh, blk.cross_dp, blk.C, blk.Cp
+    B, N, _ = hidden_states.shape
+    T = encoder_hidden_states.shape[1]
+    mod = (s["scale_shift_table"].reshape(1, 6 * D) + timestep).view(B, 6, D)             # table add on [B, 6 D]: torch, one rounding as ug_add_bf16
+    sh_a, sc_a, g_a, sh_m, sc_m, g_m = (mod[:, i] for i in range(6))
+    # --- self attention: ReLU linear attention on the column blocks of the fused projection ---
+    n1 = A.adaln_modulate(hidden_states, sh_a, sc_a, blk.norm_eps)
+    def qkv(i, n, kind):                                 # frozen: row block i of the load-time pack [q; k; v] (all three frozen: neighbours, one GEMM)
+        t = s.get(f"attn1.{n}.{kind}")
+        return t if t is None or t.requires_grad else blk._p["qkv_w" if kind == "weight" else "qkv_b"][i * D:(i + 1) * D]
+    names = ("to_q", "to_k", "to_v")
+    q, k, v = A.linear_n(n1, [qkv(i, n, "weight") for i, n in enumerate(names)], [qkv(i, n, "bias") for i, n in enumerate(names)])
+    att = A.linear_attention(q, k, v, H1)
+    h1 = A.gate_residual(hidden_states, A.linear(att, s["attn1.to_out.0.weight"], s["attn1.to_out.0.bias"]), g_a)
+    # --- cross attention on the padded head slots, the true scale ---
+    slot_w = lambda w: _pad_rows(w, Hc, dc, dp)
+    q2 = A.linear(h1, _sana_w(blk, "attn2.to_q.weight", "q2_w", slot_w), _sana_w(blk, "attn2.to_q.bias", "q2_b", slot_w))
+    W2 = Hc * dp
+
+    def kv(i, n, kind):                                  # frozen: row block i of the load-time pack [k slots; v slots] (neighbours: one GEMM)
+        t = s[f"attn2.{n}.{kind}"]
+        return slot_w(t) if t.requires_grad else blk._p["kv2_w" if kind == "weight" else "kv2_b"][i * W2:(i + 1) * W2]
+    kv_w = [kv(i, n, "weight") for i, n in enumerate(("to_k", "to_v"))]
+    kv_b = [kv(i, n, "bias") for i, n in enumerate(("to_k", "to_v"))]
+    k2, v2 = A.linear_n(encoder_hidden_states, kv_w, kv_b)
+    outs = [A.attention(q2[b0:b0 + nb], k2[b0:b0 + nb, :keys], v2[b0:b0 + nb, :keys], Hc, scale=dc ** -0.5) for b0, nb, keys in runs]
+    a2 = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    o2_w = _sana_w(blk, "attn2.to_out.0.weight", "o2_w", lambda w: F.pad(w.reshape(D, Hc, dc), (0, dp - dc)).reshape(D, W2) if dp != dc else w)
+    h2 = A.linear_res_scale(h1, a2, o2_w, s["attn2.to_out.0.bias"], 1.0)
+    # --- Mix-FFN ---
+    n2 = A.adaln_modulate(h2, sh_m, sc_m, blk.norm_eps)
+    u = A.linear(n2, s["ff.conv_inverted.weight"].view(2 * C, D), s["ff.conv_inverted.bias"])
+    glu = A.GluDwConv.apply(u.view(B * N, 2 * C), s["ff.conv_depth.weight"], s["ff.conv_depth.bias"], B, height, width, C, Cp)
+    pt_w = _sana_w(blk, "ff.conv_point.weight", "pt_w", lambda w: F.pad(w.view(D, C), (0, Cp - C)) if Cp != C else w.view(D, C))
+    f = A.linear(glu, pt_w, None)
+    return A.gate_residual(h2, f.view(B, N, D), g_m)
+
+
+def _sana_ckpt(model, fn, *tensors):
+    if getattr(model, "_grad_checkpoint", False):
+        from torch.utils.checkpoint import checkpoint
+        return checkpoint(fn, *tensors, use_reentrant=False)
+    return fn(*tensors)
+
+
+def sana_forward(model, hidden_states, encoder_hidden_states, timestep, encoder_attention_mask=None):
+    """SanaTransformer2DModel.forward under autograd: [B, C, H, W] -> [B, out_channels, H, W]. The GEMMs, the modulated norms, both attentions and the
+    Mix-FFN run the HIP kernels; what stays torch on the GPU is the glue the inference path does in small kernels of its own: the layout changes, the
+    position-table add, the SiLUs of the timestep MLP on [B, D], the caption RMSNorm on [B T, D] and the modulation-table adds."""
+    c, D, dt, s = model.config, model.D, model.dtype, model._sd
+    B, Cin, H, W = hidden_states.shape
+    T = encoder_hidden_states.shape[1]
+    N, M = H * W, B * H * W
+    runs = model.blocks[0]._mask_runs(encoder_attention_mask, B, T) if model.blocks else None
+    # patch embedding at patch_size 1: a linear on the pixels, K = in_channels zero-padded to the GEMM's granularity
+    x = F.pad(hidden_states.permute(0, 2, 3, 1).reshape(M, Cin), (0, model.Kin - Cin))
+    pw = s["patch_embed.proj.weight"]
+    pw = F.pad(pw.view(D, Cin), (0, model.Kin - Cin)) if pw.requires_grad else model._p["patch_w"]
+    h = A.linear(x, pw, s["patch_embed.proj.bias"]).view(B, N, D)
+    pos = model.position_table(H, W)
+    if pos is not None:
+        h = (h.float() + pos[None]).to(dt)
+    # AdaLayerNormSingle
+    tp = ops.timestep_embed(timestep.reshape(B).to(device=h.device, dtype=torch.float32), torch.empty(B, 256, device=h.device, dtype=dt))
+    lin = lambda name, t: A.linear(t, s[name + ".weight"], s[name + ".bias"])
+    et = lin("time_embed.emb.timestep_embedder.linear_2", F.silu(lin("time_embed.emb.timestep_embedder.linear_1", tp)))
+    mod = lin("time_embed.linear", F.silu(et))
+    # caption projection (linear, GELU-tanh, linear) and RMSNorm
+    enc = encoder_hidden_states.reshape(B * T, c["caption_channels"])
+    c2 = lin("caption_projection.linear_2", A.GeluTanh.apply(lin("caption_projection.linear_1", enc)))
+    cn = ((c2.float() * torch.rsqrt(c2.float().pow(2).mean(-1, keepdim=True) + 1e-5)).to(dt) * s["caption_norm.weight"]).view(B, T, D)
+    for blk in model.blocks:
+        h = _sana_ckpt(model, lambda h_, cn_, mod_, blk=blk: sana_block_forward(blk, h_, cn_, mod_, H, W, runs), h, cn, mod)
+    # SanaModulatedNorm: (scale_shift_table[None] + embedded_timestep[:, None]).chunk(2, 1) = shift, scale
+    fm = s["scale_shift_table"][None] + et[:, None]
+    nf = A.adaln_modulate(h, fm[:, 0], fm[:, 1], c["norm_eps"])
+    oc = c["out_channels"]
+    P64 = (oc + 63) // 64 * 64                                                               # out_features is the contraction length of dX = dY W
+    ow, ob = s["proj_out.weight"], s["proj_out.bias"]
+    y = A.linear(nf, F.pad(ow, (0, 0, 0, P64 - oc)) if ow.requires_grad else model._p["out_w64"], F.pad(ob, (0, P64 - oc)) if ob.requires_grad else model._p["out_b64"])
+    return y[:, :, :oc].reshape(B, H, W, oc).permute(0, 3, 1, 2).contiguous()
