@@ -137,11 +137,23 @@ int ug_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t batches, int64_t rows_per_
 /* O = softmax(Q K^T / sqrt(dh)) V, non-causal, no mask; Q rows [Lq], K/V rows [Lkv]; head h occupies
  * columns [h*dh, (h+1)*dh) of each row. Strides in elements. Replaces F.scaled_dot_product_attention
  * (src/UniGenUtils.py:601 and diffusers FluxAttnProcessor2_0). dh in {64, 128}.
- * Row strides: the bf16 kernels of this family (ug_flash_attn_fwd, ug_flash_attn_fwd_lse, ug_flash_attn_bwd, ug_flash_attn_fwd_wide) stream K / V
- * (the backward: Q / dO too) with LDS-DMAs whose per-lane byte offsets over a 64-row tile are 32-bit, 2 (63 rs + 120) < 2^32. One rule for every
- * row stride of the three narrow entry points - q, k, v, o and the backward's dout, dq, dk, dv -: 0 < rs < 2^24 elements, UG_ERR_UNSUPPORTED
- * otherwise (the widest row of the package is 21 504). Batch strides are 64-bit everywhere: any multiple of 8 (o: 4). The fp32 twins
- * (ug_flash_attn_fwd_f32, _wide_f32, _bias_f32) and ug_flash_attn_fwd_bias with a table or a mask index in 64 bits and take any row stride. */
+ *
+ * Strided attention views. Every attention entry point takes each operand as a view (pointer, row stride, batch stride), strides in elements, so
+ * that the column blocks of a packed buffer are read and written in place. One checker (csrc/ug_common.h: ug_check_views) applies, per view,
+ * a multiple both strides must have, an alignment of the base in bytes (either missed: UG_ERR_BAD_ALIGN) and, for some, 0 < row stride < 2^24
+ * (UG_ERR_UNSUPPORTED; looked at only when every view of the call is aligned). Batch strides are 64-bit everywhere.
+ *   entry                                          stride multiple / base alignment                    row stride in (0, 2^24)
+ *   ug_flash_attn_fwd, _fwd_lse                    q, k, v: 8 / 16;  o: 4 / 8                          q, k, v, o
+ *   ug_flash_attn_fwd_wide                         q, k, v: 8 / 16;  o: 4 / 8                          k, v
+ *   ug_flash_attn_fwd_bias (table or mask given)   q, k, v: 8 / 16;  o: 4 / 8                          none
+ *   ug_flash_attn_fwd_f32, _bias_f32, _wide_f32    all: 4 / 16                                         none
+ *   ug_flash_attn_bwd                              all eight: 8;  q, k, v, o, dout: 16;  dq, dk, dv: 8 all eight
+ *   ug_linear_attn, _bwd (fp32 twins)              all: 8 (4) / 16;  workspace and state: 16           none
+ * The bound is there because the bf16 kernels stream K / V (the backward: Q / dO too) with LDS-DMAs whose per-lane byte offsets over a 64-row tile
+ * are 32-bit, 2 (63 rs + 120) < 2^32; the narrow entry points apply it to every row stride (the widest row of the package is 21 504). The fp32
+ * twins and ug_flash_attn_fwd_bias with a table or a mask index in 64 bits. Before the views an entry point returns UG_OK when there is nothing to
+ * do (batches or Lq / N zero: no pointer is looked at), then refuses null operands and non-positive counts (UG_ERR_BAD_SHAPE), then its head width
+ * and a sequence of 2^30 or more (UG_ERR_UNSUPPORTED); after them come the grid limits and, in the backward, the workspace (UG_ERR_BAD_SHAPE). */
 int ug_flash_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
                       const void* k, int64_t k_row_stride, int64_t k_batch_stride,
                       const void* v, int64_t v_row_stride, int64_t v_batch_stride,
@@ -150,9 +162,8 @@ int ug_flash_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_batch_strid
                       float softmax_scale, ug_stream_t stream);
 
 /* ug_flash_attn_fwd at head width 512: the single-head mid-block attention of AutoencoderKL (diffusers Attention(heads = 1, dim_head = 512);
- * unigen_amd/vae.py), without the [Lq, Lkv] score matrix in memory. Same arguments, strides in elements, same stride and alignment rules
- * (q / k / v row and batch strides multiples of 8, bases 16-byte aligned; o: multiples of 4, 8-byte aligned); any Lq, Lkv >= 1. dh must be 512
- * (UG_ERR_UNSUPPORTED otherwise; 64 and 128 stay with ug_flash_attn_fwd), K / V row strides within (0, 2^24), softmax_scale > 0.
+ * unigen_amd/vae.py), without the [Lq, Lkv] score matrix in memory. Same arguments; views as in "Strided attention views" above; any Lq, Lkv >= 1. dh must be 512
+ * (UG_ERR_UNSUPPORTED otherwise; 64 and 128 stay with ug_flash_attn_fwd), softmax_scale > 0.
  * bf16 in / out, fp32 accumulation, online softmax, P rounded to bf16 as the P.V operand. No workspace, no atomics, no state between launches:
  * two launches give the same bits, and the launch can be captured in a graph (128 KiB of dynamic LDS; one workgroup = 128 query rows). */
 int ug_flash_attn_fwd_wide(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
@@ -376,7 +387,7 @@ int ug_flash_attn_fwd_f32(const void* q, int64_t q_row_stride, int64_t q_batch_s
                           void* o, int64_t o_row_stride, int64_t o_batch_stride,
                           int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
                           float softmax_scale, ug_stream_t stream);
-/* fp32 twin of ug_flash_attn_fwd_wide (dh = 512 only): plain FMA loops, exact online softmax; strides multiples of 4 elements, bases 16-byte aligned */
+/* fp32 twin of ug_flash_attn_fwd_wide (dh = 512 only): plain FMA loops, exact online softmax ("Strided attention views") */
 int ug_flash_attn_fwd_wide_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
                                const void* k, int64_t k_row_stride, int64_t k_batch_stride,
                                const void* v, int64_t v_row_stride, int64_t v_batch_stride,
@@ -829,8 +840,8 @@ int ug_minmax_to_u8(const float* d, int64_t B, int64_t HW, uint8_t* out, int32_t
  * with q' = relu(q), k' = relu(k), per (batch, head):
  *   S[d][j] = sum_n v[n][d] k'[n][j]     z[j] = sum_n k'[n][j]     out[n][d] = sum_j S[d][j] q'[n][j] / (sum_j z[j] q'[n][j] + 1e-15)
  * q, k, v are upcast, everything is fp32 (S and z included: they are never rounded to bf16), the output is rounded once. dh must be 32
- * (UG_ERR_UNSUPPORTED otherwise); any N >= 1. q / k / v / o take a row stride and a batch stride each, in elements (the packed [q | k | v] output of
- * one GEMM is read in place): multiples of 8 (fp32 twin: 4), bases 16-byte aligned, UG_ERR_BAD_ALIGN otherwise. The caller-owned, 16-byte aligned
+ * (UG_ERR_UNSUPPORTED otherwise); any N >= 1. q / k / v / o are views ("Strided attention views"; the packed [q | k | v] output of one GEMM is
+ * read in place). The caller-owned, 16-byte aligned
  * workspace of the size the query returns needs no initialisation: the per-chunk partial states are written, then summed in ascending chunk order, then
  * applied - three launches, no atomics, nothing kept between calls, so two calls give the same bits and the call can be captured in a graph.
  * GUARANTEE for the backward: on return the first batches * heads * 1056 floats of the workspace hold the state, per (batch, head) S^T[j][d]
@@ -856,7 +867,7 @@ int ug_glu_dwconv3x3_f32(const void* x, int64_t ldx, const void* w9, const void*
  * is no recompute path, and the forward's rounded output is not an input: o = S q' / den is recomputed in fp32. With g = dout / den,
  * c = -(dout . o) / den:  dq' = g S + c z,  dS = g^T q',  dz = c^T q',  dk' = v dS + dz,  dv = k' dS^T,  dq = dq' [q > 0],  dk = dk' [k > 0].
  * dS and dz stay fp32; dq, dk, dv are rounded once, at the store; each takes a row and a batch stride (the three may be the column blocks of one
- * [M][3 D] buffer: the dY of the fused QKV projection). Strides, alignment and limits as in the forward (state 16-byte aligned too); dh = 32 only, any
+ * [M][3 D] buffer: the dY of the fused QKV projection). Views ("Strided attention views") and limits as in the forward; dh = 32 only, any
  * N >= 1. The caller-owned, 16-byte aligned workspace of ug_linear_attn_bwd_workspace_bytes() needs no initialisation (smaller: UG_ERR_BAD_SHAPE): the
  * query pass writes dq and one partial dS | dz per 128 query rows, the partials are summed in ascending order, the key pass writes dk and dv - three
  * launches, no atomics, nothing kept between calls: two calls give the same bits, and the call can be captured in a graph. */

@@ -103,6 +103,37 @@ def test_flash_attn_bias(gpu, Lq, mode):
             assert e <= b and ew <= bw, (Lq, mode, dt, name, e, b, ew, bw)
 
 
+def test_fp32_twin_with_a_zero_table_is_the_plain_fp32_reference(gpu):
+    """ug_flash_attn_fwd_bias_f32 and ug_flash_attn_fwd_f32 are two instantiations of one kernel (csrc/verify_f32.hip): with an all-zero table and no
+    mask the biased one gives the plain one's bits. B = 2, H = 3, Lq = 70, Lkv = 65 (a ragged last 64-row block whose spare lanes re-read the
+    clamped row, keys past one 64-key tile), operands the column blocks of one packed [B, L, 3 H 64] buffer. With the mask added, the same call
+    meets the float64 reference at the twin's bound (rel-L2 <= 1e-5, every row <= 1e-4)."""
+    from unigen_amd import ops
+    B, H, Lq, Lkv, dh = 2, 3, 70, 65, 64
+    D, W = H * dh, 3 * H * dh
+    g = torch.Generator().manual_seed(7065)
+    qkv = torch.randn(B, Lq, W, generator=g, dtype=F32)
+    dev = qkv.to(gpu)
+    flat = dev.view(B * Lq, W)
+    zero = torch.zeros(H, 2 * Lq - 1, dtype=F32, device=gpu)
+    kw = dict(batches=B, heads=H, dh=dh, Lq=Lq, Lkv=Lkv, q_strides=(W, Lq * W), k_strides=(W, Lq * W), v_strides=(W, Lq * W), o_strides=(D, Lq * D), scale=dh ** -0.5)
+
+    def run(fn, **extra):
+        out = torch.full((B, Lq, D), float("nan"), device=gpu, dtype=F32)
+        fn(flat, flat[:, D:], flat[:, 2 * D:], out, **kw, **extra)
+        torch.cuda.synchronize()
+        return out.cpu()
+
+    plain, biased = run(ops.flash_attn), run(ops.flash_attn_bias, rel_table=zero, causal=False)
+    assert torch.isfinite(plain).all() and torch.equal(plain.view(torch.int32), biased.view(torch.int32)), "a zero table changed the plain reference's bits"
+    q, k, v = (qkv[:, :L_, i * D:(i + 1) * D].reshape(B, L_, H, dh) for i, L_ in ((0, Lq), (1, Lkv), (2, Lkv)))
+    truth = R.attention(q, k, v, dh ** -0.5, zero.cpu(), True)
+    got = run(ops.flash_attn_bias, rel_table=zero, causal=True).view(B, Lq, H, dh)
+    e, ew = rel_l2(got, truth), worst_row(got, truth)
+    print(f"TEXT attn f32 zero table + causal Lq={Lq} Lkv={Lkv}: rel_l2 {e:.3e} (bound 1e-5) worst row {ew:.3e} (bound 1e-4)")
+    assert e <= 1e-5 and ew <= 1e-4, (e, ew)
+
+
 @pytest.mark.parametrize("heads", (2, 64))
 @pytest.mark.parametrize("Lq", (1, 77, 512))
 def test_t5_rel_table_bit_exact(gpu, Lq, heads):

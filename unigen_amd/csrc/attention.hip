@@ -1102,23 +1102,19 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
 
 }  // namespace
 
-static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k,
+static int flash_attn_fwd_impl(const char* who, const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k,
                                int64_t k_row_stride, int64_t k_batch_stride, const void* v, int64_t v_row_stride,
                                int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
                                int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale,
                                float* lse_out, int64_t lse_ld, ug_stream_t stream) {
     if (batches == 0 || Lq == 0) return UG_OK;
-    UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd: bad arguments");
-    UG_REQUIRE(dh == 128 || dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: head dim %d not in {64, 128}", dh);
-    UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: sequence too long");
-    UG_REQUIRE(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 8 == 0 && k_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 8),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd: strides must be multiples of 8 elements and bases 16-byte aligned");
-    // the LDS-DMAs of K and V form 32-bit byte offsets over a 64-row tile from the row stride cut to int (63 rs + 120 < 2^31 is what they can hold);
-    // one rule for every row stride of the family, the one of ug_flash_attn_fwd_wide
-    for (int64_t rs : {q_row_stride, k_row_stride, v_row_stride, o_row_stride})
-        UG_REQUIRE(rs > 0 && rs < (1 << 24), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: q / k / v / o row strides must be within (0, 2^24) elements");
+    UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
+    UG_REQUIRE(dh == 128 || dh == 64, UG_ERR_UNSUPPORTED, "%s: head dim %d not in {64, 128}", who, dh);
+    UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "%s: sequence too long", who);
+    // the row-stride bound: the LDS-DMAs of K and V form 32-bit byte offsets over a 64-row tile from the row stride cut to int (63 rs + 120 < 2^31
+    // is what they can hold); one rule for every row stride of the family, the one of ug_flash_attn_fwd_wide
+    const ug_view_rule views[] = {{"q", UG_VIEW(q), 8, 16, true}, {"k", UG_VIEW(k), 8, 16, true}, {"v", UG_VIEW(v), 8, 16, true}, {"o", UG_VIEW(o), 4, 8, true}};
+    if (const int rc = ug_check_views(who, views)) return rc;
 #ifdef UG_PROBE_BUILD     // probe library: every forward form, the UG_ATTN_* environment switches select (tools/probe/csrc/attn_fwd_variants.hip)
     return ug_attn_fwd_variants(q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
                                 o_batch_stride, batches, heads, Lq, Lkv, dh, softmax_scale, lse_out, lse_ld, stream);
@@ -1127,7 +1123,7 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
     // flash_attn_kernel. The dispatcher only chooses the DMA form at head width 64.
     const int nQ = (int)((Lq + 255) / 256);            // 8 waves x 32 query rows per workgroup
     const int64_t nwg = (int64_t)nQ * heads * batches;
-    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd: grid too large");
+    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: grid too large", who);
     const float c = softmax_scale * 1.4426950408889634f;
     // (Round 4: the same stagger on v_mfma_f32_16x16x32_bf16 - flash_attn_m16_kernel, probe library, UG_ATTN_M16=1 - measured +3.5...+4.2 % in a
     // sustained interleaved A/B at 4608^2 / 4096 x 4608 / 8192 x 8704 and -5.6 % INSIDE the cfg2 forward (1113 vs 1177 TFLOP/s, same box, same
@@ -1148,7 +1144,7 @@ static int flash_attn_fwd_impl(const void* q, int64_t q_row_stride, int64_t q_ba
     if (dh == 128) launch(flash_attn_kernel<128, false>);
     else if (bufd_ok) launch(flash_attn_kernel<64, true>);
     else launch(flash_attn_kernel<64, false>);
-    UG_CHECK_LAUNCH("ug_flash_attn_fwd");
+    UG_CHECK_LAUNCH(who);
     return UG_OK;
 }
 
@@ -1157,7 +1153,7 @@ extern "C" int ug_flash_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_
                                  int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
                                  int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale,
                                  ug_stream_t stream) {
-    return flash_attn_fwd_impl(q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
+    return flash_attn_fwd_impl(__func__, q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
                                o_batch_stride, batches, heads, Lq, Lkv, dh, softmax_scale, nullptr, 0, stream);
 }
 
@@ -1167,7 +1163,7 @@ extern "C" int ug_flash_attn_fwd_lse(const void* q, int64_t q_row_stride, int64_
                                      int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh, float softmax_scale,
                                      float* lse2, int64_t lse_ld, ug_stream_t stream) {
     UG_REQUIRE(lse2 && lse_ld >= Lq, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_lse: lse2 [batches][heads][lse_ld >= Lq] needed");
-    return flash_attn_fwd_impl(q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
+    return flash_attn_fwd_impl(__func__, q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride,
                                o_batch_stride, batches, heads, Lq, Lkv, dh, softmax_scale, lse2, lse_ld, stream);
 }
 
@@ -1236,13 +1232,11 @@ extern "C" int ug_flash_attn_bwd(const void* q, int64_t q_rs, int64_t q_bs, cons
     UG_REQUIRE(q && k && v && o && dout && dq && dk && dv && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_bwd: bad arguments");
     UG_REQUIRE(dh == 128 || dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: head dim %d not in {64, 128}", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: sequence too long");
-    const int64_t strides[] = {q_rs, q_bs, k_rs, k_bs, v_rs, v_bs, o_rs, o_bs, do_rs, do_bs, dq_rs, dq_bs, dk_rs, dk_bs, dv_rs, dv_bs};
-    for (int64_t sgl : strides) UG_REQUIRE(sgl % 8 == 0, UG_ERR_BAD_ALIGN, "ug_flash_attn_bwd: strides must be multiples of 8 elements");
-    UG_REQUIRE(ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16) && ug_aligned(dout, 16) && ug_aligned(dq, 8) &&
-               ug_aligned(dk, 8) && ug_aligned(dv, 8), UG_ERR_BAD_ALIGN, "ug_flash_attn_bwd: bases must be 16-byte aligned");
-    // as the forward: the streamed operands' LDS-DMAs hold 32-bit byte offsets over a 64-row tile (63 rs + 120 < 2^31); one rule for all eight
-    for (int64_t rs : {q_rs, k_rs, v_rs, o_rs, do_rs, dq_rs, dk_rs, dv_rs})
-        UG_REQUIRE(rs > 0 && rs < (1 << 24), UG_ERR_UNSUPPORTED, "ug_flash_attn_bwd: q / k / v / o / dout / dq / dk / dv row strides must be within (0, 2^24) elements");
+    // the row-stride bound as in the forward: the streamed operands' LDS-DMAs hold 32-bit byte offsets over a 64-row tile (63 rs + 120 < 2^31)
+    const ug_view_rule views[] = {{"q", {q, q_rs, q_bs}, 8, 16, true},          {"k", {k, k_rs, k_bs}, 8, 16, true},     {"v", {v, v_rs, v_bs}, 8, 16, true},
+                                  {"o", {o, o_rs, o_bs}, 8, 16, true},          {"dout", {dout, do_rs, do_bs}, 8, 16, true},
+                                  {"dq", {dq, dq_rs, dq_bs}, 8, 8, true},       {"dk", {dk, dk_rs, dk_bs}, 8, 8, true},  {"dv", {dv, dv_rs, dv_bs}, 8, 8, true}};
+    if (const int rc = ug_check_views("ug_flash_attn_bwd", views)) return rc;
     const int64_t stat_ld = (Lq + 63) / 64 * 64;
     UG_REQUIRE(workspace && ug_aligned(workspace, 16) && workspace_bytes >= ug_flash_attn_bwd_workspace_bytes(batches, heads, Lq), UG_ERR_BAD_SHAPE,
                "ug_flash_attn_bwd: workspace of ug_flash_attn_bwd_workspace_bytes() needed");
@@ -1266,12 +1260,11 @@ extern "C" int ug_flash_attn_bwd(const void* q, int64_t q_rs, int64_t q_bs, cons
     const bool pair_dq = gq2 < (1ll << 31) && (pdq == 2 || (pdq == 1 && dh == 128 && Lq >= 2048));
     (void)hipMemsetAsync(workspace, 0, (size_t)(2 * batches * heads * stat_ld) * sizeof(float), s);     // padded statistics rows read as 0
     const int64_t total = batches * Lq * heads;
-    if (dh == 128)
-        hipLaunchKernelGGL(attn_delta_kernel<128>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, (const bf16_t*)o, o_rs, o_bs, (const bf16_t*)dout, do_rs, do_bs,
-                           delta, stat_ld, total, (int)heads, (int)Lq);
-    else
-        hipLaunchKernelGGL(attn_delta_kernel<64>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, s, (const bf16_t*)o, o_rs, o_bs, (const bf16_t*)dout, do_rs, do_bs,
-                           delta, stat_ld, total, (int)heads, (int)Lq);
+    const auto delta_launch = [&](auto kernel, int per_wg) {        // per_wg: the (batch, query, head) items of a workgroup, 256 / (dh / 8)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((total + per_wg - 1) / per_wg)), dim3(256), 0, s, (const bf16_t*)o, o_rs, o_bs, (const bf16_t*)dout, do_rs,
+                           do_bs, delta, stat_ld, total, (int)heads, (int)Lq);
+    };
+    if (dh == 128) delta_launch(attn_delta_kernel<128>, 16); else delta_launch(attn_delta_kernel<64>, 32);
     const ug_attn_bwd_args a = {(const bf16_t*)q, q_rs, q_bs, (const bf16_t*)k, k_rs, k_bs, (const bf16_t*)v, v_rs, v_bs, (const bf16_t*)dout, do_rs, do_bs,
                                 (bf16_t*)dq, dq_rs, dq_bs, (bf16_t*)dk, dk_rs, dk_bs, (bf16_t*)dv, dv_rs, dv_bs, lse2, delta, stat_ld,
                                 batches, (int)heads, (int)Lq, (int)Lkv, c, softmax_scale, s};

@@ -303,13 +303,9 @@ extern "C" int ug_flash_attn_fwd_wide(const void* q, int64_t q_row_stride, int64
     UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_wide: bad arguments");
     UG_REQUIRE(dh == WDH, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide: head dim %d is not 512 (64 and 128: ug_flash_attn_fwd)", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide: sequence too long");
-    UG_REQUIRE(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 8 == 0 && k_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 8),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd_wide: strides must be multiples of 8 elements and bases 16-byte aligned");
-    // the LDS-DMAs address a tile's 32 rows with 32-bit byte offsets from the tile's base
-    UG_REQUIRE(k_row_stride > 0 && v_row_stride > 0 && k_row_stride < (1 << 24) && v_row_stride < (1 << 24), UG_ERR_UNSUPPORTED,
-               "ug_flash_attn_fwd_wide: K / V row strides must be within (0, 2^24) elements");
+    // the row-stride bound: the LDS-DMAs address a tile's 32 rows of K and V with 32-bit byte offsets from the tile's base
+    const ug_view_rule views[] = {{"q", UG_VIEW(q), 8, 16, false}, {"k", UG_VIEW(k), 8, 16, true}, {"v", UG_VIEW(v), 8, 16, true}, {"o", UG_VIEW(o), 4, 8, false}};
+    if (const int rc = ug_check_views(__func__, views)) return rc;
     UG_REQUIRE(softmax_scale > 0.f, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide: softmax_scale must be positive");
     const int nQ = (int)((Lq + WQR - 1) / WQR);
     const int64_t nwg = (int64_t)nQ * heads * batches;
@@ -333,10 +329,8 @@ extern "C" int ug_flash_attn_fwd_wide_f32(const void* q, int64_t q_row_stride, i
     UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_wide_f32: bad arguments");
     UG_REQUIRE(dh == WDH, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: head dim %d is not 512 (64 and 128: ug_flash_attn_fwd_f32)", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: sequence too long");
-    UG_REQUIRE(q_row_stride % 4 == 0 && k_row_stride % 4 == 0 && v_row_stride % 4 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 4 == 0 && k_batch_stride % 4 == 0 && v_batch_stride % 4 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd_wide_f32: strides must be multiples of 4 elements and bases 16-byte aligned");
+    const ug_view_rule views[] = {{"q", UG_VIEW(q), 4, 16, false}, {"k", UG_VIEW(k), 4, 16, false}, {"v", UG_VIEW(v), 4, 16, false}, {"o", UG_VIEW(o), 4, 16, false}};
+    if (const int rc = ug_check_views(__func__, views)) return rc;
     const int nQ = (int)((Lq + 15) / 16);
     const int64_t nwg = (int64_t)nQ * heads * batches;
     UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: grid too large");

@@ -11,6 +11,21 @@ void ug_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int ug_check_views(const char* who, const ug_view_rule* rules, int n) {
+    for (int i = 0; i < n; ++i) {
+        const ug_view_rule& r = rules[i];
+        // mult and align are powers of two: masks, not the divisions a run-time divisor would cost on every launch
+        UG_REQUIRE(((r.v.rs | r.v.bs) & (r.mult - 1)) == 0 && (reinterpret_cast<uintptr_t>(r.v.p) & (uintptr_t)(r.align - 1)) == 0, UG_ERR_BAD_ALIGN,
+                   "%s: %s: strides must be multiples of %d elements and the base %d-byte aligned", who, r.name, r.mult, r.align);
+    }
+    for (int i = 0; i < n; ++i) {
+        const ug_view_rule& r = rules[i];
+        UG_REQUIRE(!r.bounded || (r.v.rs > 0 && r.v.rs < (1 << 24)), UG_ERR_UNSUPPORTED,
+                   "%s: row strides must be within (0, 2^24) elements: %s has %lld", who, r.name, (long long)r.v.rs);
+    }
+    return UG_OK;
+}
+
 #include <stdlib.h>
 #include <string.h>
 #include <map>

@@ -199,9 +199,9 @@ int linear_attn_impl(const char* who, const void* q, int64_t q_rs, int64_t q_bs,
     UG_REQUIRE(q && k && v && o && workspace && batches > 0 && heads > 0 && N > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
     UG_REQUIRE(dh == LA_DH, UG_ERR_UNSUPPORTED, "%s: head dim %d is not 32", who, dh);
     constexpr int A = ElemT<T>::kF32 ? 4 : 8;              // elements of 16 bytes
-    UG_REQUIRE(q_rs % A == 0 && k_rs % A == 0 && v_rs % A == 0 && o_rs % A == 0 && q_bs % A == 0 && k_bs % A == 0 && v_bs % A == 0 && o_bs % A == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16) && ug_aligned(workspace, 16),
-               UG_ERR_BAD_ALIGN, "%s: strides must be multiples of %d elements and bases 16-byte aligned", who, A);
+    const ug_view_rule views[] = {{"q", {q, q_rs, q_bs}, A, 16, false}, {"k", {k, k_rs, k_bs}, A, 16, false}, {"v", {v, v_rs, v_bs}, A, 16, false},
+                                  {"o", {o, o_rs, o_bs}, A, 16, false}, {"workspace", {workspace, 0, 0}, A, 16, false}};
+    if (const int rc = ug_check_views(who, views)) return rc;
     // grid limits: y = head groups and z = batches below 65536; the reduce pass has one workgroup per (batch, head) on x
     UG_REQUIRE(N < (1ll << 30) && batches < 65536 && (heads + LA_HG - 1) / LA_HG < 65536 && batches * (int64_t)heads < (1ll << 31), UG_ERR_UNSUPPORTED,
                "%s: too large", who);

@@ -269,21 +269,18 @@ __global__ __launch_bounds__(256) void linattn_bwd_kv_kernel(const T* __restrict
     }
 }
 
-struct LaView { const void* p; int64_t rs, bs; };
-
 template <typename T>
-int linear_attn_bwd_impl(const char* who, LaView q, LaView k, LaView v, LaView dout, const float* state, LaView dq, LaView dk, LaView dv, int64_t batches,
+int linear_attn_bwd_impl(const char* who, ug_view q, ug_view k, ug_view v, ug_view dout, const float* state, ug_view dq, ug_view dk, ug_view dv, int64_t batches,
                          int32_t heads, int64_t N, int32_t dh, void* workspace, int64_t workspace_bytes, ug_stream_t stream) {
     if (batches == 0 || N == 0) return UG_OK;
     UG_REQUIRE(q.p && k.p && v.p && dout.p && dq.p && dk.p && dv.p && workspace && batches > 0 && heads > 0 && N > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
     UG_REQUIRE(state, UG_ERR_BAD_SHAPE, "%s: state (what ug_linear_attn left at the start of its workspace) is required; there is no recompute path", who);
     UG_REQUIRE(dh == LB_DH, UG_ERR_UNSUPPORTED, "%s: head dim %d is not 32", who, dh);
     constexpr int A = ElemT<T>::kF32 ? 4 : 8;              // elements of 16 bytes
-    const LaView views[7] = {q, k, v, dout, dq, dk, dv};
-    for (const LaView& w : views)
-        UG_REQUIRE(w.rs % A == 0 && w.bs % A == 0 && ug_aligned(w.p, 16), UG_ERR_BAD_ALIGN, "%s: strides must be multiples of %d elements and bases 16-byte aligned",
-                   who, A);
-    UG_REQUIRE(ug_aligned(state, 16) && ug_aligned(workspace, 16), UG_ERR_BAD_ALIGN, "%s: state and workspace must be 16-byte aligned", who);
+    const ug_view_rule views[] = {{"q", q, A, 16, false},   {"k", k, A, 16, false},   {"v", v, A, 16, false},   {"dout", dout, A, 16, false},
+                                  {"dq", dq, A, 16, false}, {"dk", dk, A, 16, false}, {"dv", dv, A, 16, false}, {"state", {state, 0, 0}, A, 16, false},
+                                  {"workspace", {workspace, 0, 0}, A, 16, false}};
+    if (const int rc = ug_check_views(who, views)) return rc;
     // grid limits: y = head groups and z = batches below 65536; the reduce pass has one workgroup per (batch, head) on x
     UG_REQUIRE(N < (1ll << 30) && batches < 65536 && (heads + LB_HG - 1) / LB_HG < 65536 && batches * (int64_t)heads < (1ll << 31), UG_ERR_UNSUPPORTED,
                "%s: too large", who);
@@ -530,9 +527,8 @@ extern "C" int64_t ug_linear_attn_bwd_workspace_bytes(int64_t batches, int64_t h
                        const float* state, void* dq, int64_t dq_row_stride, int64_t dq_batch_stride, void* dk, int64_t dk_row_stride, int64_t dk_batch_stride, \
                        void* dv, int64_t dv_row_stride, int64_t dv_batch_stride, int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace,       \
                        int64_t workspace_bytes, ug_stream_t stream)
-#define UG_LAB_ARGS(who) (who, {q, q_row_stride, q_batch_stride}, {k, k_row_stride, k_batch_stride}, {v, v_row_stride, v_batch_stride},                       \
-                          {dout, do_row_stride, do_batch_stride}, state, {dq, dq_row_stride, dq_batch_stride}, {dk, dk_row_stride, dk_batch_stride},            \
-                          {dv, dv_row_stride, dv_batch_stride}, batches, heads, N, dh, workspace, workspace_bytes, stream)
+#define UG_LAB_ARGS(who) (who, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), {dout, do_row_stride, do_batch_stride}, state, UG_VIEW(dq), UG_VIEW(dk), UG_VIEW(dv),      \
+                          batches, heads, N, dh, workspace, workspace_bytes, stream)
 extern "C" int ug_linear_attn_bwd UG_LAB_PARAMS { return linear_attn_bwd_impl<bf16_t> UG_LAB_ARGS("ug_linear_attn_bwd"); }
 extern "C" int ug_linear_attn_bwd_f32 UG_LAB_PARAMS { return linear_attn_bwd_impl<float> UG_LAB_ARGS("ug_linear_attn_bwd_f32"); }
 #undef UG_LAB_PARAMS

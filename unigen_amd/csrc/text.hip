@@ -5,7 +5,7 @@
 //   ug_rmsnorm_rows          T5LayerNorm;   ug_layernorm_rows   nn.LayerNorm with weight and bias
 //   ug_gated_gelu            gelu_new(a) * b over the two halves of the stacked [wi_0; wi_1] projection;   ug_quick_gelu   x sigmoid(1.702 x)
 //   ug_gelu_erf              0.5 x (1 + erf(x / sqrt 2)), the activation of SD3's second CLIP (OpenCLIP bigG)
-// and the `_f32` verification twin of each (fp32 storage, no intermediate rounding).
+// and the `_f32` verification twin of each (fp32 storage, no intermediate rounding); the attention twin runs verify_f32.hip's one fp32 kernel.
 //
 // The attention kernel is deliberately plain next to attention.hip's: at T5-XXL (512 tokens, 64 heads) attention is about 2 % of the encoder's
 // FLOPs. One workgroup = 4 waves = 128 query rows of one (batch, head), Q fragments in registers, K tiles of 64 keys staged row-major and V
@@ -146,67 +146,6 @@ __global__ __launch_bounds__(256) void attn_bias_kernel(
                 const u32x2 w = {pack2bf(oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv), pack2bf(oacc[db][4 * g + 2] * inv, oacc[db][4 * g + 3] * inv)};
                 *(u32x2*)(op + db * 32 + g * 8 + 4 * h) = w;
             }
-    }
-}
-
-// fp32 twin: verify_f32.hip's one-thread-per-query kernel with the bias (same LDS table, natural base) and the causal limit
-template <int DH>
-__global__ __launch_bounds__(64) void attn_bias_f32_kernel(
-    const float* __restrict__ q, int64_t q_rs, int64_t q_bs, const float* __restrict__ k, int64_t k_rs, int64_t k_bs,
-    const float* __restrict__ v, int64_t v_rs, int64_t v_bs, float* __restrict__ o, int64_t o_rs, int64_t o_bs,
-    const float* __restrict__ rel_table, int rel_len, int causal, int heads, int Lq, int Lkv, int nQ, float scale) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float (*qs)[DH + 4] = (float (*)[DH + 4])smem;            // [64][DH + 4]
-    float* tab = (float*)smem + 64 * (DH + 4);
-    const int lane = threadIdx.x;
-    const int qt = blockIdx.x % nQ, bh = blockIdx.x / nQ;
-    const int head = bh % heads, b = bh / heads;
-    const int row = qt * 64 + lane;
-    const int rl = row < Lq ? row : Lq - 1;
-    const int tab_n = 2 * rel_len - 1;
-    if (rel_table) {
-        for (int i = lane; i < tab_n; i += 64) tab[i] = rel_table[(int64_t)head * tab_n + i];
-        __syncthreads();
-    }
-    const float* qp = q + (int64_t)b * q_bs + (int64_t)rl * q_rs + head * DH;
-#pragma unroll
-    for (int d = 0; d < DH; d += 4) *(f32x4*)&qs[lane][d] = *(const f32x4*)(qp + d);
-    const float* Kb = k + (int64_t)b * k_bs + head * DH;
-    const float* Vb = v + (int64_t)b * v_bs + head * DH;
-    float acc[DH];
-#pragma unroll
-    for (int d = 0; d < DH; ++d) acc[d] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int jend = causal ? min(Lkv, rl + 1) : Lkv;
-    for (int j = 0; j < jend; ++j) {
-        const float* kr = Kb + (int64_t)j * k_rs;
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < DH; d += 4) {
-            const f32x4 kv = *(const f32x4*)(kr + d);
-            const f32x4 qv = *(const f32x4*)&qs[lane][d];
-            s = fmaf(qv[0], kv[0], s); s = fmaf(qv[1], kv[1], s); s = fmaf(qv[2], kv[2], s); s = fmaf(qv[3], kv[3], s);
-        }
-        s *= scale;
-        if (rel_table) s += tab[j - rl + rel_len - 1];
-        const float mn = fmaxf(m, s);
-        const float alpha = expf(m - mn);
-        const float pj = expf(s - mn);
-        l = l * alpha + pj;
-        m = mn;
-        const float* vr = Vb + (int64_t)j * v_rs;
-#pragma unroll
-        for (int d = 0; d < DH; d += 4) {
-            const f32x4 vv = *(const f32x4*)(vr + d);
-            acc[d] = fmaf(pj, vv[0], acc[d] * alpha); acc[d + 1] = fmaf(pj, vv[1], acc[d + 1] * alpha);
-            acc[d + 2] = fmaf(pj, vv[2], acc[d + 2] * alpha); acc[d + 3] = fmaf(pj, vv[3], acc[d + 3] * alpha);
-        }
-    }
-    if (row < Lq) {
-        const float inv = 1.0f / l;
-        float* op = o + (int64_t)b * o_bs + (int64_t)row * o_rs + head * DH;
-#pragma unroll
-        for (int d = 0; d < DH; d += 4) *(f32x4*)(op + d) = (f32x4){acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv};
     }
 }
 
@@ -459,10 +398,8 @@ extern "C" int ug_flash_attn_fwd_bias(const void* q, int64_t q_row_stride, int64
     const int rc = attn_bias_check("ug_flash_attn_fwd_bias", q, k, v, o, batches, heads, Lq, Lkv, rel_table, rel_len);
     if (rc != UG_OK) return rc;
     UG_REQUIRE(dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_bias: head dim %d with a bias or a causal mask (64 only)", dh);
-    UG_REQUIRE(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 8 == 0 && k_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 8),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd_bias: strides must be multiples of 8 elements and bases 16-byte aligned");
+    const ug_view_rule views[] = {{"q", UG_VIEW(q), 8, 16, false}, {"k", UG_VIEW(k), 8, 16, false}, {"v", UG_VIEW(v), 8, 16, false}, {"o", UG_VIEW(o), 4, 8, false}};
+    if (const int vrc = ug_check_views(__func__, views)) return vrc;
     const int nQ = (int)((Lq + AQ - 1) / AQ);
     const int64_t nwg = (int64_t)nQ * heads * batches;
     UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_bias: grid too large");
@@ -491,19 +428,8 @@ extern "C" int ug_flash_attn_fwd_bias_f32(const void* q, int64_t q_row_stride, i
     const int rc = attn_bias_check("ug_flash_attn_fwd_bias_f32", q, k, v, o, batches, heads, Lq, Lkv, rel_table, rel_len);
     if (rc != UG_OK) return rc;
     UG_REQUIRE(dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_bias_f32: head dim %d with a bias or a causal mask (64 only)", dh);
-    UG_REQUIRE(q_row_stride % 4 == 0 && k_row_stride % 4 == 0 && v_row_stride % 4 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 4 == 0 && k_batch_stride % 4 == 0 && v_batch_stride % 4 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd_bias_f32: strides must be multiples of 4 elements and bases 16-byte aligned");
-    const int nQ = (int)((Lq + 63) / 64);
-    const int64_t nwg = (int64_t)nQ * heads * batches;
-    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_bias_f32: grid too large");
-    const size_t lds = 64 * (64 + 4) * sizeof(float) + (rel_table ? (size_t)(2 * rel_len - 1) * sizeof(float) : 0);
-    hipLaunchKernelGGL(attn_bias_f32_kernel<64>, dim3((unsigned)nwg), dim3(64), lds, (hipStream_t)stream, (const float*)q, q_row_stride, q_batch_stride,
-                       (const float*)k, k_row_stride, k_batch_stride, (const float*)v, v_row_stride, v_batch_stride, (float*)o, o_row_stride, o_batch_stride,
-                       rel_table, (int)rel_len, (int)causal, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale);
-    UG_CHECK_LAUNCH("ug_flash_attn_fwd_bias_f32");
-    return UG_OK;
+    return ug_flash_attn_f32_launch(__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), UG_VIEW(o), batches, heads, Lq, Lkv, dh, softmax_scale, rel_table, rel_len,
+                                    causal, stream);
 }
 
 extern "C" int ug_t5_rel_table(const void* weight, int32_t num_buckets, int32_t max_distance, int32_t heads, int64_t L, float* table, ug_stream_t stream) {

@@ -44,6 +44,22 @@ int ug_env_int(const char* name, int dflt);
 
 static inline bool ug_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// ---- strided attention views (host; unigen_hip.h "Strided attention views") -----------------------------------------------------------
+// An attention operand as the entry points take it: base pointer, row stride and batch stride in elements. A plain buffer (workspace, state)
+// is a view with both strides 0.
+struct ug_view { const void* p; int64_t rs, bs; };
+#define UG_VIEW(x) {x, x##_row_stride, x##_batch_stride}      // from an entry point's parameters x, x_row_stride, x_batch_stride
+// one line of an entry point's table: both strides multiples of `mult` elements, the base aligned to `align` bytes (powers of two, both), and,
+// where `bounded`, the row stride within (0, 2^24)
+struct ug_view_rule { const char* name; ug_view v; int mult, align; bool bounded; };
+// UG_ERR_BAD_ALIGN for the first view off its multiple or alignment; only when every view passed that, UG_ERR_UNSUPPORTED for the first bounded
+// row stride out of range; else UG_OK. The last error starts with `who`, the entry point's name, and names the view.
+int ug_check_views(const char* who, const ug_view_rule* rules, int n);
+template <int N> static inline int ug_check_views(const char* who, const ug_view_rule (&rules)[N]) { return ug_check_views(who, rules, N); }
+// verify_f32.hip: view rules, grid limit and launch of the one fp32 softmax-attention kernel, for ug_flash_attn_fwd_f32 and _fwd_bias_f32 (text.hip)
+int ug_flash_attn_f32_launch(const char* who, ug_view q, ug_view k, ug_view v, ug_view o, int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                             float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream);
+
 // ---- bf16 <-> f32 (device) -------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float(((unsigned)u) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {  // RNE, NaN-preserving (v_cvt_pk_bf16_f32)

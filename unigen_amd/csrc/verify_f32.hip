@@ -1,4 +1,4 @@
-// fp32 VERIFICATION kernels: ug_gemm_f32 and ug_flash_attn_fwd_f32.
+// fp32 VERIFICATION kernels: ug_gemm_f32 and ug_flash_attn_fwd_f32 (whose kernel also serves ug_flash_attn_fwd_bias_f32 of text.hip).
 //
 // The product path computes in bf16 (gemm.hip, attention.hip) with the reference's bf16 rounding points, so a forward of a deep
 // transformer can only agree with another bf16 evaluation to ~1e-2 (bf16 eps = 7.8e-3 per op). To show that the HOST ORCHESTRATION
@@ -98,19 +98,36 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const ug_gemm_desc p) {
     }
 }
 
-// O = softmax(Q K^T * scale) V in fp32: one thread per query row (64 rows of one (batch, head) per block), keys streamed with
-// wave-uniform addresses, exact online softmax (running max updated per key), fp32 accumulators in registers, q in LDS.
-template <int DH>
+// O = softmax(Q K^T * scale + bias) V in fp32, the reference of every softmax attention: one thread per query row (64 rows of one (batch, head)
+// per block), keys streamed with wave-uniform addresses, exact online softmax (running max updated per key), fp32 accumulators in registers, q in
+// LDS. BIAS (ug_flash_attn_fwd_bias_f32): rel_table (or NULL) adds tab[k - q + rel_len - 1] from the head's table slice, held in LDS behind q,
+// and causal ends a row's keys at its own index; without BIAS the three arguments are not read and q's LDS image is static.
+template <int DH, bool BIAS>
 __global__ __launch_bounds__(64) void flash_attn_f32_kernel(
     const float* __restrict__ q, int64_t q_rs, int64_t q_bs, const float* __restrict__ k, int64_t k_rs, int64_t k_bs,
     const float* __restrict__ v, int64_t v_rs, int64_t v_bs, float* __restrict__ o, int64_t o_rs, int64_t o_bs,
-    int heads, int Lq, int Lkv, int nQ, float scale) {
-    __shared__ __attribute__((aligned(16))) float qs[64][DH + 4];
+    int heads, int Lq, int Lkv, int nQ, float scale, const float* __restrict__ rel_table, int rel_len, int causal) {
+    float (*qs)[DH + 4];                                      // [64][DH + 4]
+    float* tab = nullptr;                                     // [2 rel_len - 1]
+    if constexpr (BIAS) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+        qs = (float (*)[DH + 4])smem;
+        tab = (float*)smem + 64 * (DH + 4);
+    } else {
+        __shared__ __attribute__((aligned(16))) float qs_static[64][DH + 4];
+        qs = qs_static;
+    }
     const int lane = threadIdx.x;
     const int qt = blockIdx.x % nQ, bh = blockIdx.x / nQ;
     const int head = bh % heads, b = bh / heads;
     const int row = qt * 64 + lane;
     const int rl = row < Lq ? row : Lq - 1;
+    const bool biased = BIAS && rel_table;
+    if (biased) {
+        const int tab_n = 2 * rel_len - 1;
+        for (int i = lane; i < tab_n; i += 64) tab[i] = rel_table[(int64_t)head * tab_n + i];
+        __syncthreads();
+    }
     const float* qp = q + (int64_t)b * q_bs + (int64_t)rl * q_rs + head * DH;
 #pragma unroll
     for (int d = 0; d < DH; d += 4) *(f32x4*)&qs[lane][d] = *(const f32x4*)(qp + d);
@@ -120,7 +137,8 @@ __global__ __launch_bounds__(64) void flash_attn_f32_kernel(
 #pragma unroll
     for (int d = 0; d < DH; ++d) acc[d] = 0.f;
     float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < Lkv; ++j) {
+    const int jend = BIAS && causal ? min(Lkv, rl + 1) : Lkv;
+    for (int j = 0; j < jend; ++j) {
         const float* kr = Kb + (int64_t)j * k_rs;
         float s = 0.f;
 #pragma unroll
@@ -130,6 +148,7 @@ __global__ __launch_bounds__(64) void flash_attn_f32_kernel(
             s = fmaf(qv[0], kv[0], s); s = fmaf(qv[1], kv[1], s); s = fmaf(qv[2], kv[2], s); s = fmaf(qv[3], kv[3], s);
         }
         s *= scale;
+        if (biased) s += tab[j - rl + rel_len - 1];
         const float mn = fmaxf(m, s);
         const float alpha = expf(m - mn);            // exp(-inf) = 0 on the first key
         const float pj = expf(s - mn);
@@ -174,6 +193,27 @@ extern "C" int ug_gemm_f32(const ug_gemm_desc* dp, ug_stream_t stream) {
     return UG_OK;
 }
 
+// The tail both fp32 softmax-attention entry points share, after their own shape and head-width checks: the view rules, the grid limit and the
+// launch. rel_table or causal select the BIAS instantiation (head width 64 only, which the caller has checked).
+int ug_flash_attn_f32_launch(const char* who, ug_view q, ug_view k, ug_view v, ug_view o, int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
+                             float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream) {
+    const ug_view_rule views[] = {{"q", q, 4, 16, false}, {"k", k, 4, 16, false}, {"v", v, 4, 16, false}, {"o", o, 4, 16, false}};
+    if (const int rc = ug_check_views(who, views)) return rc;
+    const int nQ = (int)((Lq + 63) / 64);
+    const int64_t nwg = (int64_t)nQ * heads * batches;
+    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: grid too large", who);
+    const auto launch = [&](auto kernel, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64), lds, (hipStream_t)stream, (const float*)q.p, q.rs, q.bs, (const float*)k.p, k.rs, k.bs,
+                           (const float*)v.p, v.rs, v.bs, (float*)o.p, o.rs, o.bs, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale, rel_table, (int)rel_len,
+                           (int)causal);
+    };
+    if (rel_table || causal) launch(flash_attn_f32_kernel<64, true>, 64 * (64 + 4) * sizeof(float) + (rel_table ? (size_t)(2 * rel_len - 1) * sizeof(float) : 0));
+    else if (dh == 128) launch(flash_attn_f32_kernel<128, false>, 0);
+    else launch(flash_attn_f32_kernel<64, false>, 0);
+    UG_CHECK_LAUNCH(who);
+    return UG_OK;
+}
+
 extern "C" int ug_flash_attn_fwd_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k,
                                      int64_t k_row_stride, int64_t k_batch_stride, const void* v, int64_t v_row_stride,
                                      int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride,
@@ -183,21 +223,5 @@ extern "C" int ug_flash_attn_fwd_f32(const void* q, int64_t q_row_stride, int64_
     UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_f32: bad arguments");
     UG_REQUIRE(dh == 128 || dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_f32: head dim %d not in {64, 128}", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_f32: sequence too long");
-    UG_REQUIRE(q_row_stride % 4 == 0 && k_row_stride % 4 == 0 && v_row_stride % 4 == 0 && o_row_stride % 4 == 0 &&
-               q_batch_stride % 4 == 0 && k_batch_stride % 4 == 0 && v_batch_stride % 4 == 0 && o_batch_stride % 4 == 0 &&
-               ug_aligned(q, 16) && ug_aligned(k, 16) && ug_aligned(v, 16) && ug_aligned(o, 16),
-               UG_ERR_BAD_ALIGN, "ug_flash_attn_fwd_f32: strides must be multiples of 4 elements and bases 16-byte aligned");
-    const int nQ = (int)((Lq + 63) / 64);
-    const int64_t nwg = (int64_t)nQ * heads * batches;
-    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_f32: grid too large");
-    if (dh == 128)
-        hipLaunchKernelGGL(flash_attn_f32_kernel<128>, dim3((unsigned)nwg), dim3(64), 0, (hipStream_t)stream, (const float*)q, q_row_stride, q_batch_stride,
-                           (const float*)k, k_row_stride, k_batch_stride, (const float*)v, v_row_stride, v_batch_stride, (float*)o, o_row_stride,
-                           o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale);
-    else
-        hipLaunchKernelGGL(flash_attn_f32_kernel<64>, dim3((unsigned)nwg), dim3(64), 0, (hipStream_t)stream, (const float*)q, q_row_stride, q_batch_stride,
-                           (const float*)k, k_row_stride, k_batch_stride, (const float*)v, v_row_stride, v_batch_stride, (float*)o, o_row_stride,
-                           o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale);
-    UG_CHECK_LAUNCH("ug_flash_attn_fwd_f32");
-    return UG_OK;
+    return ug_flash_attn_f32_launch(__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), UG_VIEW(o), batches, heads, Lq, Lkv, dh, softmax_scale, nullptr, 0, 0, stream);
 }
