@@ -149,6 +149,7 @@ int ug_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t batches, int64_t rows_per_
  *   ug_flash_attn_fwd_f32, _bias_f32, _wide_f32    all: 4 / 16                                         none
  *   ug_flash_attn_bwd                              all eight: 8;  q, k, v, o, dout: 16;  dq, dk, dv: 8 all eight
  *   ug_linear_attn, _bwd (fp32 twins)              all: 8 (4) / 16;  workspace and state: 16           none
+ *   ug_flash_attn_fwd_softcap (fp32 twin)          q, k, v: 8 (4) / 16;  o: 4 / 8 (4 / 16)              none
  * The bound is there because the bf16 kernels stream K / V (the backward: Q / dO too) with LDS-DMAs whose per-lane byte offsets over a 64-row tile
  * are 32-bit, 2 (63 rs + 120) < 2^32; the narrow entry points apply it to every row stride (the widest row of the package is 21 504). The fp32
  * twins and ug_flash_attn_fwd_bias with a table or a mask index in 64 bits. Before the views an entry point returns UG_OK when there is nothing to
@@ -897,6 +898,56 @@ int ug_glu_dwconv3x3_bwd(const void* x, int64_t ldx, const void* w9, const void*
                          float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 int ug_glu_dwconv3x3_bwd_f32(const void* x, int64_t ldx, const void* w9, const void* bias, const void* dout, int64_t lddo, void* dx, int64_t lddx, float* dw9,
                              float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
+
+/* ---- Gemma-2 text encoder (csrc/gemma.hip; unigen_amd/gemma.py: transformers' Gemma2Model, the prompt encoder of Sana). Its matrix work is
+ * ug_gemm_bf16, its gated activation ug_gated_gelu (gelu_pytorch_tanh is gelu_new). Every bf16 entry has an `_f32` twin declared beside it. ---- */
+/* Causal self-attention with grouped K/V heads, logit soft-capping, a sliding window and a key length per sample (transformers'
+ * eager_attention_forward under Gemma-2's causal / sliding masks and a right-padded attention_mask). Query head h occupies columns [h dh, (h + 1) dh)
+ * of a q / o row and reads K/V head h / (heads / kv_heads), at columns [that * dh, ..) of a k / v row; Lq = Lkv = L.
+ *   s_qk = softcap ? softcap * tanh(softmax_scale * q.k / softcap) : softmax_scale * q.k
+ *   key k gets probability 0 when k > q, or window && k <= q - window, or kv_len && k >= kv_len[b].
+ * kv_len: device int32 [batches] or NULL; kv_len[b] >= 1 is the caller's contract (values above L count as L). A row without a live key - a padded
+ * row further than `window` behind kv_len[b], nothing else - is written as zeros (the module's additive mask spreads such a row over all keys).
+ * Views as in "Strided attention views": q, k, v 8 / 16, o 4 / 8 (the twin: all 4 / 16), no row-stride bound. Order of refusals: nothing to do
+ * (batches or L zero: UG_OK), null operands, non-positive counts, heads % kv_heads != 0, a negative softcap or window (UG_ERR_BAD_SHAPE), then
+ * dh != 256 and L >= 2^30 (UG_ERR_UNSUPPORTED), then the views. bf16 in / out, fp32 accumulation, online softmax, P rounded to bf16 as the P.V operand; the
+ * bf16 entry evaluates tanh through exp2 and a reciprocal, the twin with tanhf. No workspace, no atomics, no state: two launches give the same
+ * bits and the launch can be captured in a graph (36.5 KiB of static LDS; one workgroup = 128 query rows of one head). */
+int ug_flash_attn_fwd_softcap(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                              const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                              const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                              void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                              int64_t batches, int32_t heads, int32_t kv_heads, int64_t L, int32_t dh,
+                              float softmax_scale, float softcap, int64_t window, const int32_t* kv_len, ug_stream_t stream);
+int ug_flash_attn_fwd_softcap_f32(const void* q, int64_t q_row_stride, int64_t q_batch_stride,
+                                  const void* k, int64_t k_row_stride, int64_t k_batch_stride,
+                                  const void* v, int64_t v_row_stride, int64_t v_batch_stride,
+                                  void* o, int64_t o_row_stride, int64_t o_batch_stride,
+                                  int64_t batches, int32_t heads, int32_t kv_heads, int64_t L, int32_t dh,
+                                  float softmax_scale, float softcap, int64_t window, const int32_t* kv_len, ug_stream_t stream);
+/* apply_rotary_pos_emb of modeling_gemma2.py (rotate_half), in place on `nheads` consecutive dh-wide heads from column col0 of buf [rows][ld]: the
+ * q and k heads of a packed q | k | v projection (nheads = heads + kv_heads; the v columns are not touched). Row r has position r % rows_per_batch.
+ * cos_tab, sin_tab: [>= rows_per_batch][dh / 2] in the storage dtype (the module casts cos / sin to the activations' dtype), for i < dh / 2:
+ *   y[i] = bf16(bf16(x[i] cos[i]) - bf16(x[i + dh/2] sin[i]))     y[i + dh/2] = bf16(bf16(x[i + dh/2] cos[i]) + bf16(x[i] sin[i]))
+ * (three rounding points, none in the twin). dh must be 256 (UG_ERR_UNSUPPORTED); ld, col0 multiples of 8 (4) elements, bases 16-byte aligned. */
+int ug_rope_half(void* buf, int64_t ld, int64_t rows, int64_t rows_per_batch, int64_t col0, int32_t nheads, int32_t dh, const void* cos_tab,
+                 const void* sin_tab, ug_stream_t stream);
+int ug_rope_half_f32(void* buf, int64_t ld, int64_t rows, int64_t rows_per_batch, int64_t col0, int32_t nheads, int32_t dh, const void* cos_tab,
+                     const void* sin_tab, ug_stream_t stream);
+/* Gemma2RMSNorm with an optional residual: y = bf16((x * rsqrt(mean(x^2) + eps)) * (1 + w)), statistics and both products in fp32, ONE rounding
+ * (ug_rmsnorm_rows is T5's: weight w, two roundings); out = residual ? bf16(residual + y) : y, the layer's `residual + hidden_states` (no rounding at
+ * all in the twin). residual: rows at ldr, or NULL (ldr ignored); out may be x or the residual itself. D a multiple of 8 (UG_ERR_UNSUPPORTED otherwise), rows
+ * 16-byte aligned; one pass over the row up to D = 4608. */
+int ug_gemma_rmsnorm_rows(const void* x, int64_t ldx, const void* w, const void* residual, int64_t ldr, void* out, int64_t ldo, int64_t rows, int64_t D,
+                          float eps, ug_stream_t stream);
+int ug_gemma_rmsnorm_rows_f32(const void* x, int64_t ldx, const void* w, const void* residual, int64_t ldr, void* out, int64_t ldo, int64_t rows, int64_t D,
+                              float eps, ug_stream_t stream);
+/* ug_gather_rows with a multiplier: out[i][:W] = bf16(src[idx[i]][:W] * scale) (zeros when idx[i] < 0). Gemma2TextScaledWordEmbedding: the caller passes
+ * hidden_size ** 0.5 already rounded to the storage dtype, as the module does. */
+int ug_gather_rows_scaled(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+                          ug_stream_t stream);
+int ug_gather_rows_scaled_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+                              ug_stream_t stream);
 
 int ug_version(void);
 const char* ug_last_error(void);

@@ -8,7 +8,8 @@ __version__ = "0.1.0"
 _LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training_sigmas": "objective", "sample_density": "objective",
          "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text", "CLIPTextModelWithProjection": "text",
          "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text",
-         "SanaTransformerBlock": "sana", "SanaTransformer2DModel": "sana"}
+         "SanaTransformerBlock": "sana", "SanaTransformer2DModel": "sana",
+         "Gemma2Model": "gemma", "encode_prompt_sana": "gemma"}
 __all__ = sorted(_LAZY)
 
 

@@ -1291,3 +1291,62 @@ def glu_dwconv3x3_bwd(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, dou
     if ev is not None:
         _timer.end("glu_dwconv_bwd", 2.0 * 9 * 2 * C * B * H * W * (3 if dw9 is not None else 2), ev, tag=(B, H, W, C))
     return dx, dw9, dbias
+
+
+# ---- Gemma-2 text encoder (csrc/gemma.hip) ---------------------------------------------------------------------------------------------
+def flash_attn_softcap(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batches: int, heads: int, kv_heads: int, dh: int, L_: int,
+                       q_strides, k_strides, v_strides, o_strides, scale: float, softcap: float = 0.0, window: int = 0,
+                       kv_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal attention with grouped K/V heads (query head h reads K/V head h // (heads // kv_heads)), logits capped as softcap * tanh(s / softcap)
+    (0: off), keys at or before q - window hidden (0: no window) and keys from kv_len[b] on hidden (kv_len int32 [batches] on the device, or None)."""
+    dt = _act(q, "q")
+    _chk(k, "k", dt); _chk(v, "v", dt); _chk(out, "out", dt)
+    if kv_len is not None:
+        _chk(kv_len, "kv_len", torch.int32)
+        if kv_len.shape != (batches,) or not kv_len.is_contiguous():
+            raise ValueError(f"kv_len: expected a contiguous int32 [batches = {batches}] tensor, got {tuple(kv_len.shape)}")
+    ev = _timer.begin("attn") if _timer is not None else None
+    _call("ug_flash_attn_fwd_softcap", dt, q.data_ptr(), q_strides[0], q_strides[1], k.data_ptr(), k_strides[0], k_strides[1], v.data_ptr(), v_strides[0],
+          v_strides[1], out.data_ptr(), o_strides[0], o_strides[1], batches, heads, kv_heads, L_, dh, scale, softcap, window, _p(kv_len), _stream())
+    if ev is not None:
+        _timer.end("attn", 2.0 * batches * heads * L_ * L_ * dh, ev, tag=(batches, heads, L_, L_, dh))
+    return out
+
+
+def rope_half(buf: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, rows_per_batch: int, col0: int, nheads: int, dh: int) -> torch.Tensor:
+    """Rotate-half RoPE in place on `nheads` consecutive dh-wide heads from column col0 of buf [rows, ld]; cos / sin [>= rows_per_batch, dh // 2] in
+    buf's dtype, row r at position r % rows_per_batch."""
+    dt = _act(buf, "buf")
+    _chk(cos, "cos", dt); _chk(sin, "sin", dt)
+    rows = buf.shape[0]
+    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[0] < rows_per_batch or cos.shape[1] != dh // 2 or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"cos / sin: expected contiguous [>= {rows_per_batch}, {dh // 2}] tables, got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    assert buf.dim() == 2 and buf.stride(1) == 1
+    _call("ug_rope_half", dt, buf.data_ptr(), buf.stride(0), rows, rows_per_batch, col0, nheads, dh, cos.data_ptr(), sin.data_ptr(), _stream())
+    return buf
+
+
+def gemma_rmsnorm_rows(x: torch.Tensor, w: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gemma2RMSNorm over the last dimension of x [rows, D] (weight 1 + w, one rounding); with `residual` the sum residual + norm(x)."""
+    dt = _act(x, "x")
+    _chk(w, "w", dt)
+    rows, D = x.shape
+    out = torch.empty(rows, D, dtype=dt, device=x.device) if out is None else out
+    _chk(out, "out", dt)
+    assert w.numel() == D and out.shape == x.shape
+    if residual is not None:
+        _chk(residual, "residual", dt)
+        assert residual.shape == x.shape
+    _call("ug_gemma_rmsnorm_rows", dt, x.data_ptr(), x.stride(0), w.data_ptr(), _p(residual), residual.stride(0) if residual is not None else 0,
+          out.data_ptr(), out.stride(0), rows, D, eps, _stream())
+    return out
+
+
+def gather_rows_scaled(src: torch.Tensor, idx: torch.Tensor, scale: float, out: torch.Tensor) -> torch.Tensor:
+    """out[i] = src[idx[i]] * scale (zeros where idx[i] < 0); src [R, W], idx int32 [n], out [n, W]."""
+    dt = _act(src, "src")
+    _chk(idx, "idx", torch.int32); _chk(out, "out", dt)
+    n, W = out.shape
+    assert idx.numel() == n and src.shape[1] == W and idx.is_contiguous()
+    _call("ug_gather_rows_scaled", dt, src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), n, W, scale, _stream())
+    return out
