@@ -899,8 +899,9 @@ int ug_glu_dwconv3x3_bwd(const void* x, int64_t ldx, const void* w9, const void*
 int ug_glu_dwconv3x3_bwd_f32(const void* x, int64_t ldx, const void* w9, const void* bias, const void* dout, int64_t lddo, void* dx, int64_t lddx, float* dw9,
                              float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, int64_t workspace_bytes, ug_stream_t stream);
 
-/* ---- Gemma-2 text encoder (csrc/gemma.hip; unigen_amd/gemma.py: transformers' Gemma2Model, the prompt encoder of Sana). Its matrix work is
- * ug_gemm_bf16, its gated activation ug_gated_gelu (gelu_pytorch_tanh is gelu_new). Every bf16 entry has an `_f32` twin declared beside it. ---- */
+/* ---- Gemma-2 text encoder (csrc/text.hip, whose attention and row-norm templates it shares with T5 and CLIP; the gather: csrc/elementwise.hip;
+ * unigen_amd/gemma.py: transformers' Gemma2Model, the prompt encoder of Sana). Its matrix work is ug_gemm_bf16, its gated activation
+ * ug_gated_gelu (gelu_pytorch_tanh is gelu_new). Every bf16 entry has an `_f32` twin declared beside it. ---- */
 /* Causal self-attention with grouped K/V heads, logit soft-capping, a sliding window and a key length per sample (transformers'
  * eager_attention_forward under Gemma-2's causal / sliding masks and a right-padded attention_mask). Query head h occupies columns [h dh, (h + 1) dh)
  * of a q / o row and reads K/V head h / (heads / kv_heads), at columns [that * dh, ..) of a k / v row; Lq = Lkv = L.

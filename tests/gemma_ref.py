@@ -1,4 +1,4 @@
-"""float64 references of the Gemma-2 kernels and model (unigen_amd/csrc/gemma.hip, unigen_amd/gemma.py), restated from the published semantics of
+"""float64 references of the Gemma-2 kernels and model (unigen_amd/csrc/text.hip, unigen_amd/gemma.py), restated from the published semantics of
 transformers' Gemma2Model (modeling_gemma2.py: Gemma2RMSNorm, Gemma2RotaryEmbedding, apply_rotary_pos_emb, eager_attention_forward under the
 causal / sliding-window masks and a right-padded attention_mask, Gemma2TextScaledWordEmbedding, Gemma2DecoderLayer).
 tests/test_gemma_ref_cpu.py pins them against the installed transformers and against tests/golden/gemma_tiny.safetensors.

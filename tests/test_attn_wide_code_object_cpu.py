@@ -1,4 +1,4 @@
-"""The head-width-512 flash attention forward (csrc/attn_wide.hip) without a GPU: the two kernels as compiled (through tests/code_object.py) and the
+"""The head-width-512 flash attention forward (csrc/attn_wide.hip) without a GPU: the bf16 kernel and its fp32 twin (verify_f32.hip's one kernel at 16 lanes per row) as compiled (through tests/code_object.py) and the
 refusals of their C entry points (fake aligned pointers: every refusal comes before any launch).
 
 The register ceilings are what the head commit compiles to with the flags of unigen_amd/build.py (hipcc 7.2.26015); compiler output is deterministic, so
@@ -12,7 +12,7 @@ from tests import code_object_contracts as CC
 # vgpr_count is the metadata's: it includes the AGPRs (unified file)
 CEILINGS = {
     "flash_attn_wide_kernel": dict(vgpr_count=512, agpr_count=256, sgpr_count=46, sgpr_spill_count=0, max_flat_workgroup_size=256),
-    "flash_attn_wide_f32_kernel": dict(vgpr_count=100, agpr_count=0, sgpr_count=39, sgpr_spill_count=0, max_flat_workgroup_size=256),
+    "flash_attn_f32_kernel<512, 16, false, false>": dict(vgpr_count=100, agpr_count=0, sgpr_count=39, sgpr_spill_count=0, max_flat_workgroup_size=256),
 }
 LAUNCH_THREADS = 256          # both launches: dim3(256)
 

@@ -1,30 +1,55 @@
-"""The Gemma-2 kernels (csrc/gemma.hip) without a GPU: the kernels as compiled (through tests/code_object.py) and the refusals of their C entry points
-(fake aligned pointers: every refusal comes before any launch).
+"""The text-encoder kernels (csrc/text.hip; the fp32 attention twin in csrc/verify_f32.hip, the gather in csrc/elementwise.hip) without a GPU: the
+kernels as compiled (through tests/code_object.py) and the refusals of the Gemma-2 C entry points (fake aligned pointers: every refusal comes before any
+launch).
 
-The register ceilings are what the head commit compiles to with the flags of unigen_amd/build.py (hipcc 7.2.26015); compiler output is deterministic, so
-there is no margin, as in tests/code_object_contracts.py. vgpr_count is the metadata's: it includes the AGPRs (the attention kernel runs one wave per
-SIMD - Q fragments 64 registers, the O^T accumulator 128, S^T 16 - and so may use more than 256 registers per lane; what no kernel may do is spill)."""
+The register ceilings are what the commit that introduced each row compiled to with the flags of unigen_amd/build.py (hipcc 7.2.26015); compiler output is
+deterministic, so there is no margin, as in tests/code_object_contracts.py. The Gemma-2 rows are those of the kernels' first versions (attn_softcap_kernel,
+attn_softcap_f32_kernel, gemma_norm_rows_kernel, gather_rows_scaled_kernel), the T5 / CLIP rows those of attn_bias_kernel and norm_rows_kernel<T, LN, REG>
+before the two families became one template each. vgpr_count is the metadata's: it includes the AGPRs (the dh-256 attention runs one wave per SIMD - Q
+fragments 64 registers, the O^T accumulator 128, S^T 16 - and so may use more than 256 registers per lane; what no kernel may do is spill). The attention
+tiles are dynamic LDS (the launch's third argument), so group_segment_fixed_size is 0."""
 import pytest
 
 from tests import code_object as CO
 from tests import code_object_contracts as CC
 
-_C = lambda v, a, s, lds: dict(vgpr_count=v, agpr_count=a, sgpr_count=s, sgpr_spill_count=0, group_segment_fixed_size=lds, max_flat_workgroup_size=256)
-ATTN_LDS = 2 * (32 * (256 + 8) + 256 * (32 + 8))          # the K image [32][264] and the transposed V image [256][40], bf16
+_C = lambda v, a, s, lds, wg=256, sspill=0: dict(vgpr_count=v, agpr_count=a, sgpr_count=s, sgpr_spill_count=sspill, group_segment_fixed_size=lds,
+                                                 max_flat_workgroup_size=wg)
 CEILINGS = {
-    "attn_softcap_kernel<false>": _C(413, 157, 48, ATTN_LDS),
-    "attn_softcap_kernel<true>": _C(425, 169, 49, ATTN_LDS),
-    "attn_softcap_f32_kernel": _C(162, 0, 46, 0),
+    # attn_plain_kernel<DH, KT, BIAS, CAUSAL, CAP, RAGGED>: Gemma-2 without and with the soft cap; T5 (table), CLIP (causal), both
+    "attn_plain_kernel<256, 32, false, true, false, true>": _C(413, 157, 48, 0),
+    "attn_plain_kernel<256, 32, false, true, true, true>": _C(425, 169, 49, 0),
+    "attn_plain_kernel<64, 64, true, false, false, false>": _C(148, 32, 44, 0),
+    "attn_plain_kernel<64, 64, false, true, false, false>": _C(148, 32, 40, 0),
+    "attn_plain_kernel<64, 64, true, true, false, false>": _C(156, 32, 42, 0),
+    # flash_attn_f32_kernel<DH, LPR, BIAS, RAGGED>: the Gemma-2 twin; the plain twins and the T5 / CLIP one (q in 17 / 33 KiB of static LDS, 64 threads);
+    # the dh-512 twin has its row in tests/test_attn_wide_code_object_cpu.py and one here, so that every instantiation of a template is in one table
+    "flash_attn_f32_kernel<256, 4, false, true>": _C(162, 0, 46, 0),
+    "flash_attn_f32_kernel<64, 1, false, false>": _C(140, 0, 97, 17408, 64),
+    "flash_attn_f32_kernel<128, 1, false, false>": _C(274, 18, 106, 33792, 64, 4),
+    "flash_attn_f32_kernel<64, 1, true, false>": _C(140, 0, 102, 17408, 64),
+    "flash_attn_f32_kernel<512, 16, false, false>": _C(100, 0, 39, 0),
     "rope_half_kernel<unsigned short>": _C(38, 0, 30, 0),
     "rope_half_kernel<float>": _C(46, 0, 30, 0),
-    "gemma_norm_rows_kernel<unsigned short, true>": _C(112, 0, 34, 0),
-    "gemma_norm_rows_kernel<unsigned short, false>": _C(39, 0, 26, 0),
-    "gemma_norm_rows_kernel<float, true>": _C(114, 0, 34, 0),
-    "gemma_norm_rows_kernel<float, false>": _C(34, 0, 26, 0),
-    "gather_rows_scaled_kernel<unsigned short>": _C(20, 0, 44, 0),
-    "gather_rows_scaled_kernel<float>": _C(26, 0, 46, 0),
+    "norm_rows_kernel<unsigned short, NormGemma, true>": _C(112, 0, 34, 0),
+    "norm_rows_kernel<unsigned short, NormGemma, false>": _C(39, 0, 26, 0),
+    "norm_rows_kernel<float, NormGemma, true>": _C(114, 0, 34, 0),
+    "norm_rows_kernel<float, NormGemma, false>": _C(34, 0, 26, 0),
+    "norm_rows_kernel<unsigned short, NormT5, true>": _C(102, 0, 34, 0),
+    "norm_rows_kernel<unsigned short, NormT5, false>": _C(27, 0, 24, 0),
+    "norm_rows_kernel<float, NormT5, true>": _C(106, 0, 34, 0),
+    "norm_rows_kernel<float, NormT5, false>": _C(28, 0, 24, 0),
+    "norm_rows_kernel<unsigned short, NormLN, true>": _C(112, 0, 36, 0),
+    "norm_rows_kernel<unsigned short, NormLN, false>": _C(38, 0, 28, 0),
+    "norm_rows_kernel<float, NormLN, true>": _C(112, 0, 36, 0),
+    "norm_rows_kernel<float, NormLN, false>": _C(44, 0, 28, 0),
+    "gather_rows_kernel<unsigned short, true>": _C(20, 0, 44, 0),
+    "gather_rows_kernel<float, true>": _C(26, 0, 46, 0),
+    "gather_rows_kernel<unsigned short, false>": _C(20, 0, 42, 0, 1024),          # ug_gather_rows: no launch bound, as ever
+    "gather_rows_kernel<float, false>": _C(24, 0, 42, 0, 1024),
 }
-LAUNCH_THREADS = 256          # every launch of csrc/gemma.hip is dim3(256)
+# every launch of these kernels is dim3(256), but the fp32 attention twin's one lane per row (dim3(64)) and ug_gather_rows, which declares no bound
+LAUNCH_THREADS = {n: c["max_flat_workgroup_size"] for n, c in CEILINGS.items()}
 
 
 @pytest.fixture(scope="module")
@@ -44,7 +69,7 @@ def test_gemma_kernels_meet_their_contract(product, name):
     assert CC.universal_violations(name, rec, {}) == [], rec          # wave64, static stack, no scratch, no VGPR spills, static LDS <= 64 KiB
     for f, c in CEILINGS[name].items():
         assert rec[f] <= c, (name, f, rec[f], c)
-    assert rec["max_flat_workgroup_size"] == LAUNCH_THREADS, rec
+    assert rec["max_flat_workgroup_size"] == LAUNCH_THREADS[name], rec
     assert name not in CC.EXCEPTIONS
 
 

@@ -1,4 +1,4 @@
-"""GPU tests of the Gemma-2 text encoder (unigen_amd/csrc/gemma.hip, unigen_amd/gemma.py) against the float64 references of tests/gemma_ref.py, which
+"""GPU tests of the Gemma-2 text encoder (unigen_amd/csrc/text.hip, unigen_amd/gemma.py) against the float64 references of tests/gemma_ref.py, which
 tests/test_gemma_ref_cpu.py pins against transformers. No test here imports transformers or reads anything outside the repository.
 
 Bounds (docs/PARITY_TOLERANCES.md, "Gemma-2 text encoder"):

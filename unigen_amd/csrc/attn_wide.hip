@@ -240,58 +240,6 @@ __global__ __launch_bounds__(256) void flash_attn_wide_kernel(
         }
 }
 
-// fp32 verification twin: plain FMA loops. 16 query rows per 256-thread workgroup, 16 threads per row: thread (row, part) owns columns
-// 64 i + 4 part .. + 3 (i = 0..7) of its row's q and accumulator in registers (no LDS: a [64][512 + 4] fp32 query image, the form of
-// flash_attn_f32_kernel, would be 132 KB). Per key the 16 partial dot products are summed with a butterfly (every thread of the row gets the same
-// bits), then the exact online softmax (running max updated per key) runs replicated in the 16 threads.
-__global__ __launch_bounds__(256) void flash_attn_wide_f32_kernel(
-    const float* __restrict__ q, int64_t q_rs, int64_t q_bs, const float* __restrict__ k, int64_t k_rs, int64_t k_bs,
-    const float* __restrict__ v, int64_t v_rs, int64_t v_bs, float* __restrict__ o, int64_t o_rs, int64_t o_bs,
-    int heads, int Lq, int Lkv, int nQ, float scale) {
-    const int part = threadIdx.x & 15, rloc = threadIdx.x >> 4;
-    const int qt = blockIdx.x % nQ, bh = blockIdx.x / nQ;
-    const int head = bh % heads, b = bh / heads;
-    const int row = qt * 16 + rloc;
-    const int rl = row < Lq ? row : Lq - 1;
-    const float* qp = q + (int64_t)b * q_bs + (int64_t)rl * q_rs + head * WDH + 4 * part;
-    f32x4 qr[8], acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { qr[i] = *(const f32x4*)(qp + 64 * i); acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    const float* Kb = k + (int64_t)b * k_bs + head * WDH + 4 * part;
-    const float* Vb = v + (int64_t)b * v_bs + head * WDH + 4 * part;
-    float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < Lkv; ++j) {
-        const float* kr = Kb + (int64_t)j * k_rs;
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const f32x4 kv = *(const f32x4*)(kr + 64 * i);
-            s = fmaf(qr[i][0], kv[0], s); s = fmaf(qr[i][1], kv[1], s); s = fmaf(qr[i][2], kv[2], s); s = fmaf(qr[i][3], kv[3], s);
-        }
-#pragma unroll
-        for (int msk = 1; msk < 16; msk <<= 1) s += __shfl_xor(s, msk, 64);
-        s *= scale;
-        const float mn = fmaxf(m, s);
-        const float alpha = expf(m - mn);            // exp(-inf) = 0 on the first key
-        const float pj = expf(s - mn);
-        l = l * alpha + pj;
-        m = mn;
-        const float* vr = Vb + (int64_t)j * v_rs;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const f32x4 vv = *(const f32x4*)(vr + 64 * i);
-            acc[i][0] = fmaf(pj, vv[0], acc[i][0] * alpha); acc[i][1] = fmaf(pj, vv[1], acc[i][1] * alpha);
-            acc[i][2] = fmaf(pj, vv[2], acc[i][2] * alpha); acc[i][3] = fmaf(pj, vv[3], acc[i][3] * alpha);
-        }
-    }
-    if (row < Lq) {
-        const float inv = 1.0f / l;
-        float* op = o + (int64_t)b * o_bs + (int64_t)row * o_rs + head * WDH + 4 * part;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *(f32x4*)(op + 64 * i) = (f32x4){acc[i][0] * inv, acc[i][1] * inv, acc[i][2] * inv, acc[i][3] * inv};
-    }
-}
-
 }  // namespace
 
 extern "C" int ug_flash_attn_fwd_wide(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k,
@@ -329,14 +277,6 @@ extern "C" int ug_flash_attn_fwd_wide_f32(const void* q, int64_t q_row_stride, i
     UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_wide_f32: bad arguments");
     UG_REQUIRE(dh == WDH, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: head dim %d is not 512 (64 and 128: ug_flash_attn_fwd_f32)", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: sequence too long");
-    const ug_view_rule views[] = {{"q", UG_VIEW(q), 4, 16, false}, {"k", UG_VIEW(k), 4, 16, false}, {"v", UG_VIEW(v), 4, 16, false}, {"o", UG_VIEW(o), 4, 16, false}};
-    if (const int rc = ug_check_views(__func__, views)) return rc;
-    const int nQ = (int)((Lq + 15) / 16);
-    const int64_t nwg = (int64_t)nQ * heads * batches;
-    UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_wide_f32: grid too large");
-    hipLaunchKernelGGL(flash_attn_wide_f32_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, (const float*)q, q_row_stride, q_batch_stride,
-                       (const float*)k, k_row_stride, k_batch_stride, (const float*)v, v_row_stride, v_batch_stride, (float*)o, o_row_stride,
-                       o_batch_stride, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale);
-    UG_CHECK_LAUNCH("ug_flash_attn_fwd_wide_f32");
-    return UG_OK;
+    // verify_f32.hip's one kernel, 16 lanes per query row (a [64][512 + 4] fp32 query image in LDS, its form at head width 64 and 128, would be 132 KB)
+    return ug_flash_attn_f32_launch(__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), UG_VIEW(o), batches, heads, Lq, Lkv, dh, softmax_scale, {}, stream);
 }

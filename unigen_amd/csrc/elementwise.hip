@@ -415,9 +415,10 @@ __global__ void add_rowbcast_f32_kernel(T* __restrict__ x, int64_t ldx, const fl
     }
 }
 
-template <typename T>
-__global__ void gather_rows_kernel(const T* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ idx, T* __restrict__ out,
-                                   int64_t ld_out, int64_t n, int chunks_per_row) {
+// out[i][:W] = src[idx[i]][:W] (zeros when idx[i] < 0); SCALED (ug_gather_rows_scaled, Gemma2TextScaledWordEmbedding): rnd(src[idx[i]][:W] * scale).
+template <typename T, bool SCALED>
+__global__ __launch_bounds__(SCALED ? 256 : 1024) void gather_rows_kernel(const T* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ idx,
+                                                                          T* __restrict__ out, int64_t ld_out, int64_t n, int chunks_per_row, float scale) {
     const int64_t total = n * chunks_per_row;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / chunks_per_row; const int c = (int)(i - r * chunks_per_row);
@@ -425,6 +426,10 @@ __global__ void gather_rows_kernel(const T* __restrict__ src, int64_t ld_src, co
         if (s >= 0) {
             float f[8];
             ElemT<T>::load8(src + (int64_t)s * ld_src + c * 8, f);       // exact: a bf16 -> f32 -> bf16 round trip is the identity
+            if constexpr (SCALED) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] *= scale;
+            }
             ElemT<T>::store8(out + r * ld_out + c * 8, f);
         } else {
             ElemT<T>::zero8(out + r * ld_out + c * 8);
@@ -485,16 +490,22 @@ int add_rowbcast_impl(void* x, int64_t ldx, const float* table, int64_t ldt, int
     return UG_OK;
 }
 
-template <typename T>
-int gather_rows_impl(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t stream) {
+// ug_gather_rows (both element types: leading dimensions in multiples of 8, idx and the leading dimensions' size taken on trust, as ever) and
+// ug_gather_rows_scaled (16-byte rows per element type, idx 4-byte aligned, leading dimensions at least W)
+template <typename T, bool SCALED>
+int gather_rows_impl(const char* who, const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+                     ug_stream_t stream) {
     if (n == 0 || W == 0) return UG_OK;
-    UG_REQUIRE(src && idx && out && n > 0 && W > 0, UG_ERR_BAD_SHAPE, "ug_gather_rows: bad arguments");
-    UG_REQUIRE(W % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0 && ug_aligned(src, 16) && ug_aligned(out, 16), UG_ERR_BAD_ALIGN,
-               "ug_gather_rows: 16-byte alignment required");
+    UG_REQUIRE(src && idx && out && n > 0 && W > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
+    UG_REQUIRE(!SCALED || (ld_src >= W && ld_out >= W), UG_ERR_BAD_SHAPE, "%s: leading dimensions below W", who);
+    constexpr int ldm = SCALED ? 16 / (int)sizeof(T) : 8;
+    UG_REQUIRE(W % 8 == 0 && ld_src % ldm == 0 && ld_out % ldm == 0 && ug_aligned(src, 16) && ug_aligned(out, 16) && (!SCALED || ug_aligned(idx, 4)),
+               UG_ERR_BAD_ALIGN, "%s: W must be a multiple of 8 and rows 16-byte aligned", who);
     const int64_t total = n * (W / 8);
     const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, ld_src, idx, (T*)out, ld_out, n, (int)(W / 8));
-    UG_CHECK_LAUNCH("ug_gather_rows");
+    hipLaunchKernelGGL((gather_rows_kernel<T, SCALED>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, ld_src, idx, (T*)out, ld_out, n,
+                       (int)(W / 8), scale);
+    UG_CHECK_LAUNCH(who);
     return UG_OK;
 }
 
@@ -620,10 +631,18 @@ extern "C" int ug_add_rowbcast_f32_f32(void* x, int64_t ldx, const float* table,
 }
 
 extern "C" int ug_gather_rows(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t s) {
-    return gather_rows_impl<bf16_t>(src, ld_src, idx, out, ld_out, n, W, s);
+    return gather_rows_impl<bf16_t, false>("ug_gather_rows", src, ld_src, idx, out, ld_out, n, W, 1.0f, s);
 }
 extern "C" int ug_gather_rows_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t s) {
-    return gather_rows_impl<float>(src, ld_src, idx, out, ld_out, n, W, s);
+    return gather_rows_impl<float, false>("ug_gather_rows", src, ld_src, idx, out, ld_out, n, W, 1.0f, s);       // the message names the family, as ever
+}
+extern "C" int ug_gather_rows_scaled(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+                                     ug_stream_t s) {
+    return gather_rows_impl<bf16_t, true>(__func__, src, ld_src, idx, out, ld_out, n, W, scale, s);
+}
+extern "C" int ug_gather_rows_scaled_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+                                         ug_stream_t s) {
+    return gather_rows_impl<float, true>(__func__, src, ld_src, idx, out, ld_out, n, W, scale, s);
 }
 
 extern "C" int ug_adaln_modulate(const void* x, int64_t ldx, int64_t x_rpb, int64_t x_bstride, const void* shift,

@@ -56,9 +56,16 @@ struct ug_view_rule { const char* name; ug_view v; int mult, align; bool bounded
 // row stride out of range; else UG_OK. The last error starts with `who`, the entry point's name, and names the view.
 int ug_check_views(const char* who, const ug_view_rule* rules, int n);
 template <int N> static inline int ug_check_views(const char* who, const ug_view_rule (&rules)[N]) { return ug_check_views(who, rules, N); }
-// verify_f32.hip: view rules, grid limit and launch of the one fp32 softmax-attention kernel, for ug_flash_attn_fwd_f32 and _fwd_bias_f32 (text.hip)
+// verify_f32.hip: view rules, grid limit and launch of the one fp32 softmax-attention kernel, for ug_flash_attn_fwd_f32 (dh 64, 128), _fwd_bias_f32
+// and _fwd_softcap_f32 (text.hip; 64 and 256) and _fwd_wide_f32 (attn_wide.hip; 512). What an entry adds to softmax(scale Q K^T) V, all zero = nothing:
+struct ug_attn_f32_mods {
+    const float* rel_table; int rel_len;      // dh 64: + rel_table[head][k - q + rel_len - 1]
+    int causal;                               // dh 64: keys above the diagonal are masked (dh 256: always)
+    float softcap; int window;                // dh 256: softcap * tanh(s / softcap); only the last `window` keys up to the diagonal
+    const int32_t* kv_len; int group;         // dh 256: keys per sample (or NULL); query heads per K/V head
+};
 int ug_flash_attn_f32_launch(const char* who, ug_view q, ug_view k, ug_view v, ug_view o, int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
-                             float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream);
+                             float softmax_scale, const ug_attn_f32_mods& mods, ug_stream_t stream);
 
 // ---- bf16 <-> f32 (device) -------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float(((unsigned)u) << 16); }

@@ -1,4 +1,4 @@
-// fp32 VERIFICATION kernels: ug_gemm_f32 and ug_flash_attn_fwd_f32 (whose kernel also serves ug_flash_attn_fwd_bias_f32 of text.hip).
+// fp32 VERIFICATION kernels: ug_gemm_f32 and ug_flash_attn_fwd_f32 (whose kernel also serves the _bias_f32 and _softcap_f32 twins of text.hip and attn_wide.hip's _wide_f32).
 //
 // The product path computes in bf16 (gemm.hip, attention.hip) with the reference's bf16 rounding points, so a forward of a deep
 // transformer can only agree with another bf16 evaluation to ~1e-2 (bf16 eps = 7.8e-3 per op). To show that the HOST ORCHESTRATION
@@ -98,57 +98,78 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const ug_gemm_desc p) {
     }
 }
 
-// O = softmax(Q K^T * scale + bias) V in fp32, the reference of every softmax attention: one thread per query row (64 rows of one (batch, head)
-// per block), keys streamed with wave-uniform addresses, exact online softmax (running max updated per key), fp32 accumulators in registers, q in
-// LDS. BIAS (ug_flash_attn_fwd_bias_f32): rel_table (or NULL) adds tab[k - q + rel_len - 1] from the head's table slice, held in LDS behind q,
-// and causal ends a row's keys at its own index; without BIAS the three arguments are not read and q's LDS image is static.
-template <int DH, bool BIAS>
-__global__ __launch_bounds__(64) void flash_attn_f32_kernel(
+// O = softmax(f(Q K^T * scale)) V in fp32, the reference of every softmax attention: LPR lanes per query row (64 rows of one (batch, head) per
+// block at LPR 1 and 4, 16 at LPR 16), keys streamed one at a time, exact online softmax (running max updated per key), fp32 accumulators in
+// registers. The 16-byte chunk c of a head row belongs to lane c % LPR of its query row: a lane holds DH / LPR columns of q and of the accumulator,
+// visits its chunks in ascending order, and the LPR partial dot products meet in the ascending butterfly xor 1, 2, 4, 8 (every lane of the row
+// gets the same bits, and runs the softmax replicated). At LPR 1 q lives in LDS (with the accumulator a 128-wide row would not fit the registers).
+// BIAS (ug_flash_attn_fwd_bias_f32): rel_table (or NULL) adds tab[k - q + rel_len - 1] from the head's table slice, held in dynamic LDS behind q,
+// and causal ends a row's keys at its own index. RAGGED (ug_flash_attn_fwd_softcap_f32): always causal; the soft cap with tanhf, the window's
+// first key, the sample's key length and the K/V head of a group of query heads; a row with no live key is zeros. Without the flag the
+// arguments are not read.
+template <int DH, int LPR, bool BIAS, bool RAGGED>
+__global__ __launch_bounds__(LPR == 1 ? 64 : 256) void flash_attn_f32_kernel(
     const float* __restrict__ q, int64_t q_rs, int64_t q_bs, const float* __restrict__ k, int64_t k_rs, int64_t k_bs,
     const float* __restrict__ v, int64_t v_rs, int64_t v_bs, float* __restrict__ o, int64_t o_rs, int64_t o_bs,
-    int heads, int Lq, int Lkv, int nQ, float scale, const float* __restrict__ rel_table, int rel_len, int causal) {
-    float (*qs)[DH + 4];                                      // [64][DH + 4]
-    float* tab = nullptr;                                     // [2 rel_len - 1]
-    if constexpr (BIAS) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-        qs = (float (*)[DH + 4])smem;
-        tab = (float*)smem + 64 * (DH + 4);
-    } else {
-        __shared__ __attribute__((aligned(16))) float qs_static[64][DH + 4];
-        qs = qs_static;
+    int heads, int Lq, int Lkv, int nQ, float scale, ug_attn_f32_mods mods) {
+    constexpr int ROWS = LPR == 1 ? 64 : 256 / LPR;           // query rows per block
+    constexpr int NCH = DH / 4 / LPR;                         // 16-byte chunks per lane; its chunk i is columns 4 (LPR i + part) .. + 3
+    float (*qs)[DH + 4] = nullptr;                            // [ROWS][DH + 4]
+    if constexpr (LPR == 1) {
+        __shared__ __attribute__((aligned(16))) float qs_lds[ROWS][DH + 4];
+        qs = qs_lds;
     }
-    const int lane = threadIdx.x;
+    const int part = threadIdx.x % LPR, rloc = threadIdx.x / LPR;
     const int qt = blockIdx.x % nQ, bh = blockIdx.x / nQ;
     const int head = bh % heads, b = bh / heads;
-    const int row = qt * 64 + lane;
-    const int rl = row < Lq ? row : Lq - 1;
-    const bool biased = BIAS && rel_table;
-    if (biased) {
-        const int tab_n = 2 * rel_len - 1;
-        for (int i = lane; i < tab_n; i += 64) tab[i] = rel_table[(int64_t)head * tab_n + i];
-        __syncthreads();
+    const int kvh = RAGGED ? head / mods.group : head;
+    const int row = qt * ROWS + rloc;
+    const int rl = row < Lq ? row : Lq - 1;                   // rows past the end repeat the last one (the lanes of a row stay together) and are not stored
+    float* tab = nullptr;                                     // [2 rel_len - 1]
+    const bool biased = BIAS && mods.rel_table;
+    if constexpr (BIAS) {
+        extern __shared__ __attribute__((aligned(16))) float tab_lds[];
+        tab = tab_lds;
+        if (biased) {
+            const int tab_n = 2 * mods.rel_len - 1;
+            for (int i = threadIdx.x; i < tab_n; i += ROWS * LPR) tab[i] = mods.rel_table[(int64_t)head * tab_n + i];
+            __syncthreads();
+        }
     }
-    const float* qp = q + (int64_t)b * q_bs + (int64_t)rl * q_rs + head * DH;
+    const float* qp = q + (int64_t)b * q_bs + (int64_t)rl * q_rs + head * DH + 4 * part;
+    f32x4 qr[LPR == 1 ? 1 : NCH], acc[NCH];
 #pragma unroll
-    for (int d = 0; d < DH; d += 4) *(f32x4*)&qs[lane][d] = *(const f32x4*)(qp + d);
-    const float* Kb = k + (int64_t)b * k_bs + head * DH;
-    const float* Vb = v + (int64_t)b * v_bs + head * DH;
-    float acc[DH];
-#pragma unroll
-    for (int d = 0; d < DH; ++d) acc[d] = 0.f;
+    for (int i = 0; i < NCH; ++i) {
+        const f32x4 t = *(const f32x4*)(qp + 4 * LPR * i);
+        if constexpr (LPR == 1) *(f32x4*)&qs[rloc][4 * i] = t;
+        else qr[i] = t;
+        acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    const float* Kb = k + (int64_t)b * k_bs + kvh * DH + 4 * part;
+    const float* Vb = v + (int64_t)b * v_bs + kvh * DH + 4 * part;
     float m = -INFINITY, l = 0.f;
-    const int jend = BIAS && causal ? min(Lkv, rl + 1) : Lkv;
-    for (int j = 0; j < jend; ++j) {
+    int jlo = 0, jhi = Lkv;                                   // the row's live keys
+    if constexpr (BIAS) { if (mods.causal) jhi = min(Lkv, rl + 1); }
+    if constexpr (RAGGED) {
+        jhi = min(rl + 1, mods.kv_len ? min(max(mods.kv_len[b], 0), Lkv) : Lkv);
+        if (mods.window) jlo = max(0, rl - mods.window + 1);
+    }
+    for (int j = jlo; j < jhi; ++j) {
         const float* kr = Kb + (int64_t)j * k_rs;
         float s = 0.f;
 #pragma unroll
-        for (int d = 0; d < DH; d += 4) {
-            const f32x4 kv = *(const f32x4*)(kr + d);
-            const f32x4 qv = *(const f32x4*)&qs[lane][d];
+        for (int i = 0; i < NCH; ++i) {
+            const f32x4 kv = *(const f32x4*)(kr + 4 * LPR * i);
+            f32x4 qv;
+            if constexpr (LPR == 1) qv = *(const f32x4*)&qs[rloc][4 * i];
+            else qv = qr[i];
             s = fmaf(qv[0], kv[0], s); s = fmaf(qv[1], kv[1], s); s = fmaf(qv[2], kv[2], s); s = fmaf(qv[3], kv[3], s);
         }
+#pragma unroll
+        for (int msk = 1; msk < LPR; msk <<= 1) s += __shfl_xor(s, msk, 64);
         s *= scale;
-        if (biased) s += tab[j - rl + rel_len - 1];
+        if constexpr (RAGGED) { if (mods.softcap > 0.f) s = mods.softcap * tanhf(s / mods.softcap); }
+        if (biased) s += tab[j - rl + mods.rel_len - 1];
         const float mn = fmaxf(m, s);
         const float alpha = expf(m - mn);            // exp(-inf) = 0 on the first key
         const float pj = expf(s - mn);
@@ -156,17 +177,17 @@ __global__ __launch_bounds__(64) void flash_attn_f32_kernel(
         m = mn;
         const float* vr = Vb + (int64_t)j * v_rs;
 #pragma unroll
-        for (int d = 0; d < DH; d += 4) {
-            const f32x4 vv = *(const f32x4*)(vr + d);
-            acc[d] = fmaf(pj, vv[0], acc[d] * alpha); acc[d + 1] = fmaf(pj, vv[1], acc[d + 1] * alpha);
-            acc[d + 2] = fmaf(pj, vv[2], acc[d + 2] * alpha); acc[d + 3] = fmaf(pj, vv[3], acc[d + 3] * alpha);
+        for (int i = 0; i < NCH; ++i) {
+            const f32x4 vv = *(const f32x4*)(vr + 4 * LPR * i);
+            acc[i][0] = fmaf(pj, vv[0], acc[i][0] * alpha); acc[i][1] = fmaf(pj, vv[1], acc[i][1] * alpha);
+            acc[i][2] = fmaf(pj, vv[2], acc[i][2] * alpha); acc[i][3] = fmaf(pj, vv[3], acc[i][3] * alpha);
         }
     }
     if (row < Lq) {
-        const float inv = 1.0f / l;
-        float* op = o + (int64_t)b * o_bs + (int64_t)row * o_rs + head * DH;
+        const float inv = l > 0.f ? 1.0f / l : 0.f;  // no live key (RAGGED only): zeros
+        float* op = o + (int64_t)b * o_bs + (int64_t)row * o_rs + head * DH + 4 * part;
 #pragma unroll
-        for (int d = 0; d < DH; d += 4) *(f32x4*)(op + d) = (f32x4){acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv};
+        for (int i = 0; i < NCH; ++i) *(f32x4*)(op + 4 * LPR * i) = (f32x4){acc[i][0] * inv, acc[i][1] * inv, acc[i][2] * inv, acc[i][3] * inv};
     }
 }
 
@@ -193,23 +214,25 @@ extern "C" int ug_gemm_f32(const ug_gemm_desc* dp, ug_stream_t stream) {
     return UG_OK;
 }
 
-// The tail both fp32 softmax-attention entry points share, after their own shape and head-width checks: the view rules, the grid limit and the
-// launch. rel_table or causal select the BIAS instantiation (head width 64 only, which the caller has checked).
+// The tail every fp32 softmax-attention entry point shares, after its own shape and head-width checks: the view rules, the grid limit and the
+// launch. The head width selects the lanes per row; at 64, rel_table or causal select the BIAS instantiation; 256 is the RAGGED one.
 int ug_flash_attn_f32_launch(const char* who, ug_view q, ug_view k, ug_view v, ug_view o, int64_t batches, int32_t heads, int64_t Lq, int64_t Lkv, int32_t dh,
-                             float softmax_scale, const float* rel_table, int64_t rel_len, int32_t causal, ug_stream_t stream) {
+                             float softmax_scale, const ug_attn_f32_mods& mods, ug_stream_t stream) {
     const ug_view_rule views[] = {{"q", q, 4, 16, false}, {"k", k, 4, 16, false}, {"v", v, 4, 16, false}, {"o", o, 4, 16, false}};
     if (const int rc = ug_check_views(who, views)) return rc;
-    const int nQ = (int)((Lq + 63) / 64);
+    const int lpr = dh == 512 ? 16 : dh == 256 ? 4 : 1, rows = lpr == 1 ? 64 : 256 / lpr;
+    const int nQ = (int)((Lq + rows - 1) / rows);
     const int64_t nwg = (int64_t)nQ * heads * batches;
     UG_REQUIRE(nwg < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: grid too large", who);
     const auto launch = [&](auto kernel, size_t lds) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64), lds, (hipStream_t)stream, (const float*)q.p, q.rs, q.bs, (const float*)k.p, k.rs, k.bs,
-                           (const float*)v.p, v.rs, v.bs, (float*)o.p, o.rs, o.bs, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale, rel_table, (int)rel_len,
-                           (int)causal);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(rows * lpr), lds, (hipStream_t)stream, (const float*)q.p, q.rs, q.bs, (const float*)k.p, k.rs, k.bs,
+                           (const float*)v.p, v.rs, v.bs, (float*)o.p, o.rs, o.bs, (int)heads, (int)Lq, (int)Lkv, nQ, softmax_scale, mods);
     };
-    if (rel_table || causal) launch(flash_attn_f32_kernel<64, true>, 64 * (64 + 4) * sizeof(float) + (rel_table ? (size_t)(2 * rel_len - 1) * sizeof(float) : 0));
-    else if (dh == 128) launch(flash_attn_f32_kernel<128, false>, 0);
-    else launch(flash_attn_f32_kernel<64, false>, 0);
+    if (dh == 512) launch(flash_attn_f32_kernel<512, 16, false, false>, 0);
+    else if (dh == 256) launch(flash_attn_f32_kernel<256, 4, false, true>, 0);
+    else if (mods.rel_table || mods.causal) launch(flash_attn_f32_kernel<64, 1, true, false>, mods.rel_table ? (size_t)(2 * mods.rel_len - 1) * sizeof(float) : 0);
+    else if (dh == 128) launch(flash_attn_f32_kernel<128, 1, false, false>, 0);
+    else launch(flash_attn_f32_kernel<64, 1, false, false>, 0);
     UG_CHECK_LAUNCH(who);
     return UG_OK;
 }
@@ -223,5 +246,5 @@ extern "C" int ug_flash_attn_fwd_f32(const void* q, int64_t q_row_stride, int64_
     UG_REQUIRE(q && k && v && o && batches > 0 && heads > 0 && Lq > 0 && Lkv > 0, UG_ERR_BAD_SHAPE, "ug_flash_attn_fwd_f32: bad arguments");
     UG_REQUIRE(dh == 128 || dh == 64, UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_f32: head dim %d not in {64, 128}", dh);
     UG_REQUIRE(Lq < (1 << 30) && Lkv < (1 << 30), UG_ERR_UNSUPPORTED, "ug_flash_attn_fwd_f32: sequence too long");
-    return ug_flash_attn_f32_launch(__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), UG_VIEW(o), batches, heads, Lq, Lkv, dh, softmax_scale, nullptr, 0, 0, stream);
+    return ug_flash_attn_f32_launch(__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), UG_VIEW(o), batches, heads, Lq, Lkv, dh, softmax_scale, {}, stream);
 }

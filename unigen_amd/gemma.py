@@ -4,7 +4,7 @@ heads over 4 key/value heads of width 256, feed-forward 9216) on token ids, and 
 Per layer the launches are: norm, q | k | v GEMM (one packed weight), rotate-half RoPE in place on the q and k heads, causal attention with
 grouped K/V heads, the logit soft cap, the sliding window of that layer and the key length of each sample (ug_flash_attn_fwd_softcap), o_proj
 GEMM, norm + residual, norm, gate | up GEMM (stacked), gated GELU (ug_gated_gelu: gelu_pytorch_tanh is gelu_new), down GEMM, norm + residual
-(csrc/gemma.hip, csrc/text.hip, csrc/gemm.hip). Parameters in fp32 run the same orchestration through the `_f32` verification twins.
+(csrc/text.hip, csrc/gemm.hip). Parameters in fp32 run the same orchestration through the `_f32` verification twins.
 
 The attention mask must be a prefix mask (right padding): it becomes one key length per sample, computed on the device. There is no tokenizer
 here: callers pass token ids or attach a tokenizer callable of their own. There is no backward: Sana freezes its text encoder.

@@ -1293,7 +1293,7 @@ def glu_dwconv3x3_bwd(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, dou
     return dx, dw9, dbias
 
 
-# ---- Gemma-2 text encoder (csrc/gemma.hip) ---------------------------------------------------------------------------------------------
+# ---- Gemma-2 text encoder (csrc/text.hip) ----------------------------------------------------------------------------------------------
 def flash_attn_softcap(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batches: int, heads: int, kv_heads: int, dh: int, L_: int,
                        q_strides, k_strides, v_strides, o_strides, scale: float, softcap: float = 0.0, window: int = 0,
                        kv_len: Optional[torch.Tensor] = None) -> torch.Tensor:
