@@ -8,8 +8,10 @@ products and its sum, the norm's single output, the residual sums, the gated GEL
 output, the cos / sin table and the embedding multiplier) - the "rounding-point variant" / "bf16-rounded run" that the GPU tests measure the
 kernels' error against.
 
-A query row without a single live key (only with a window, on padded rows more than `window` behind kv_len) is ZERO here and in the kernel; the
-module's additive mask spreads such a row evenly over all keys. The fixture and the pinned comparisons have no such row."""
+A query row without a single live key (every row of a sample whose kv_len is 0; with a window the padded rows from kv_len + window - 1 on) is ZERO
+here and in the kernel; the module's additive mask spreads such a row evenly over all keys, and in float64 (its softmax casts the mask to fp32, where
+it is -inf) turns it into NaN. tests/golden/gemma_tiny.safetensors has no such row; tests/golden/gemma_tiny_window.safetensors (TINY_WINDOW) has 24,
+which are compared apart (window_dead_rows)."""
 import zlib
 
 import torch
@@ -41,19 +43,66 @@ def live_keys(L: int, window: int = 0, kv_len=None, B: int = 1, qrows=None) -> t
     return live
 
 
-def attention(q, k, v, scale: float, softcap: float = 0.0, window: int = 0, kv_len=None, rnd=None, dtype=F64, qrows=None):
+MUTANTS = ("window+1", "window-1", "kvlen+1", "group_mod", "no_rescale", "tile_skip_early", "cap_as_clamp")
+MUTANT_TILE = 32            # the key tile of the kernel the mutants imitate (attn_plain_kernel at head width 256)
+
+
+def _mutant_live(mutant, L: int, window: int, kv_len, B: int) -> torch.Tensor:
+    """live_keys as a kernel with one off-by-one mistake would see them (all L query rows)"""
+    qpos, kpos = torch.arange(L)[:, None], torch.arange(L)[None, :]
+    live = kpos <= qpos
+    if window:
+        w = window + 1 if mutant == "window+1" else window - 1 if mutant == "window-1" else window
+        live = live & (kpos > qpos - w)                                 # window - 1 = 0 hides every key: unlike live_keys, where 0 means no window
+        if mutant == "tile_skip_early":                                 # the tile whose LAST key is the window's first is taken for one behind the window
+            first = qpos - window + 1
+            live = live & ~((first >= 0) & (first % MUTANT_TILE == MUTANT_TILE - 1) & (kpos // MUTANT_TILE == first // MUTANT_TILE))
+    live = live[None].expand(B, L, L)
+    if kv_len is not None:
+        n = torch.as_tensor(kv_len).view(B, 1, 1)
+        live = live & (kpos[None] < (torch.clamp(n + 1, max=L) if mutant == "kvlen+1" else n))
+    return live
+
+
+def _no_rescale(s, v):
+    """online softmax over tiles of MUTANT_TILE keys in which the accumulator and the sum are NOT scaled when the running maximum moves.
+    s [B, H, L, L] with -inf at hidden keys, v [B, L, H, dh] -> (numerator [B, L, H, dh], sum [B, L, H, 1])"""
+    B, H, L, _ = s.shape
+    m = torch.full((B, H, L, 1), float("-inf"), dtype=s.dtype)
+    den, acc = torch.zeros(B, H, L, 1, dtype=s.dtype), torch.zeros(B, L, H, v.shape[-1], dtype=s.dtype)
+    for k0 in range(0, L, MUTANT_TILE):
+        st = s[..., k0:k0 + MUTANT_TILE]
+        m = torch.maximum(m, st.amax(-1, keepdim=True))
+        p = torch.exp(st - torch.where(torch.isinf(m), torch.zeros_like(m), m))
+        den = den + p.sum(-1, keepdim=True)
+        acc = acc + torch.einsum("bhqk,bkhd->bqhd", p, v[:, k0:k0 + MUTANT_TILE])
+    return acc, den.permute(0, 2, 1, 3)
+
+
+def attention(q, k, v, scale: float, softcap: float = 0.0, window: int = 0, kv_len=None, rnd=None, dtype=F64, qrows=None, mutant=None):
     """q [B, L, H, dh], k / v [B, L, KV, dh] -> [B, L, H, dh]: query head h reads K/V head h // (H // KV). rnd: the probabilities exp(s - max) are
     rounded as the P.V operand (the row sum is of the unrounded ones) and the output is rounded. dtype: float64, or float32 for the host evaluation
-    of the same formula that bounds the fp32 twin's tanh. qrows: q holds only these rows [B, n, H, dh] of the sequence."""
+    of the same formula that bounds the fp32 twin's tanh. qrows: q holds only these rows [B, n, H, dh] of the sequence.
+    mutant (one of MUTANTS; exact float64 on all rows only): the same attention with one mistake a kernel could make, for
+    tests/test_gemma_attn_cases_cpu.py to show that the case grid of tests/gemma_attn_cases.py would see it."""
     q, k, v = q.to(dtype), k.to(dtype), v.to(dtype)
     B, L, H = q.shape[0], k.shape[1], q.shape[2]
     g = H // k.shape[2]
-    k, v = k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)
+    if mutant is not None:
+        assert mutant in MUTANTS and dtype == F64 and rnd is None and qrows is None, mutant
+    if mutant == "group_mod":
+        idx = torch.arange(H) % k.shape[2]
+        k, v = k[:, :, idx], v[:, :, idx]
+    else:
+        k, v = k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)
     s = torch.einsum("bqhd,bkhd->bhqk", q, k) * scale
     if softcap:
-        s = torch.tanh(s / softcap) * softcap
-    live = live_keys(L, window, kv_len, B, qrows)[:, None]
+        s = s.clamp(-softcap, softcap) if mutant == "cap_as_clamp" else torch.tanh(s / softcap) * softcap
+    live = (live_keys(L, window, kv_len, B, qrows) if mutant is None else _mutant_live(mutant, L, window, kv_len, B))[:, None]
     s = s.masked_fill(~live, float("-inf"))
+    if mutant == "no_rescale":
+        num, den = _no_rescale(s, v)
+        return num / torch.where(den > 0, den, torch.ones_like(den))
     mx = s.amax(-1, keepdim=True)
     p = torch.exp(s - torch.where(torch.isinf(mx), torch.zeros_like(mx), mx))
     den = p.sum(-1).permute(0, 2, 1)[..., None]
@@ -195,6 +244,28 @@ def tiny_inputs():
 
 
 TINY = {"a": (TINY_A, STD_A, 1), "b": (TINY_B, STD_B, 2)}
+
+# A sliding layer whose window is more than a 32-key tile and shorter than the prompt (tests/golden/gemma_tiny_window.safetensors): 100 tokens, the
+# second sample with 37 live ones, the weights at config B's standard deviations so that the window shows in the output.
+TINY_C = dict(_TINY, attn_logit_softcapping=50.0, sliding_window=40, max_position_embeddings=128)
+TINY_WINDOW = (TINY_C, STD_B, 4)
+WINDOW_B, WINDOW_L, WINDOW_LIVE = 2, 100, 37
+
+
+def window_inputs():
+    """ids int64 [2, 100] and the prefix mask [2, 100] whose second row has 37 ones"""
+    ids = (_hash_normal(WINDOW_B * WINDOW_L, 54321) + 126).view(WINDOW_B, WINDOW_L) % 128
+    mask = torch.ones(WINDOW_B, WINDOW_L, dtype=torch.int64)
+    mask[1, WINDOW_LIVE:] = 0
+    return ids, mask
+
+
+def window_dead_rows(cfg, mask):
+    """bool [B, L]: the rows that have no live key in a sliding layer (padded rows `sliding_window` or more behind the last live key). gemma_ref and
+    the kernel define their attention output as zero, the module's additive mask spreads them evenly over all keys: the stated departure of the
+    header, so these rows are compared apart."""
+    L = mask.shape[1]
+    return ~live_keys(L, cfg["sliding_window"], mask.sum(1), mask.shape[0]).any(-1)
 
 
 def rel_l2(a, b):

@@ -4,6 +4,14 @@ integer function of their names (gemma_ref.tiny_state), and the fixture records 
 Needs transformers; no download (HF_HUB_OFFLINE=1).
 
     python tests/golden/make_gemma_golden.py
+
+With the argument `window` it writes tests/golden/gemma_tiny_window.safetensors instead and leaves the first file alone: the same for
+gemma_ref.TINY_WINDOW (sliding window 40) on 100 tokens, the second sample with 37 live ones. There the padded rows 76 .. 99 of the second sample have
+no live key in a sliding layer. The module in float64 turns them into NaN (its additive mask is -inf once the softmax casts it to fp32), and through
+0 x NaN in P.V every row of that sample with them; rows 0 .. 75 depend on none of them (the mask is causal), so their truth is the module's output on
+the first 76 tokens of that sample alone, and the fixture keeps NaN in rows 76 .. 99, where gemma_ref and the kernels define zero attention instead.
+
+    python tests/golden/make_gemma_golden.py window
 """
 import os
 import sys
@@ -35,5 +43,35 @@ def main():
     print(path, os.path.getsize(path), "bytes")
 
 
+def window_outputs(cfg, sd, ids, mask):
+    """-> (masked [2, L, hidden], unmasked) float64: the module's outputs on the window fixture's inputs, the second sample's masked rows as the header says"""
+    dead = R.window_dead_rows(cfg, mask)
+    assert not bool(dead[0].any()) and bool(dead[1].any())
+    n = int((~dead[1]).sum())                                           # the rows before the first one without a live key
+    assert not bool(dead[1, :n].any()) and bool(dead[1, n:].all())
+    with torch.no_grad():
+        m = R.hf_model(cfg, sd)
+        full, nomask = m(input_ids=ids, attention_mask=mask)[0], m(input_ids=ids)[0]
+        head = m(input_ids=ids[1:, :n], attention_mask=mask[1:, :n])[0]
+    assert bool(torch.isfinite(full[0]).all()) and bool(torch.isfinite(head).all()) and bool(torch.isfinite(nomask).all())
+    assert bool(torch.isnan(full[1, n:]).all()), "the module gives the rows without a live key a value now: compare them too"
+    out = full.clone()
+    out[1, :n] = head[0]
+    return out, nomask
+
+
+def main_window():
+    from safetensors.torch import save_file
+    cfg, std, seed = R.TINY_WINDOW
+    ids, mask = R.window_inputs()
+    sd = R.tiny_state(cfg, std, seed)
+    masked, nomask = window_outputs(cfg, sd, ids, mask)
+    out = {"ids": ids.to(torch.int32), "mask": mask.to(torch.int32), "c.out.mask": masked.float(), "c.out.nomask": nomask.float(),
+           "c.weight_sum": torch.stack([v.double().sum() for _, v in sorted(sd.items())]).sum().view(1)}
+    path = os.path.join(HERE, "gemma_tiny_window.safetensors")
+    save_file({k: v.contiguous() for k, v in out.items()}, path)
+    print(path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    main_window() if sys.argv[1:] == ["window"] else main()

@@ -255,6 +255,39 @@ def test_tiny_gemma_matches_transformers(gpu, tag):
     assert e32 <= 1e-5 and e32_0 <= 1e-5 and e16 <= 1.5 * e_var
 
 
+def test_tiny_gemma_window_matches_transformers(gpu):
+    """gemma_ref.TINY_WINDOW: sliding layers with a window of 40 on 100 tokens (more than a 32-key tile, less than the prompt), the second sample with 37
+    live tokens, under the model bounds above. The truth is the fixture's transformers output; on the 24 padded rows of the second sample that have
+    no live key in a sliding layer the module (float64) has NaN, and the truth there is gemma_ref's float64 run with its defined zero attention
+    (tests/test_gemma_ref_cpu.py pins that run against the module on every other row). All rows count."""
+    from safetensors.torch import load_file
+    from unigen_amd.gemma import Gemma2Model
+    g = load_file(os.path.join(os.path.dirname(GOLDEN), "gemma_tiny_window.safetensors"))
+    cfg, std, seed = R.TINY_WINDOW
+    sd = R.tiny_state(cfg, std, seed)
+    ids, mask = g["ids"], g["mask"]
+    ref = R.model(sd, cfg, ids.long(), mask.long())
+    dead = R.window_dead_rows(cfg, mask.long())
+    truth, truth0 = g["c.out.mask"].double(), g["c.out.nomask"].double()
+    assert torch.equal(torch.isnan(truth).any(-1), dead) and int(dead.sum()) == 24
+    truth = torch.where(dead[..., None], ref, truth)
+    e_var = rel_l2(R.model(sd, cfg, ids.long(), mask.long(), R.bf), truth)
+
+    def build(dt):
+        m = Gemma2Model.from_config(cfg, device=gpu, dtype=dt)
+        m.load_state_dict(sd)
+        return m
+    m32 = build(F32)
+    o32 = m32(ids, attention_mask=mask)[0].cpu()
+    e32, e32_0, e32_dead = rel_l2(o32, truth), rel_l2(m32(ids)[0].cpu(), truth0), rel_l2(o32[dead], truth[dead])
+    out = build(BF)(ids.to(gpu), attention_mask=mask.to(gpu))
+    assert out.last_hidden_state.dtype == BF and tuple(out[0].shape) == (2, R.WINDOW_L, 128) and torch.isfinite(out[0]).all()
+    e16 = rel_l2(out[0].cpu(), truth)
+    print(f"GEMMA tiny window: fp32 path {e32:.3e} with the mask ({e32_dead:.3e} on the rows without a live key), {e32_0:.3e} without (bound 1e-5); "
+          f"bf16 path {e16:.3e}, bf16-rounded reference {e_var:.3e}, ratio {e16 / e_var:.3f} (bound 1.5)")
+    assert e32 <= 1e-5 and e32_0 <= 1e-5 and e32_dead <= 1e-5 and e16 <= 1.5 * e_var
+
+
 def test_gemma_layer_at_2b_geometry(gpu):
     """One gemma-2-2b layer (hidden 2304, 8 query heads over 4 K/V heads of 256, feed-forward 9216) on B = 2, L = 300, the second sample with 211 live
     tokens: the packed GEMMs, the RoPE launch and the grouped attention at their real shapes, checked on 26 rows of each sample (first, last, tile

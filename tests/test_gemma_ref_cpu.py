@@ -89,6 +89,60 @@ def test_the_fixture_sees_the_cap_the_window_and_the_mask(golden):
         assert float(d[0].max()) == 0 and float(d[1, :R.TINY_LIVE].max()) == 0 and float(d[1, R.TINY_LIVE:].max()) > 0.5
 
 
+GOLDEN_WINDOW = os.path.join(os.path.dirname(GOLDEN), "gemma_tiny_window.safetensors")
+
+
+def _window_case_errors(masked_want, nomask_want, storage: float):
+    """gemma_ref against the module's outputs for TINY_WINDOW (sliding window 40, 100 tokens, the second sample with 37 live ones): every row with a
+    live key in the sliding layers under the rule of the other fixture; the 24 rows without one are where the module (float64, eager) has NaN and
+    the reference its defined zero attention - finite, and not compared against NaN."""
+    cfg, std, seed = R.TINY_WINDOW
+    sd = R.tiny_state(cfg, std, seed)
+    ids, mask = R.window_inputs()
+    dead = R.window_dead_rows(cfg, mask)
+    assert dead.sum(1).tolist() == [0, R.WINDOW_L - R.WINDOW_LIVE - cfg["sliding_window"] + 1]
+    assert torch.equal(torch.isnan(masked_want).any(-1), dead) and bool(torch.isfinite(nomask_want).all())
+    got, got0 = R.model(sd, cfg, ids, mask), R.model(sd, cfg, ids, None)
+    assert bool(torch.isfinite(got).all())
+    bound = FP32_OPS(cfg["num_hidden_layers"]) + storage
+    for b in range(R.WINDOW_B):                                         # each sample on its own: the short one must not hide behind the long one
+        e = R.rel_l2(got[b][~dead[b]], masked_want[b][~dead[b]])
+        print(f"TINY_WINDOW sample {b}: {int((~dead[b]).sum())} rows, rel-L2 {e:.3e} (bound {bound:.3e})")
+        assert e <= bound, (b, e)
+    e0 = R.rel_l2(got0, nomask_want)
+    assert e0 <= bound, e0
+    assert float((got[1, :R.WINDOW_LIVE] - got0[1, :R.WINDOW_LIVE]).abs().max()) == 0 and float((got[1, R.WINDOW_LIVE:] - got0[1, R.WINDOW_LIVE:]).abs().max()) > 0.5
+    return sd, cfg, ids, mask, got
+
+
+def test_window_case_matches_transformers_live():
+    pytest.importorskip("transformers")
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_gemma_golden", os.path.join(os.path.dirname(GOLDEN), "make_gemma_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    cfg, std, seed = R.TINY_WINDOW
+    ids, mask = R.window_inputs()
+    masked, nomask = gen.window_outputs(cfg, {k: v.double() for k, v in R.tiny_state(cfg, std, seed).items()}, ids, mask)
+    _window_case_errors(masked, nomask, 0.0)
+
+
+def test_window_case_matches_the_fixture():
+    from safetensors.torch import load_file
+    g = load_file(GOLDEN_WINDOW)
+    ids, mask = R.window_inputs()
+    assert torch.equal(g["ids"].long(), ids) and torch.equal(g["mask"].long(), mask)
+    sd, cfg, _, _, got = _window_case_errors(g["c.out.mask"].double(), g["c.out.nomask"].double(), 2.0 ** -24)
+    total = torch.stack([v.double().sum() for _, v in sorted(sd.items())]).sum()
+    assert float(total) == float(g["c.weight_sum"]), "the weights are not the ones the fixture was made with"
+    # the window is visible: without it the float64 output moves by several times the bf16 bound of the model test (a model that ignored the
+    # window would miss that bound by the same factor)
+    bound = 1.5 * R.rel_l2(R.model(sd, cfg, ids, mask, R.bf), got)
+    moved = R.rel_l2(R.model(sd, dict(cfg, sliding_window=4096), ids, mask), got)
+    print(f"TINY_WINDOW: bf16 bound {bound:.3e}; the window moves the output by {moved:.3f}")
+    assert moved >= 5 * bound
+
+
 def test_attention_reference_properties():
     g = torch.Generator().manual_seed(1)
     q, k, v = (torch.randn(2, 20, h, 16, generator=g, dtype=F64) for h in (4, 2, 2))

@@ -26,8 +26,9 @@
 // cap * tanh(x / cap) with tanh(y) = 1 - 2 / (e^2y + 1) through v_exp_f32 and v_rcp_f32 (exact limits -1 and 1 at e^2y = 0 and inf; absolute
 // error a few 2^-24, which the cap multiplies: far below the bf16 rounding of P). A causal launch ends its key loop at the workgroup's last
 // query row (or the sample's key length) and starts it at the window's first key of the workgroup's first row; a wave skips the tiles that lie
-// wholly above its own 32 rows' diagonal or behind its window. A row none of whose keys is live (possible only with a window, on padded rows
-// beyond kv_len + window) is written as zeros.
+// wholly above its own 32 rows' diagonal or behind its window. A row none of whose keys is live (every row of a sample whose kv_len is 0, and
+// with a window the padded rows from kv_len + window - 1 on) is written as zeros. K and V rows in [kv_len, L) are still read and enter the
+// products with a probability of zero: they must be finite.
 #include "ug_common.h"
 #include <math.h>
 #include <type_traits>
