@@ -800,7 +800,9 @@ int ug_img_u8_to_patches(const uint8_t* img, int64_t bstride, int64_t rstride, i
                          const float* mean_host, const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
 int ug_img_u8_to_patches_f32(const uint8_t* img, int64_t bstride, int64_t rstride, int64_t B, int64_t H, int64_t W, int32_t C, int32_t P, double rescale,
                              const float* mean_host, const float* std_host, void* out, int64_t ld_out, int64_t Kp, ug_stream_t stream);
-/* y = max(x, 0) over n contiguous elements, n a multiple of 8; y may be x. */
+/* y = x < 0 ? +0 : x over n contiguous elements, n a multiple of 8; y may be x. torch.relu's values bit for bit: a NaN propagates (it is not
+ * laundered into 0, which would hide an upstream fault), -0 stays -0, +-inf give +0 / +inf. The head's fused ReLU (ug_depth_head_out) is a
+ * different contract: it feeds a dot product and is specified on finite inputs. */
 int ug_relu(const void* x, void* y, int64_t n, ug_stream_t stream);
 int ug_relu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
 /* Second half of nn.ConvTranspose2d(C, C, kernel = stride = f): `prod` is the fp32 product (UG_EPI_F32) of the input rows [B h w][Cin] with the

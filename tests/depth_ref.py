@@ -3,6 +3,8 @@ CPU, from transformers' modules (models/depth_anything, models/dinov2, models/dp
 from the kernels. It takes transformers' state dict. `forward(..., dtype=torch.float64)` is the truth the GPU tests compare against;
 `round_bf16=True` rounds every tensor a bf16 module run materialises (the rounding points of the HIP path) while computing in `dtype`.
 tests/test_depth_ref_cpu.py pins it to transformers and to tests/golden/depth_tiny.safetensors (tests/golden/make_depth_golden.py).
+`bilinear_variant` / `bicubic_variant` are the one part that does follow the kernels: csrc/depth.hip's stated fp32 coordinate and weight arithmetic
+with float64 taps, the tight reference of the kernel sweep (tests/depth_kernel_cases.py), itself held to F.interpolate in float64 on the host.
 
 No GPU and no transformers are needed to import or run this file.
 """
@@ -99,7 +101,11 @@ def fingerprint(sd):
 
 def case_images(name, B=2):
     """The uint8 model inputs [B, H, W, 3] of a fixture case: smooth ramps plus seeded noise, so that neighbouring patches differ."""
-    H, W = CASES[name]
+    return images(*CASES[name], B)
+
+
+def images(H, W, B=2):
+    """uint8 [B, H, W, 3] of any size, by case_images' rule"""
     g = torch.Generator().manual_seed(1000 + H * 7 + W)
     yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
     imgs = []
@@ -194,6 +200,102 @@ def bicubic(x, Ho, Wo):
 def head_out(x, C, w, bias, max_depth=1.0, metric=False):
     v = (torch.relu(x[..., :C]) * w).sum(-1) + bias
     return (torch.sigmoid(v) if metric else torch.relu(v)) * max_depth
+
+
+# ---- the interpolation kernels' own arithmetic (csrc/depth.hip, -ffp-contract=off): the source coordinate, its floor or truncation, the weights and the
+# cubic coefficients in numpy float32, one rounding per operation as the kernel writes them; the taps' products and sums in float64. Kernel and
+# variant then share their weights bit for bit, and what separates them is the kernel's fp32 roundings of products and sums alone, which a bound
+# counts (BILINEAR_K, BICUBIC_K). F.interpolate in fp32 cannot play this part: torch's CPU kernels contract the coordinate into an FMA, which moves
+# it by an ulp - hundreds of 2^-24 scale at 518 pixels. `slip` names one deliberate mistake (tests/depth_kernel_cases.py, SLIPS). -----------------------------
+_f32 = np.float32
+BILINEAR_K = 4      # r = hy0 * (wx0 a + wx1 b) + hy1 * (wx0 c + wx1 d): a tap passes its product, the inner sum, the product with hy, the outer sum
+BICUBIC_K = 8       # r += row[j] cx[j] from 0, acc += r cy[i] from 0: tap (0, 0) passes its product, 3 sums (0 + p is exact), the product with cy, 3 sums
+
+
+def lin_scale32(n_in, n_out, align):
+    """lin_scale of depth.hip: the host's float division"""
+    if align:
+        return _f32(n_in - 1) / _f32(n_out - 1) if n_out > 1 else _f32(0)
+    return _f32(n_in) / _f32(n_out)
+
+
+def lin_src32(n_in, n_out, align, slip=None):
+    """lin_src of depth.hip for every output index -> (i0, i1 int64 [n_out], l0, l1 float32 [n_out])"""
+    if slip == "align_swapped":
+        align = not align
+    o = np.arange(n_out, dtype=np.float32)
+    scale = lin_scale32(n_in, n_out, align)
+    if align:
+        s = scale * o
+    elif slip == "no_half_pixel":
+        s = np.maximum(scale * o, _f32(0))
+    else:
+        s = scale * (o + _f32(0.5)) - _f32(0.5)
+        if slip != "negative_not_clamped":
+            s = np.maximum(s, _f32(0))
+    assert s.dtype == np.float32
+    i0 = np.minimum(s.astype(np.int64), n_in - 1)                       # (int)s truncates
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = s - i0.astype(np.float32)
+    if slip != "negative_not_clamped":                                  # the slip extrapolates at the border: l1 = -0.25, l0 = 1.25
+        l1 = np.minimum(np.maximum(l1, _f32(0)), _f32(1))
+    l0 = _f32(1) - l1
+    assert l0.dtype == l1.dtype == np.float32
+    return i0, i1, l0, l1
+
+
+def bilinear_variant(x, Ho, Wo, align, slip=None):
+    """x float64 [B, H, W, C] -> (the kernel's result with exact products and sums, sum |w_i| |x_i| of its four taps), float64 [B, Ho, Wo, C]"""
+    B, H, W, C = x.shape
+    y0, y1, hy0, hy1 = lin_src32(H, Ho, align, slip)
+    x0, x1, wx0, wx1 = lin_src32(W, Wo, align, slip)
+    hy0, hy1 = (torch.from_numpy(t.astype(np.float64))[None, :, None, None] for t in (hy0, hy1))
+    wx0, wx1 = (torch.from_numpy(t.astype(np.float64))[None, None, :, None] for t in (wx0, wx1))
+    tap = lambda yi, xi: x[:, torch.from_numpy(yi)][:, :, torch.from_numpy(xi)]
+    a, b, c, d = tap(y0, x0), tap(y0, x1), tap(y1, x0), tap(y1, x1)
+    val = hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d)
+    mag = hy0.abs() * (wx0.abs() * a.abs() + wx1.abs() * b.abs()) + hy1.abs() * (wx0.abs() * c.abs() + wx1.abs() * d.abs())
+    return val, mag
+
+
+def cubic_coef32(t, A=-0.75):
+    """cubic_coef of depth.hip on float32 [n] -> float32 [n, 4]; 5 A, 8 A, 4 A, A + 2 and A + 3 are exact for A = -0.75 and -0.5"""
+    A = _f32(A)
+    x0, x1, x2, x3 = t + _f32(1), t, _f32(1) - t, _f32(2) - t
+    outer = lambda u: ((A * u - _f32(5) * A) * u + _f32(8) * A) * u - _f32(4) * A
+    inner = lambda u: ((A + _f32(2)) * u - (A + _f32(3))) * u * u + _f32(1)
+    c = np.stack([outer(x0), inner(x1), inner(x2), outer(x3)], -1)
+    assert c.dtype == np.float32
+    return c
+
+
+def cubic_src32(n_in, n_out, slip=None):
+    """bicubic_kernel's coordinate for every output index -> (clamped tap indices int64 [n_out, 4], coefficients float32 [n_out, 4])"""
+    o = np.arange(n_out, dtype=np.float32)
+    r = lin_scale32(n_in, n_out, False) * (o + _f32(0.5)) - _f32(0.5)
+    fl = np.floor(r)
+    assert r.dtype == fl.dtype == np.float32
+    top = max(n_in - 2, 0) if slip == "taps_clamped_short" else n_in - 1
+    idx = np.clip(fl.astype(np.int64)[:, None] - 1 + np.arange(4), 0, top)
+    return idx, cubic_coef32(r - fl, -0.5 if slip == "cubic_a_half" else -0.75)
+
+
+def bicubic_variant(x, Ho, Wo, slip=None):
+    """x float64 [B, H, W] -> (the kernel's result with exact products and sums, sum |cy_i cx_j| |x_ij| of its sixteen taps), float64 [B, Ho, Wo]"""
+    iy, cy = cubic_src32(x.shape[1], Ho, slip)
+    ix, cx = cubic_src32(x.shape[2], Wo, slip)
+    cy, cx = torch.from_numpy(cy.astype(np.float64)), torch.from_numpy(cx.astype(np.float64))
+    iy, ix = torch.from_numpy(iy), torch.from_numpy(ix)
+    val = torch.zeros(x.shape[0], Ho, Wo, dtype=torch.float64)
+    mag = torch.zeros_like(val)
+    for i in range(4):
+        rows = x[:, iy[:, i]]
+        for j in range(4):
+            t = rows[:, :, ix[:, j]]
+            w = cy[:, i, None] * cx[None, :, j]
+            val += w * t
+            mag += w.abs() * t.abs()
+    return val, mag
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------------------------------

@@ -59,14 +59,14 @@ __global__ __launch_bounds__(128) void u8_to_patches_kernel(const uint8_t* __res
     }
 }
 
-// ---- ReLU over n contiguous elements, 8 per lane ------------------------------------------------------------------------------------------------
+// ---- ReLU over n contiguous elements, 8 per lane: x < 0 ? +0 : x, so NaN and -0 pass through as in torch.relu (fmaxf would launder a NaN into 0) ----
 template <typename T> __global__ __launch_bounds__(256) void relu_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8, int vec) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
     float f[8];
     ld8<T>(x + i * 8, f, vec != 0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = fmaxf(f[j], 0.0f);
+    for (int j = 0; j < 8; ++j) f[j] = f[j] < 0.0f ? 0.0f : f[j];
     st8<T>(y + i * 8, f, vec != 0);
 }
 

@@ -1124,7 +1124,7 @@ def img_u8_to_patches(x: torch.Tensor, patch: int, mean, std, rescale: float = 1
 
 
 def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """max(x, 0), contiguous, numel a multiple of 8; out may be x itself."""
+    """x < 0 ? +0 : x (torch.relu's values: NaN propagates, -0 stays -0), contiguous, numel a multiple of 8; out may be x itself."""
     dt = _act(x, "x")
     out = torch.empty_like(x) if out is None else out
     _chk(out, "out", dt)
