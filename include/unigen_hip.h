@@ -109,6 +109,41 @@ int64_t ug_gemm_workspace_bytes(void);
 /* replaces every nn.Linear on the path (torch F.linear -> BLAS) incl. fused epilogues. */
 int ug_gemm_bf16(const ug_gemm_desc* d, ug_stream_t stream);
 
+/* Which kernel ug_gemm_bf16 launches for a descriptor, and how - the dispatcher's own answer (gemm_check, then gemm_plan of csrc/gemm.hip),
+ * computed on the host: no device, no HIP call, no pointer dereferenced (pointer VALUES count: alignment, workspace NULL or not).
+ * ug_gemm_plan(d, ncu, force_tile, out): the plan of *d on a chip of ncu > 0 compute units under UG_GEMM_FORCE_TILE = force_tile (0: none).
+ * Returns what ug_gemm_bf16 returns for a refused descriptor (same code, same message), else UG_OK with *out filled; M == 0 (nothing to launch)
+ * gives UG_OK and an all-zero *out. ug_gemm_bf16(d) launches ug_gemm_plan(d, CUs of the device, UG_GEMM_FORCE_TILE).
+ *
+ * The dispatch rules, in the order they apply (T256 / T128 = tiles of 256^2 / 128^2 over all groups, KT = K / 64 K-tiles):
+ *   1. Fill: the 256^2 kernel (one persistent workgroup per CU) when M, N >= 192 and T256 / roundup(T256, 256) >= 0.6 T128 / roundup(T128, 512).
+ *   2. Small M: a launch that lost rule 1 with M, N >= 192 and T256 < ncu still takes the 256^2 kernel when rule 7 would split it and the
+ *      priced split (1.53 KT / slices + 22 + 2.5 slices us) is below 0.9 x the 128^2 kernel's rounds (0.97 or 1.27 us per K-tile). Not UG_EPI_F32.
+ *   3. force_tile 128 / 256 overrides rules 1-2.
+ *   4. The 256^2 kernel addresses a tile's A and W rows by unsigned 32-bit byte offsets from the tile's first row: a non-monotonic A row map
+ *      (a_bstride < a_rpb), or 255 rows (plus the A map's batch jumps inside them) + K elements reaching 2^31 bytes, go to the 128^2 kernel.
+ *   5. A LoRA segment (lora_r > 0) takes the 256^2 kernel's LoRA variant only with K >= 128 and not under UG_EPI_F32, skips rule 4, never splits.
+ *   6. UG_EPI_QKV_ROPE exists in the 256^2 kernel only (variant by head width): what rule 4 sends away is refused there; rules 1-3 do not apply.
+ *   7. Split-K tail: the T256 % ncu tiles of the last round, padded to a multiple of 8 (rem8), are each cut into
+ *      nslices = min(ncu / rem8, 8, KT / 4) K-slices when there are any, they fill at most half the CUs, KT >= 96, nslices >= 2 and the
+ *      workspace is there, 16-byte aligned and holds 4096 + rem8 nslices 256 KiB; with T256 < ncu the grid is rem8 x nslices workgroups.
+ *   8. wide16 bit 0: 16-byte epilogue accesses (N, ldc, c_gstride multiples of 8, C 16-byte aligned; the same of R under a residual epilogue);
+ *      bit 1: one row map per tile (c_rpb, and r_rpb under a residual epilogue, multiples of 256).
+ *   9. ug_conv2d_nhwc takes the 256^2 kernel's convolution variant (A gathered per filter tap) when B Ho Wo and Cout are multiples of 256,
+ *      Cin / 64 is a power of two >= 2, K >= 3 K-tiles, there are at least UG_CONV256_MIN_TILES (192) tiles, B < 256, H, W < 2048, Ho, Wo < 4096,
+ *      out and R are 16-byte aligned and the zero page holds 2 (Cin + 64) bytes; UG_CONV256=0 switches it off. No split-K tail. */
+enum { UG_GEMM_PLAIN = 0, UG_GEMM_LORA = 1, UG_GEMM_QK128 = 2, UG_GEMM_QK64 = 3, UG_GEMM_CONV = 4 };
+typedef struct ug_gemm_dispatch {
+    int32_t tile;                                   /* 128 or 256 */
+    int32_t variant;                                /* UG_GEMM_*: the 256^2 kernel's instantiation besides the epilogue (128^2: UG_GEMM_PLAIN) */
+    int32_t grid, grid_z;                           /* workgroups: 256^2 min(tiles, ncu) or rule 7's, z = 1; 128^2 tiles of one group, z = groups */
+    int32_t tiles, tiles_per_group;                 /* 256^2 tiles in all and per group (128^2: 0) */
+    int32_t rounds, full_tiles, nslices, rem8;      /* rounds of the persistent walk; tiles before the split tail; rule 7 (1, 0: no split) */
+    int32_t wide16, group_m, walk;                  /* rule 8; M-tiles per group of the tile walk and the walk's form (0 on the 128^2 kernel) */
+    int32_t lds_bytes;                              /* dynamic LDS of the launch */
+} ug_gemm_dispatch;
+int ug_gemm_plan(const ug_gemm_desc* d, int32_t ncu, int32_t force_tile, ug_gemm_dispatch* out);
+
 /* out[m][n] = R[m][n] + bf16( sum_k act(x[m][k]) * W[n][k] + b[n] ),  M <= 16 rows (per-sample vectors).
  * act: 0 none, 1 SiLU. Replaces AdaLayerNormZero.linear(silu(emb)), TimestepEmbedding, PixArtAlphaTextProjection
  * (diffusers 0.32.2 normalization.py / embeddings.py; called from UniGenTransformer.py:1222,1048-1049). */

@@ -321,7 +321,7 @@ def judge(got, truth, var=None, rows_from=None):
 
 
 def gemm_path(c, ncu, force=0, workspace=True):
-    """launch<EPI> / splitk_plan of csrc/gemm.hip restated: which kernel a descriptor without a LoRA segment runs on a chip of `ncu` CUs under
+    """gemm_plan / splitk_plan of csrc/gemm.hip restated (independently: tests/test_gemm_plan_cpu.py holds the two to each other): which kernel a descriptor without a LoRA segment runs on a chip of `ncu` CUs under
     UG_GEMM_FORCE_TILE = force, with or without the caller's workspace -> (tile, rounds of the persistent walk, K-slices of the split-K tail
     (1: none), tail tiles padded to 8, wide16 bits: 1 = 16-byte epilogue accesses, 2 = one row map per tile). The 128^2 kernel: (128, 1, 1, 0, 0).
     c: M, N, K, epilogue, groups, a_map, c_map, r_map, lda, ldw, ldc, ldr, c_gstride, r_gstride, c_off / r_off (elements the C / R base sits

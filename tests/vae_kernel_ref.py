@@ -111,7 +111,7 @@ def conv_check(c: dict, is_bf16: bool) -> int:
 
 
 def conv_takes_256(c: dict, zero_page_bytes: int = 4096, min_tiles: int = 1) -> bool:
-    """the dispatch condition of ug_conv2d_nhwc for the 256^2 GEMM kernel (with ug_gemm_launch_conv256's own K >= 3 K-tiles), pointers aside"""
+    """the dispatch condition of ug_conv2d_nhwc for the 256^2 GEMM kernel (gemm_plan's conditions of the convolution route, K >= 3 K-tiles among them), pointers aside"""
     M, ktp = c["B"] * c["Ho"] * c["Wo"], c["Cin"] // 64
     return (conv_check(c, True) == OK and M % 256 == 0 and c["Cout"] % 256 == 0 and c["Cin"] % 64 == 0 and ktp >= 2 and ktp & (ktp - 1) == 0 and
             zero_page_bytes >= 2 * (c["Cin"] + 64) and c["B"] < 256 and c["H"] < 2048 and c["W"] < 2048 and c["Ho"] < 4096 and c["Wo"] < 4096 and

@@ -827,7 +827,7 @@ int launch_pwg_t(const ug_gemm_desc& d, hipStream_t s) {
 
 }  // namespace
 
-// UG_GEMM_PWG=4 and the fused q/k RMSNorm + RoPE launch (head width 128, with RoPE): called by gemm.hip's launch_qkrope in the probe build
+// UG_GEMM_PWG=4 and the fused q/k RMSNorm + RoPE launch (head width 128, with RoPE): called by gemm.hip's gemm_launch in the probe build
 int ug_gemm_launch_pwg2_qkrope(const ug_gemm_desc& d, hipStream_t s) {
     return launch_pwg2_t<UG_EPI_QKV_ROPE, 1>(d, s);
 }

@@ -985,6 +985,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const ug_gemm_desc p, c
 #undef UG_BARRIER
 }
 
+// ---- host: gemm_check -> gemm_plan -> gemm_launch. The dispatch rules are stated once, at ug_gemm_plan in include/unigen_hip.h; the comments
+// below keep the measurements behind their constants. ----
+using GemmPlan = ug_gemm_dispatch;
+#ifdef UG_PROBE_BUILD
+constexpr int GEMM_PWG = 100, GEMM_PWG_QKROPE = 101;      // GemmPlan.variant of the probe library only: the one-wave-per-SIMD kernels (gemm_pwg.hip)
+#endif
+
 // UG_GEMM_FORCE_TILE=128|256 pins the kernel choice (tests / A-B timing); default: 256^2 tiles when they fill the chip.
 int forced_tile() { return ug_env_int("UG_GEMM_FORCE_TILE", 0); }
 
@@ -999,196 +1006,19 @@ int chip_cus() {
     return ncu;
 }
 
-// Split-K tail of a 256^2 launch of `tiles` tiles on `ncu` CUs (see the kernel header): the remainder tiles, padded to a multiple of 8 (rem8), are
-// each cut into `nsl` K-slices when they fill at most half the CUs, the K loop is long and the caller's workspace holds the slabs; nsl = 1: no split.
-// Measured (MI355X, with the fenced slabs of rounds 1-5): the slab round trip cost ~35 us, so the split only pays when a tile's K loop is long
-// (K = 15360 single-block proj_out: +3.5 %; K = 3072 shapes: -2...-3 %) -> require >= 96 K-tiles.
-struct SplitK { int rem8, nsl; };
-SplitK splitk_plan(const ug_gemm_desc& d, int64_t tiles, int ncu) {
-    const int rem = (int)(tiles % ncu), nkt = (int)(d.K / BK);
-    if (!UG_TUNE("UG_GEMM_SPLITK_TAIL", 1) || d.lora_r > 0 || rem == 0 || rem * 2 > ncu || !d.workspace || !ug_aligned(d.workspace, 16) ||
-        nkt < UG_TUNE("UG_GEMM_SPLITK_MIN_KT", UG_GEMM_SPLITK_MIN_KT_DEFAULT))
-        return {0, 1};
-    const int rem8 = (rem + 7) / 8 * 8;
-    int cand = ncu / rem8; if (cand > 8) cand = 8; if (cand > nkt / 4) cand = nkt / 4;
-    if (cand < 2 || (size_t)d.workspace_bytes < 4096 + (size_t)rem8 * cand * 65536 * sizeof(float)) return {0, 1};
-    return {rem8, cand};
-}
-
-template <int EPI>
-int launch(const ug_gemm_desc& d, hipStream_t s) {
-    const int groups = d.groups > 0 ? d.groups : 1;
-    const int64_t t256 = ((d.M + 255) / 256) * ((d.N + 255) / 256) * groups;
-    const int64_t t128 = ((d.M + 127) / 128) * ((d.N + 127) / 128) * groups;
-    // pick the tile by expected chip fill: 256 CUs x 1 workgroup (256^2) vs 256 x 2 (128^2, whose rate relative to the 256^2 kernel is the
-    // weight below: 0.82 on large shapes, but in the cfg2 forward the text-stream projections (M = B x 512) run better on 256^2 tiles:
-    // weight 60 % -> 2.011 images/s, 70 %: 2.004-2.008, 82 % (rounds 1-2): 1.995-2.000, 50 %: 2.010)
-    const double e256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-    const double e128 = 0.01 * UG_TUNE("UG_GEMM_E128_PCT", 60) * (double)t128 / (double)(((t128 + 511) / 512) * 512);
-    const bool lora = d.lora_r > 0;
-    bool big = (!lora || (d.K >= 2 * BK && EPI != UG_EPI_F32)) && d.M >= 192 && d.N >= 192 && e256 >= e128;
-    // Round 6 (small-M regime: the reference's own launch shape is batch 1, script/infer.sh:62-63): a FEW tiles with a LONG K loop - the text-stream and
-    // 512^2 forms of ff.net.2 (K = 12288) and of the single blocks' proj_out (K = 15360): 24-72 tiles of 256^2 - lost the fill comparison above to the
-    // 128^2 kernel, which then ran one round of whole K loops (512 x 3072 x 12288: 187 us = 207 TFLOP/s, profiles/r06i_shape_rates_cfg1.log) although
-    // the 256^2 kernel would cut exactly these launches into K-slices that fill the chip (its split-K tail). Priced in microseconds with the measured
-    // unit costs - a 256^2 K-tile 1.53 us, a 128^2 K-tile 0.97 us with one workgroup on the CU / 1.27 us with two, the slab round trip 22 + 2.5 us per slice:
-    const int ncu = chip_cus();
-    if (!big && !lora && EPI != UG_EPI_F32 && d.M >= 192 && d.N >= 192 && t256 < ncu && UG_TUNE("UG_GEMM_SPLITK_SMALLM", 1)) {
-        const SplitK sk = splitk_plan(d, t256, ncu);
-        if (sk.nsl > 1) {
-            const int nkt = (int)(d.K / BK);
-            const double t_split = 1.53 * nkt / sk.nsl + 22.0 + 2.5 * sk.nsl;     // (46 + 6 us per slice with the fenced slabs before round 6)
-            const double t_128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * nkt * (t128 <= ncu ? 0.97 : 1.27);
-            if (t_split < 0.9 * t_128) big = true;
-        }
-    }
-    const int f = forced_tile();
-    if (f == 128) big = false;
-    if (f == 256 && (!lora || (d.K >= 2 * BK && EPI != UG_EPI_F32))) big = true;
-    // the 256^2 kernel's buffer-form DMAs carry UNSIGNED 32-bit byte offsets relative to the tile's first row: the A row map must be monotonic
-    // (batch stride >= rows per batch; a broadcasting map such as RowMap(N, 0) goes to the 128^2 kernel, which keeps per-lane pointers), and the
-    // offset spans 255 rows plus one batch jump per batch boundary inside the tile: ceil(255 / rows_per_batch) of them
-    if (!lora && d.a_rpb > 0 && d.a_bstride < d.a_rpb) big = false;
+// the 256^2 kernel's buffer-form DMAs carry UNSIGNED 32-bit byte offsets relative to the tile's first row: the A row map must be monotonic
+// (batch stride >= rows per batch; a broadcasting map such as RowMap(N, 0) goes to the 128^2 kernel, which keeps per-lane pointers), and the
+// offset spans 255 rows plus one batch jump per batch boundary inside the tile: ceil(255 / rows_per_batch) of them
+bool tile256_offsets_fit(const ug_gemm_desc& d) {
+    if (d.a_rpb > 0 && d.a_bstride < d.a_rpb) return false;
     const int64_t a_jumps = d.a_rpb > 0 ? (255 + d.a_rpb - 1) / d.a_rpb : 0;
     const int64_t a_jump = d.a_rpb > 0 && d.a_bstride > d.a_rpb ? (d.a_bstride - d.a_rpb) * a_jumps : 0;
-    if (!lora && ((255 + a_jump) * d.lda + d.K) * 2 + 256 >= (int64_t)1 << 31) big = false;
-    if (!lora && (255 * d.ldw + d.K) * 2 + 256 >= (int64_t)1 << 31) big = false;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm128_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256_BYTES + 16 + UG_STAMP_LDS);
-        if (EPI != UG_EPI_F32)
-            (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, EPI != UG_EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256_BYTES + 16 + UG_STAMP_LDS);
-        attr_set = true;
-    }
-    if (big) {
-        const int total = (int)t256;
-        dim3 grid((unsigned)(total < ncu ? total : ncu), 1, 1);
-        // 16-byte epilogue accesses need 8-column granularity everywhere the epilogue touches
-        const bool res = d.epilogue == UG_EPI_RES_GATE || d.epilogue == UG_EPI_RES_SCALE;
-        const int wide16 = (d.N % 8 == 0 && d.ldc % 8 == 0 && d.c_gstride % 8 == 0 && ug_aligned(d.C, 16) &&
-                            (!res || (d.ldr % 8 == 0 && d.r_gstride % 8 == 0 && ug_aligned(d.R, 16)))) |
-                           ((d.c_rpb % 256 == 0 && (!res || d.r_rpb % 256 == 0) && UG_TUNE("UG_GEMM_EPI_ROWS_CONTIG", 1)) ? 2 : 0);
-        // (Measured and dropped, round 3: plain instead of non-temporal C stores in the full-tile epilogue - +-0.5 % on every cfg2 shape,
-        // profiles/r03d_gemm_cplain.log: the per-tile store cost is not the cache policy.)
-        // UG_GEMM_PWG=1: the one-wave-per-SIMD kernel (gemm_pwg.hip) takes every shape it supports
-#ifdef UG_PROBE_BUILD
-        if (EPI != UG_EPI_F32 && (wide16 & 1) && !lora && ug_env_int("UG_GEMM_PWG", 0) && d.K <= ug_env_int("UG_PWG_MAXK", 1 << 30) &&
-            (ug_env_int("UG_GEMM_PWG", 0) != 4 || (d.M % 256 == 0 && d.N % 256 == 0 && d.K % 128 == 0 && d.K >= 256 && d.a_rpb % 256 == 0 && total >= ncu)))
-            return ug_gemm_launch_pwg(d, s);
-#endif
-        // split-K tail (see the kernel header): needs the caller's workspace for the slabs and tickets
-        int full = total, nsl = 1;
-        // M-tiles per group of the tile walk. In the cfg2 forward (same box, bench.py x 2 each): 4 -> 2.014 images/s / GEMM 1337 TFLOP/s,
-        // 8 (rounds 1-2) 1.991-2.004 / 1322-1330, 6: 2.006, 3 / 5 / 2: 2.002-2.004, 16: 1.965, 32: 1.905 (profiles/r02c_group_m.log)
-        const int gm = ((UG_TUNE("UG_GEMM_GROUP_M", 4) & 0xff) << 8) | ((UG_TUNE("UG_GEMM_WALK", 0) & 3) << 16);
-        float* slabs = nullptr; unsigned* tickets = nullptr;
-        const SplitK sk = splitk_plan(d, total, ncu);
-        if (sk.nsl > 1) {
-            nsl = sk.nsl; full = total - total % ncu;
-            if (total < ncu) grid.x = (unsigned)(sk.rem8 * sk.nsl);     // one workgroup per K-slice (incl. the 8-alignment padding)
-            tickets = (unsigned*)d.workspace;
-            slabs = (float*)((char*)d.workspace + 4096);
-        }
-        if (lora) {     // (EPI_F32 never gets here with LoRA; its second instantiation is the plain kernel again)
-            hipLaunchKernelGGL((gemm256_kernel<EPI, EPI != UG_EPI_F32>), grid, dim3(512), LDS256_BYTES + 16 + UG_STAMP_LDS, s, d, (int)(t256 / groups), total, wide16 | gm, full, nsl, slabs, tickets, UgConvGeom{});
-        } else {
-#ifdef UG_DIAG_STAMPS
-            if (nsl == 1 && d.workspace && (size_t)d.workspace_bytes >= 4096 + (size_t)256 * 250 * 8 + (size_t)256 * 64 * 8) slabs = (float*)((char*)d.workspace + 4096);
-#endif
-            hipLaunchKernelGGL((gemm256_kernel<EPI, false>), grid, dim3(512), LDS256_BYTES + 16 + UG_STAMP_LDS, s, d, (int)(t256 / groups), total, wide16 | gm, full, nsl, slabs, tickets, UgConvGeom{});
-        }
-    } else {
-        const int nM = (int)((d.M + BM - 1) / BM), nN = (int)((d.N + BN - 1) / BN);
-        dim3 grid((unsigned)(nM * nN), 1, (unsigned)groups);
-        hipLaunchKernelGGL(gemm128_kernel<EPI>, grid, dim3(512), LDS_BYTES, s, d);
-    }
-    UG_CHECK_LAUNCH("ug_gemm_bf16");
-    return UG_OK;
+    return ((255 + a_jump) * d.lda + d.K) * 2 + 256 < ((int64_t)1 << 31) && (255 * d.ldw + d.K) * 2 + 256 < ((int64_t)1 << 31);
 }
 
-// UG_EPI_QKV_ROPE: 256^2 kernel only, whole tiles only (the q | k epilogue reduces rows across the four column waves of a tile)
-int launch_qkrope(const ug_gemm_desc& d, hipStream_t s) {
-    UG_REQUIRE(d.M % 256 == 0 && d.N % 256 == 0 && d.qk_until_n > 0 && d.qk_until_n % 256 == 0 && d.qk_until_n <= d.N, UG_ERR_UNSUPPORTED,
-               "ug_gemm_bf16: UG_EPI_QKV_ROPE needs M, N, qk_until_n multiples of 256 (M=%lld N=%lld qk_until_n=%lld)", (long long)d.M,
-               (long long)d.N, (long long)d.qk_until_n);
-    UG_REQUIRE(d.groups == 1 && d.lora_r <= 0, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE is neither grouped nor LoRA-extended");
-    const int qdh = d.qk_dh == 0 ? 128 : d.qk_dh;
-    UG_REQUIRE(qdh == 128 || qdh == 64, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE head width %d not in {64, 128}", qdh);
-    UG_REQUIRE(d.qk_wq && d.qk_wk && (d.rope_cs || qdh == 64) && ug_aligned(d.qk_wq, 8) && ug_aligned(d.qk_wk, 8) && ug_aligned(d.rope_cs, 16) &&
-               d.ldc % 8 == 0 && ug_aligned(d.C, 16), UG_ERR_BAD_ALIGN, "ug_gemm_bf16: UG_EPI_QKV_ROPE operands missing/misaligned");
-    UG_REQUIRE((d.rope_rpb == 0 || d.rope_rpb >= 256) && d.rope_rpb < (1ll << 31) && d.rope_pos0 >= 0 && d.rope_pos0 < (1ll << 31) &&
-               (d.gelu_from_n == 0 || d.gelu_from_n >= d.qk_until_n) && (d.c_shift_from_n == 0 || d.c_shift_from_n >= d.qk_until_n),
-               UG_ERR_BAD_SHAPE, "ug_gemm_bf16: UG_EPI_QKV_ROPE bad positions / column split");
-    constexpr int LDS = LDS256_BYTES + 16 + 256 * 8 * 4 + UG_STAMP_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<UG_EPI_QKV_ROPE, false, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<UG_EPI_QKV_ROPE, false, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    const int ncu = chip_cus();
-    const int total = (int)((d.M / 256) * (d.N / 256));
-    {   // this epilogue only exists in the 256^2 kernel: its buffer-form A offsets need a monotonic row map and < 2^31 bytes per tile (see launch())
-        const int64_t a_jumps = d.a_rpb > 0 ? (255 + d.a_rpb - 1) / d.a_rpb : 0;
-        const int64_t a_jump = d.a_rpb > 0 && d.a_bstride > d.a_rpb ? (d.a_bstride - d.a_rpb) * a_jumps : 0;
-        UG_REQUIRE((d.a_rpb == 0 || d.a_bstride >= d.a_rpb) && ((255 + a_jump) * d.lda + d.K) * 2 + 256 < ((int64_t)1 << 31) &&
-                   (255 * d.ldw + d.K) * 2 + 256 < ((int64_t)1 << 31), UG_ERR_BAD_SHAPE,
-                   "ug_gemm_bf16: UG_EPI_QKV_ROPE needs a monotonic A row map (batch stride %lld >= rows per batch %lld) and tiles below 2^31 bytes",
-                   (long long)d.a_bstride, (long long)d.a_rpb);
-    }
-    UG_REQUIRE(d.c_rpb % 256 == 0, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE needs the C row map's rows per batch (%lld) to be a multiple of 256",
-               (long long)d.c_rpb);
-#ifdef UG_PROBE_BUILD
-    // UG_GEMM_PWG=4: the one-wave-per-SIMD probe kernel's port of this epilogue (head width 128 with RoPE, whole rounds, K a multiple of 128)
-    if (ug_env_int("UG_GEMM_PWG", 0) == 4 && qdh == 128 && d.rope_cs && d.K % 128 == 0 && d.K >= 256 && d.a_rpb % 256 == 0 && total >= ncu &&
-        d.K <= ug_env_int("UG_PWG_MAXK", 1 << 30))
-        return ug_gemm_launch_pwg2_qkrope(d, s);
-#endif
-    const int wgm = 3 | ((UG_TUNE("UG_GEMM_GROUP_M", 4) & 0xff) << 8) | ((UG_TUNE("UG_GEMM_WALK", 0) & 3) << 16);
-    const dim3 grid((unsigned)(total < ncu ? total : ncu));
-    float* stamps = nullptr;
-#ifdef UG_DIAG_STAMPS
-    if (d.workspace && (size_t)d.workspace_bytes >= 4096 + (size_t)256 * 250 * 8) stamps = (float*)((char*)d.workspace + 4096);
-#endif
-    if (qdh == 128)
-        hipLaunchKernelGGL((gemm256_kernel<UG_EPI_QKV_ROPE, false, 128>), grid, dim3(512), LDS, s, d, total, total, wgm, total, 1, stamps, (unsigned*)nullptr, UgConvGeom{});
-    else
-        hipLaunchKernelGGL((gemm256_kernel<UG_EPI_QKV_ROPE, false, 64>), grid, dim3(512), LDS, s, d, total, total, wgm, total, 1, stamps, (unsigned*)nullptr, UgConvGeom{});
-    UG_CHECK_LAUNCH("ug_gemm_bf16");
-    return UG_OK;
-}
-
-}  // namespace
-
-// ug_conv2d_nhwc on the 256^2 kernel (see UgConvGeom): whole 256^2 tiles, bias or residual epilogue, no split-K tail (no workspace at this boundary).
-int ug_gemm_launch_conv256(const ug_gemm_desc& d, const UgConvGeom& cv, hipStream_t s) {
-    if (d.M % 256 || d.N % 256 || d.K % BK || cv.ktp < 2 || (cv.ktp & (cv.ktp - 1)) || d.K / BK < 3) return UG_ERR_UNSUPPORTED;
-    const int ncu = chip_cus();
-    constexpr int LDS = LDS256_BYTES + 16 + UG_STAMP_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<UG_EPI_BIAS, false, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<UG_EPI_RES_SCALE, false, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    const int total = (int)((d.M / 256) * (d.N / 256));
-    const int wgm = 3 | ((UG_TUNE("UG_GEMM_GROUP_M", 4) & 0xff) << 8);       // 16-byte epilogue accesses, one row map per tile (C and R are plain [M][N])
-    const dim3 grid((unsigned)(total < ncu ? total : ncu));
-    if (d.epilogue == UG_EPI_RES_SCALE)
-        hipLaunchKernelGGL((gemm256_kernel<UG_EPI_RES_SCALE, false, 128, true>), grid, dim3(512), LDS, s, d, total, total, wgm, total, 1, (float*)nullptr, (unsigned*)nullptr, cv);
-    else
-        hipLaunchKernelGGL((gemm256_kernel<UG_EPI_BIAS, false, 128, true>), grid, dim3(512), LDS, s, d, total, total, wgm, total, 1, (float*)nullptr, (unsigned*)nullptr, cv);
-    UG_CHECK_LAUNCH("ug_conv2d_nhwc(256)");
-    return UG_OK;
-}
-
-extern "C" int64_t ug_gemm_workspace_bytes(void) { return 4096 + (int64_t)256 * 65536 * (int64_t)sizeof(float); }
-
-extern "C" int ug_gemm_bf16(const ug_gemm_desc* dp, ug_stream_t stream) {
-    UG_REQUIRE(dp != nullptr, UG_ERR_BAD_SHAPE, "ug_gemm_bf16: null descriptor");
-    ug_gemm_desc d = *dp;
-    if (d.groups <= 0) d.groups = 1;
+// Every refusal of ug_gemm_bf16, in its order; d.groups is already normalised (<= 0 -> 1). M == 0 is UG_OK with nothing to launch and ends the
+// checks where it stands: the callers test it after a UG_OK.
+int gemm_check(const ug_gemm_desc& d) {
     UG_REQUIRE(d.M >= 0 && d.N > 0 && d.K > 0, UG_ERR_BAD_SHAPE, "ug_gemm_bf16: bad M/N/K %lld/%lld/%lld",
                (long long)d.M, (long long)d.N, (long long)d.K);
     if (d.M == 0) return UG_OK;
@@ -1221,14 +1051,245 @@ extern "C" int ug_gemm_bf16(const ug_gemm_desc* dp, ug_stream_t stream) {
                    UG_ERR_BAD_ALIGN, "ug_gemm_bf16: LoRA operands missing/misaligned");
         UG_REQUIRE(d.groups == 1, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: LoRA epilogue is not grouped");
     }
-    hipStream_t s = (hipStream_t)stream;
-    switch (d.epilogue) {
-        case UG_EPI_BIAS: return launch<UG_EPI_BIAS>(d, s);
-        case UG_EPI_BIAS_GELU: return launch<UG_EPI_BIAS_GELU>(d, s);
-        case UG_EPI_RES_GATE: return launch<UG_EPI_RES_GATE>(d, s);
-        case UG_EPI_RES_SCALE: return launch<UG_EPI_RES_SCALE>(d, s);
-        case UG_EPI_F32: return launch<UG_EPI_F32>(d, s);
-        case UG_EPI_QKV_ROPE: return launch_qkrope(d, s);
-        default: UG_FAIL(UG_ERR_UNSUPPORTED, "ug_gemm_bf16: unknown epilogue %d", d.epilogue);
+    if (d.epilogue != UG_EPI_QKV_ROPE) {
+        UG_REQUIRE(d.epilogue >= UG_EPI_BIAS && d.epilogue <= UG_EPI_F32, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: unknown epilogue %d", d.epilogue);
+        return UG_OK;
+    }
+    // UG_EPI_QKV_ROPE: 256^2 kernel only, whole tiles only (the q | k epilogue reduces rows across the four column waves of a tile)
+    UG_REQUIRE(d.M % 256 == 0 && d.N % 256 == 0 && d.qk_until_n > 0 && d.qk_until_n % 256 == 0 && d.qk_until_n <= d.N, UG_ERR_UNSUPPORTED,
+               "ug_gemm_bf16: UG_EPI_QKV_ROPE needs M, N, qk_until_n multiples of 256 (M=%lld N=%lld qk_until_n=%lld)", (long long)d.M,
+               (long long)d.N, (long long)d.qk_until_n);
+    UG_REQUIRE(d.groups == 1 && d.lora_r <= 0, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE is neither grouped nor LoRA-extended");
+    const int qdh = d.qk_dh == 0 ? 128 : d.qk_dh;
+    UG_REQUIRE(qdh == 128 || qdh == 64, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE head width %d not in {64, 128}", qdh);
+    UG_REQUIRE(d.qk_wq && d.qk_wk && (d.rope_cs || qdh == 64) && ug_aligned(d.qk_wq, 8) && ug_aligned(d.qk_wk, 8) && ug_aligned(d.rope_cs, 16) &&
+               d.ldc % 8 == 0 && ug_aligned(d.C, 16), UG_ERR_BAD_ALIGN, "ug_gemm_bf16: UG_EPI_QKV_ROPE operands missing/misaligned");
+    UG_REQUIRE((d.rope_rpb == 0 || d.rope_rpb >= 256) && d.rope_rpb < (1ll << 31) && d.rope_pos0 >= 0 && d.rope_pos0 < (1ll << 31) &&
+               (d.gelu_from_n == 0 || d.gelu_from_n >= d.qk_until_n) && (d.c_shift_from_n == 0 || d.c_shift_from_n >= d.qk_until_n),
+               UG_ERR_BAD_SHAPE, "ug_gemm_bf16: UG_EPI_QKV_ROPE bad positions / column split");
+    // what sends any other epilogue to the 128^2 kernel is refused here (and so is a NEGATIVE a_rpb above the batch stride, as it always was)
+    UG_REQUIRE((d.a_rpb >= 0 || d.a_bstride >= d.a_rpb) && tile256_offsets_fit(d), UG_ERR_BAD_SHAPE,
+               "ug_gemm_bf16: UG_EPI_QKV_ROPE needs a monotonic A row map (batch stride %lld >= rows per batch %lld) and tiles below 2^31 bytes",
+               (long long)d.a_bstride, (long long)d.a_rpb);
+    UG_REQUIRE(d.c_rpb % 256 == 0, UG_ERR_UNSUPPORTED, "ug_gemm_bf16: UG_EPI_QKV_ROPE needs the C row map's rows per batch (%lld) to be a multiple of 256",
+               (long long)d.c_rpb);
+    return UG_OK;
+}
+
+// Split-K tail of a 256^2 launch of `tiles` tiles on `ncu` CUs (see the kernel header): the remainder tiles, padded to a multiple of 8 (rem8), are
+// each cut into `nsl` K-slices when they fill at most half the CUs, the K loop is long and the caller's workspace holds the slabs; nsl = 1: no split.
+// Measured (MI355X, with the fenced slabs of rounds 1-5): the slab round trip cost ~35 us, so the split only pays when a tile's K loop is long
+// (K = 15360 single-block proj_out: +3.5 %; K = 3072 shapes: -2...-3 %) -> require >= 96 K-tiles.
+struct SplitK { int rem8, nsl; };
+SplitK splitk_plan(const ug_gemm_desc& d, int64_t tiles, int ncu) {
+    const int rem = (int)(tiles % ncu), nkt = (int)(d.K / BK);
+    if (!UG_TUNE("UG_GEMM_SPLITK_TAIL", 1) || d.lora_r > 0 || rem == 0 || rem * 2 > ncu || !d.workspace || !ug_aligned(d.workspace, 16) ||
+        nkt < UG_TUNE("UG_GEMM_SPLITK_MIN_KT", UG_GEMM_SPLITK_MIN_KT_DEFAULT))
+        return {0, 1};
+    const int rem8 = (rem + 7) / 8 * 8;
+    int cand = ncu / rem8; if (cand > 8) cand = 8; if (cand > nkt / 4) cand = nkt / 4;
+    if (cand < 2 || (size_t)d.workspace_bytes < 4096 + (size_t)rem8 * cand * 65536 * sizeof(float)) return {0, 1};
+    return {rem8, cand};
+}
+
+// The whole dispatch decision of a checked descriptor on a chip of `ncu` CUs: pure (no HIP call, no pointer dereferenced, and outside the probe
+// build's UG_TUNE switches no environment). `conv`: the descriptor is ug_conv2d_nhwc's implicit GEMM; tile 0 then means that the route's
+// conditions fail and the caller keeps its own kernel.
+GemmPlan gemm_plan(const ug_gemm_desc& d, int ncu, int force_tile, const UgConvRoute* conv = nullptr) {
+    GemmPlan pl = {};
+    const int groups = d.groups > 0 ? d.groups : 1;
+    const int64_t t256 = ((d.M + 255) / 256) * ((d.N + 255) / 256) * groups;
+    const int64_t t128 = ((d.M + 127) / 128) * ((d.N + 127) / 128) * groups;
+    const int nkt = (int)(d.K / BK);
+    const bool lora = d.lora_r > 0, f32 = d.epilogue == UG_EPI_F32, qk = !conv && d.epilogue == UG_EPI_QKV_ROPE;
+    SplitK sk = {0, 1};
+    bool big;
+    if (conv) {     // whole 256^2 tiles, Cin / 64 a power of two >= 2 K-tiles per tap, packed output coordinates (B < 256, Ho, Wo < 4096), no split-K tail
+        const UgConvGeom& g = conv->geom;
+        big = d.M % 256 == 0 && d.N % 256 == 0 && d.K % BK == 0 && g.ktp >= 2 && (g.ktp & (g.ktp - 1)) == 0 && nkt >= 3 &&
+              conv->zero_bytes >= 2 * (d.lda + 64) && conv->B < 256 && g.H < 2048 && g.W < 2048 && g.Ho < 4096 && g.Wo < 4096 &&
+              ug_aligned(d.C, 16) && (!d.R || ug_aligned(d.R, 16)) && t256 >= conv->min_tiles;
+    } else if (qk) {
+        big = true;     // this epilogue only exists in the 256^2 kernel: gemm_check has refused what that kernel cannot address
+    } else {
+        // pick the tile by expected chip fill: 256 CUs x 1 workgroup (256^2) vs 256 x 2 (128^2, whose rate relative to the 256^2 kernel is the
+        // weight below: 0.82 on large shapes, but in the cfg2 forward the text-stream projections (M = B x 512) run better on 256^2 tiles:
+        // weight 60 % -> 2.011 images/s, 70 %: 2.004-2.008, 82 % (rounds 1-2): 1.995-2.000, 50 %: 2.010)
+        const double e256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
+        const double e128 = 0.01 * UG_TUNE("UG_GEMM_E128_PCT", 60) * (double)t128 / (double)(((t128 + 511) / 512) * 512);
+        const bool lora256 = !lora || (d.K >= 2 * BK && !f32);      // the LoRA variant needs two K-tiles and has no fp32 epilogue
+        big = lora256 && d.M >= 192 && d.N >= 192 && e256 >= e128;
+        sk = splitk_plan(d, t256, ncu);
+        // Round 6 (small-M regime: the reference's own launch shape is batch 1, script/infer.sh:62-63): a FEW tiles with a LONG K loop - the text-stream and
+        // 512^2 forms of ff.net.2 (K = 12288) and of the single blocks' proj_out (K = 15360): 24-72 tiles of 256^2 - lost the fill comparison above to the
+        // 128^2 kernel, which then ran one round of whole K loops (512 x 3072 x 12288: 187 us = 207 TFLOP/s, profiles/r06i_shape_rates_cfg1.log) although
+        // the 256^2 kernel would cut exactly these launches into K-slices that fill the chip (its split-K tail). Priced in microseconds with the measured
+        // unit costs - a 256^2 K-tile 1.53 us, a 128^2 K-tile 0.97 us with one workgroup on the CU / 1.27 us with two, the slab round trip 22 + 2.5 us per slice:
+        if (!big && !lora && !f32 && d.M >= 192 && d.N >= 192 && t256 < ncu && sk.nsl > 1 && UG_TUNE("UG_GEMM_SPLITK_SMALLM", 1)) {
+            const double t_split = 1.53 * nkt / sk.nsl + 22.0 + 2.5 * sk.nsl;     // (46 + 6 us per slice with the fenced slabs before round 6)
+            const double t_128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * nkt * (t128 <= ncu ? 0.97 : 1.27);
+            if (t_split < 0.9 * t_128) big = true;
+        }
+        if (force_tile == 128) big = false;
+        if (force_tile == 256 && lora256) big = true;
+        if (!lora && !tile256_offsets_fit(d)) big = false;
+    }
+    if (!big) {
+        if (conv) return pl;
+        pl.tile = 128; pl.variant = UG_GEMM_PLAIN;
+        pl.grid = (int)((d.M + BM - 1) / BM) * (int)((d.N + BN - 1) / BN); pl.grid_z = groups;
+        pl.rounds = 1; pl.nslices = 1; pl.lds_bytes = LDS_BYTES;
+        return pl;
+    }
+    const int total = (int)t256;
+    pl.tile = 256; pl.tiles = pl.full_tiles = total; pl.tiles_per_group = (int)(t256 / groups);
+    pl.grid = total < ncu ? total : ncu; pl.grid_z = 1;
+    pl.rounds = (total + ncu - 1) / ncu; pl.nslices = 1;
+    pl.lds_bytes = LDS256_BYTES + 16 + UG_STAMP_LDS + (qk ? 256 * 8 * 4 : 0);
+    // M-tiles per group of the tile walk. In the cfg2 forward (same box, bench.py x 2 each): 4 -> 2.014 images/s / GEMM 1337 TFLOP/s,
+    // 8 (rounds 1-2) 1.991-2.004 / 1322-1330, 6: 2.006, 3 / 5 / 2: 2.002-2.004, 16: 1.965, 32: 1.905 (profiles/r02c_group_m.log)
+    pl.group_m = UG_TUNE("UG_GEMM_GROUP_M", 4) & 0xff;
+    if (conv) {     // 16-byte epilogue accesses, one row map per tile (C and R are plain [M][N])
+        pl.variant = UG_GEMM_CONV; pl.wide16 = 3;
+        return pl;
+    }
+    pl.walk = UG_TUNE("UG_GEMM_WALK", 0) & 3;
+    if (qk) {
+        const int qdh = d.qk_dh == 0 ? 128 : d.qk_dh;
+        pl.variant = qdh == 128 ? UG_GEMM_QK128 : UG_GEMM_QK64; pl.wide16 = 3;
+#ifdef UG_PROBE_BUILD
+        // UG_GEMM_PWG=4: the one-wave-per-SIMD probe kernel's port of this epilogue (head width 128 with RoPE, whole rounds, K a multiple of 128)
+        if (ug_env_int("UG_GEMM_PWG", 0) == 4 && qdh == 128 && d.rope_cs && d.K % 128 == 0 && d.K >= 256 && d.a_rpb % 256 == 0 && total >= ncu &&
+            d.K <= ug_env_int("UG_PWG_MAXK", 1 << 30))
+            pl.variant = GEMM_PWG_QKROPE;
+#endif
+        return pl;
+    }
+    // 16-byte epilogue accesses need 8-column granularity everywhere the epilogue touches
+    const bool res = d.epilogue == UG_EPI_RES_GATE || d.epilogue == UG_EPI_RES_SCALE;
+    pl.wide16 = (d.N % 8 == 0 && d.ldc % 8 == 0 && d.c_gstride % 8 == 0 && ug_aligned(d.C, 16) &&
+                 (!res || (d.ldr % 8 == 0 && d.r_gstride % 8 == 0 && ug_aligned(d.R, 16)))) |
+                ((d.c_rpb % 256 == 0 && (!res || d.r_rpb % 256 == 0) && UG_TUNE("UG_GEMM_EPI_ROWS_CONTIG", 1)) ? 2 : 0);
+    // (Measured and dropped, round 3: plain instead of non-temporal C stores in the full-tile epilogue - +-0.5 % on every cfg2 shape,
+    // profiles/r03d_gemm_cplain.log: the per-tile store cost is not the cache policy.)
+    pl.variant = lora ? UG_GEMM_LORA : UG_GEMM_PLAIN;
+#ifdef UG_PROBE_BUILD
+    // UG_GEMM_PWG=1: the one-wave-per-SIMD kernel (gemm_pwg.hip) takes every shape it supports
+    if (!f32 && (pl.wide16 & 1) && !lora && ug_env_int("UG_GEMM_PWG", 0) && d.K <= ug_env_int("UG_PWG_MAXK", 1 << 30) &&
+        (ug_env_int("UG_GEMM_PWG", 0) != 4 || (d.M % 256 == 0 && d.N % 256 == 0 && d.K % 128 == 0 && d.K >= 256 && d.a_rpb % 256 == 0 && total >= ncu))) {
+        pl.variant = GEMM_PWG;
+        return pl;
+    }
+#endif
+    // split-K tail (see the kernel header): needs the caller's workspace for the slabs and tickets
+    if (sk.nsl > 1) {
+        pl.nslices = sk.nsl; pl.rem8 = sk.rem8; pl.full_tiles = total - total % ncu;
+        if (total < ncu) pl.grid = sk.rem8 * sk.nsl;     // one workgroup per K-slice (incl. the 8-alignment padding)
+    }
+    return pl;
+}
+
+// The kernel's dynamic-LDS limit, raised once per process per instantiation. The attribute belongs to the device that is current at that first
+// launch: like chip_cus(), this assumes that the process drives ONE device.
+template <auto Kernel>
+void lds_limit_once(int bytes) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        attr_set = true;
     }
 }
+
+template <auto Kernel>
+void run128(const ug_gemm_desc& d, const GemmPlan& pl, hipStream_t s) {
+    lds_limit_once<Kernel>(pl.lds_bytes);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)pl.grid, 1, (unsigned)pl.grid_z), dim3(512), pl.lds_bytes, s, d);
+}
+
+template <auto Kernel>
+void run256(const ug_gemm_desc& d, const GemmPlan& pl, const UgConvGeom& cv, hipStream_t s) {
+    lds_limit_once<Kernel>(pl.lds_bytes);
+    float* slabs = nullptr; unsigned* tickets = nullptr;
+    if (pl.nslices > 1) {
+        tickets = (unsigned*)d.workspace;
+        slabs = (float*)((char*)d.workspace + 4096);
+    }
+#ifdef UG_DIAG_STAMPS      /* an unsplit launch of the plain or q/k variant stamps into the caller's workspace (the plain one: phase stamps behind the tile stamps) */
+    const bool qk = pl.variant == UG_GEMM_QK128 || pl.variant == UG_GEMM_QK64;
+    if (pl.nslices == 1 && (qk || pl.variant == UG_GEMM_PLAIN) && d.workspace &&
+        (size_t)d.workspace_bytes >= 4096 + (size_t)256 * 250 * 8 + (qk ? 0 : (size_t)256 * 64 * 8))
+        slabs = (float*)((char*)d.workspace + 4096);
+#endif
+    const int wide16_gm = pl.wide16 | (pl.group_m << 8) | (pl.walk << 16);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)pl.grid), dim3(512), pl.lds_bytes, s, d, pl.tiles_per_group, pl.tiles, wide16_gm, pl.full_tiles, pl.nslices, slabs,
+                       tickets, cv);
+}
+
+// (kernel, epilogue) -> instantiation; the 128^2 kernel stands behind the 256^2 kernel's variants
+constexpr int GEMM_T128 = 5;
+constexpr int gemm_key(int kernel, int epilogue) { return kernel * 8 + epilogue; }
+
+int gemm_launch(const ug_gemm_desc& d, const GemmPlan& pl, hipStream_t s, const UgConvGeom& cv = UgConvGeom{}) {
+#ifdef UG_PROBE_BUILD
+    if (pl.variant == GEMM_PWG) return ug_gemm_launch_pwg(d, s);
+    if (pl.variant == GEMM_PWG_QKROPE) return ug_gemm_launch_pwg2_qkrope(d, s);
+#endif
+    switch (gemm_key(pl.tile == 128 ? GEMM_T128 : pl.variant, d.epilogue)) {
+        case gemm_key(GEMM_T128, UG_EPI_BIAS): run128<gemm128_kernel<UG_EPI_BIAS>>(d, pl, s); break;
+        case gemm_key(GEMM_T128, UG_EPI_BIAS_GELU): run128<gemm128_kernel<UG_EPI_BIAS_GELU>>(d, pl, s); break;
+        case gemm_key(GEMM_T128, UG_EPI_RES_GATE): run128<gemm128_kernel<UG_EPI_RES_GATE>>(d, pl, s); break;
+        case gemm_key(GEMM_T128, UG_EPI_RES_SCALE): run128<gemm128_kernel<UG_EPI_RES_SCALE>>(d, pl, s); break;
+        case gemm_key(GEMM_T128, UG_EPI_F32): run128<gemm128_kernel<UG_EPI_F32>>(d, pl, s); break;
+        case gemm_key(UG_GEMM_PLAIN, UG_EPI_BIAS): run256<gemm256_kernel<UG_EPI_BIAS, false>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_PLAIN, UG_EPI_BIAS_GELU): run256<gemm256_kernel<UG_EPI_BIAS_GELU, false>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_PLAIN, UG_EPI_RES_GATE): run256<gemm256_kernel<UG_EPI_RES_GATE, false>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_PLAIN, UG_EPI_RES_SCALE): run256<gemm256_kernel<UG_EPI_RES_SCALE, false>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_PLAIN, UG_EPI_F32): run256<gemm256_kernel<UG_EPI_F32, false>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_LORA, UG_EPI_BIAS): run256<gemm256_kernel<UG_EPI_BIAS, true>>(d, pl, cv, s); break;      // (UG_EPI_F32 never plans the LoRA variant)
+        case gemm_key(UG_GEMM_LORA, UG_EPI_BIAS_GELU): run256<gemm256_kernel<UG_EPI_BIAS_GELU, true>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_LORA, UG_EPI_RES_GATE): run256<gemm256_kernel<UG_EPI_RES_GATE, true>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_LORA, UG_EPI_RES_SCALE): run256<gemm256_kernel<UG_EPI_RES_SCALE, true>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_QK128, UG_EPI_QKV_ROPE): run256<gemm256_kernel<UG_EPI_QKV_ROPE, false, 128>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_QK64, UG_EPI_QKV_ROPE): run256<gemm256_kernel<UG_EPI_QKV_ROPE, false, 64>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_CONV, UG_EPI_BIAS): run256<gemm256_kernel<UG_EPI_BIAS, false, 128, true>>(d, pl, cv, s); break;
+        case gemm_key(UG_GEMM_CONV, UG_EPI_RES_SCALE): run256<gemm256_kernel<UG_EPI_RES_SCALE, false, 128, true>>(d, pl, cv, s); break;
+        default: UG_FAIL(UG_ERR_UNSUPPORTED, "ug_gemm_bf16: no kernel for variant %d with epilogue %d", pl.variant, d.epilogue);
+    }
+    UG_CHECK_LAUNCH(pl.variant == UG_GEMM_CONV ? "ug_conv2d_nhwc(256)" : "ug_gemm_bf16");
+    return UG_OK;
+}
+
+// the head of both entry points: the descriptor by value, groups normalised, checked
+int gemm_accept(const ug_gemm_desc* dp, ug_gemm_desc& d) {
+    UG_REQUIRE(dp != nullptr, UG_ERR_BAD_SHAPE, "ug_gemm_bf16: null descriptor");
+    d = *dp;
+    if (d.groups <= 0) d.groups = 1;
+    return gemm_check(d);
+}
+
+}  // namespace
+
+// ug_conv2d_nhwc on the 256^2 kernel (see UgConvGeom): whole 256^2 tiles, bias or residual epilogue, no split-K tail (no workspace at this boundary).
+int ug_gemm_conv256(const ug_gemm_desc& d, const UgConvRoute& cv, hipStream_t s) {
+    const GemmPlan pl = gemm_plan(d, chip_cus(), 0, &cv);
+    return pl.tile == 256 ? gemm_launch(d, pl, s, cv.geom) : UG_ERR_UNSUPPORTED;
+}
+
+extern "C" int64_t ug_gemm_workspace_bytes(void) { return 4096 + (int64_t)256 * 65536 * (int64_t)sizeof(float); }
+
+extern "C" int ug_gemm_plan(const ug_gemm_desc* dp, int32_t ncu, int32_t force_tile, ug_gemm_dispatch* out) {
+    ug_gemm_desc d;
+    const int rc = gemm_accept(dp, d);
+    if (rc != UG_OK) return rc;
+    UG_REQUIRE(ncu > 0 && out != nullptr, UG_ERR_BAD_SHAPE, "ug_gemm_plan: needs ncu > 0 and a result");
+    *out = d.M == 0 ? GemmPlan{} : gemm_plan(d, ncu, force_tile);
+    return UG_OK;
+}
+
+extern "C" int ug_gemm_bf16(const ug_gemm_desc* dp, ug_stream_t stream) {
+    ug_gemm_desc d;
+    const int rc = gemm_accept(dp, d);
+    if (rc != UG_OK || d.M == 0) return rc;
+    return gemm_launch(d, gemm_plan(d, chip_cus(), forced_tile()), (hipStream_t)stream);
+}
+

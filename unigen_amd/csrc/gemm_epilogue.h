@@ -12,7 +12,9 @@ int ug_gemm_launch_pwg2_qkrope(const ug_gemm_desc& d, hipStream_t s);
 // Implicit-GEMM convolution on the 256^2 kernel (vae.hip -> gemm.hip): the A operand of ug_gemm_desc is the NHWC activation, gathered per filter tap.
 // M = B Ho Wo output pixels, N = Cout, K = KH KW Cin with Cin / 64 = ktp K-tiles per tap (a power of two >= 2); `zero` = at least Cin + 64 zero elements.
 struct UgConvGeom { const bf16_t* zero; int H, W, Cin, Ho, Wo, KW, stride, pad_t, pad_l, up, ktp; };
-int ug_gemm_launch_conv256(const ug_gemm_desc& d, const UgConvGeom& cv, hipStream_t s);      // UG_ERR_UNSUPPORTED: the caller keeps its own kernel
+// What ug_conv2d_nhwc hands to the GEMM dispatcher: the kernel's geometry and what only the route's conditions (gemm_plan in gemm.hip) look at
+struct UgConvRoute { UgConvGeom geom; int64_t B, zero_bytes, min_tiles; };
+int ug_gemm_conv256(const ug_gemm_desc& d, const UgConvRoute& cv, hipStream_t s);      // UG_ERR_UNSUPPORTED: the caller keeps its own kernel
 
 namespace {
 

@@ -744,19 +744,17 @@ extern "C" int ug_conv2d_nhwc(const ug_conv_desc* dp, ug_stream_t stream) {
     p.B = (int)d.B; p.H = (int)d.H; p.W = (int)d.W; p.Cin = (int)d.Cin; p.Ho = (int)d.Ho; p.Wo = (int)d.Wo; p.Cout = (int)d.Cout;
     p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad_t = d.pad_t; p.pad_l = d.pad_l; p.up = d.up;
     const int64_t M = d.B * d.Ho * d.Wo;
-    {   // the 256^2 GEMM kernel with a per-tap A gather (gemm.hip, CONV): whole tiles, Cin / 64 a power of two >= 2, at least UG_CONV256_MIN_TILES tiles
-        const int64_t ktp = d.Cin / 64, tiles = (M / 256) * (d.Cout / 256);
-        if (M % 256 == 0 && d.Cout % 256 == 0 && ktp >= 2 && (ktp & (ktp - 1)) == 0 && d.zero_page_bytes >= 2 * (d.Cin + 64) && d.B < 256 && d.H < 2048 && d.W < 2048 &&
-            d.Ho < 4096 && d.Wo < 4096 && ug_aligned(d.out, 16) && (!d.R || ug_aligned(d.R, 16)) && tiles >= ug_env_int("UG_CONV256_MIN_TILES", 192) && ug_env_int("UG_CONV256", 1)) {
-            ug_gemm_desc g = {};
-            g.A = d.x; g.lda = d.Cin; g.W = d.w; g.ldw = (int64_t)d.KH * d.KW * d.Cin; g.bias = d.bias; g.C = d.out; g.ldc = d.Cout; g.R = d.R; g.ldr = d.Cout;
-            g.M = M; g.N = d.Cout; g.K = g.ldw; g.groups = 1; g.alpha = 1.0f; g.epilogue = d.R ? UG_EPI_RES_SCALE : UG_EPI_BIAS;
-            UgConvGeom cv;
-            cv.zero = (const bf16_t*)d.zero_page; cv.H = (int)d.H; cv.W = (int)d.W; cv.Cin = (int)d.Cin; cv.Ho = (int)d.Ho; cv.Wo = (int)d.Wo; cv.KW = d.KW;
-            cv.stride = d.stride; cv.pad_t = d.pad_t; cv.pad_l = d.pad_l; cv.up = d.up; cv.ktp = (int)ktp;
-            const int rc2 = ug_gemm_launch_conv256(g, cv, (hipStream_t)stream);
-            if (rc2 != UG_ERR_UNSUPPORTED) return rc2;
-        }
+    if (ug_env_int("UG_CONV256", 1)) {   // the 256^2 GEMM kernel with a per-tap A gather (gemm.hip, CONV) where gemm_plan's conditions for this route hold
+        ug_gemm_desc g = {};
+        g.A = d.x; g.lda = d.Cin; g.W = d.w; g.ldw = (int64_t)d.KH * d.KW * d.Cin; g.bias = d.bias; g.C = d.out; g.ldc = d.Cout; g.R = d.R; g.ldr = d.Cout;
+        g.M = M; g.N = d.Cout; g.K = g.ldw; g.groups = 1; g.alpha = 1.0f; g.epilogue = d.R ? UG_EPI_RES_SCALE : UG_EPI_BIAS;
+        UgConvRoute r;
+        UgConvGeom& cv = r.geom;
+        cv.zero = (const bf16_t*)d.zero_page; cv.H = (int)d.H; cv.W = (int)d.W; cv.Cin = (int)d.Cin; cv.Ho = (int)d.Ho; cv.Wo = (int)d.Wo; cv.KW = d.KW;
+        cv.stride = d.stride; cv.pad_t = d.pad_t; cv.pad_l = d.pad_l; cv.up = d.up; cv.ktp = (int)(d.Cin / 64);
+        r.B = d.B; r.zero_bytes = d.zero_page_bytes; r.min_tiles = ug_env_int("UG_CONV256_MIN_TILES", 192);
+        const int rc2 = ug_gemm_conv256(g, r, (hipStream_t)stream);
+        if (rc2 != UG_ERR_UNSUPPORTED) return rc2;
     }
     // 256 x 128 tiles, three stages (Cout = 128 layers; convolutions with too few 256^2 tiles): whole tiles in M, at least one tile per CU pair
     [[maybe_unused]] constexpr int LDS_BIG = 3 * (256 + CBN) * CBK * 2, LDS_SMALL = 2 * (128 + CBN) * CBK * 2;

@@ -130,7 +130,7 @@ def qk_rope_fusable(M: int, N: int, until_n: int, dh: int, dtype: torch.dtype, *
     at least one full round of them (below that the dispatcher prefers the 128^2 kernel, which has no such epilogue). c_rpb / rope_rpb are the
     rows per batch of the launch's C row map and of its positions (0, the default: identity map, position = row): the epilogue needs the
     former a multiple of 256 (one scalar row map per tile) and the latter 0 or >= 256 (at most one position wrap per 16-row group) -
-    launch_qkrope refuses anything else.
+    gemm_check refuses anything else.
     UG_GEMM_FUSE_QKROPE=0 keeps the stand-alone ug_qk_rmsnorm_rope pass (A/B measurements)."""
     if os.environ.get("UG_GEMM_FUSE_QKROPE", "1") == "0":
         return False
