@@ -328,6 +328,15 @@ def test_moe_gate_bwd_random_shapes(gpu, seed):
     _check("gate d wg", dw, ref["dw"], c, var=var("dw"), mag=ref["dw_m"])
 
 
+def gelu_tanh_bwd_truth_and_tol(x, dy, dtype):
+    """-> (fp64 dx, per-element bound) of ug_gelu_tanh_bwd on x, dy as stored in dtype (tests/test_pointwise_gpu.py applies the same bound)"""
+    xd, dyd = x.double(), dy.double()
+    ref, mag = BR.gelu_tanh_bwd(xd, dyd)
+    # fp32: exp(-2u) of a rounded argument (relative error ~ |2u| u), the two added terms (16 ulps of their magnitudes), subnormal s below x = -9.9
+    two_u = (2 * 0.7978845608 * (xd + 0.044715 * xd ** 3)).abs()
+    return ref, BR.ABS_U * (1 + two_u) * mag + 2.0 ** -100 * dyd.abs() + (BR.bf16_ulp(ref) if dtype == BF else 2.0 ** -20 * ref.abs())
+
+
 @pytest.mark.parametrize("dtype", [BF, F32])
 @pytest.mark.parametrize("n,offset", [(1, 0), (7, 0), (8, 0), (9, 0), (4095, 0), (257 * 4096 + 3, 0), (4096, 1)])
 def test_gelu_tanh_bwd_sweep(gpu, dtype, n, offset):
@@ -342,11 +351,7 @@ def test_gelu_tanh_bwd_sweep(gpu, dtype, n, offset):
     x, dy = x.to(dtype), torch.randn(n + offset, generator=g).to(dtype)
     got = ops.gelu_tanh_bwd(x.to(gpu)[offset:], dy.to(gpu)[offset:])
     torch.cuda.synchronize()
-    xd, dyd = x[offset:].double(), dy[offset:].double()
-    ref, mag = BR.gelu_tanh_bwd(xd, dyd)
-    # fp32: exp(-2u) of a rounded argument (relative error ~ |2u| u), the two added terms (16 ulps of their magnitudes), subnormal s below x = -9.9
-    two_u = (2 * 0.7978845608 * (xd + 0.044715 * xd ** 3)).abs()
-    tol = BR.ABS_U * (1 + two_u) * mag + 2.0 ** -100 * dyd.abs() + (BR.bf16_ulp(ref) if dtype == BF else 2.0 ** -20 * ref.abs())
+    ref, tol = gelu_tanh_bwd_truth_and_tol(x[offset:], dy[offset:], dtype)
     _check_elem("gelu_tanh_bwd", got, ref, tol, dict(n=n, offset=offset, dtype=str(dtype)))
 
 

@@ -58,7 +58,7 @@ def build(force: bool = False, verbose: bool = False, probe: bool = False) -> st
 
 
 def _build_locked(force: bool, verbose: bool, probe: bool, objdir: str) -> str:
-    hdrs = [os.path.join(CSRC, "ug_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "attn_common.h"), HEADER]
+    hdrs = [os.path.join(CSRC, "ug_common.h"), os.path.join(CSRC, "pointwise.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "attn_common.h"), HEADER]
     sources = SOURCES + (PROBE_ONLY_SOURCES if probe else [])
     lib = PROBE_LIB if probe else LIB
     flags = (["-DUG_PROBE_BUILD", "-I", CSRC] if probe else []) + FLAGS

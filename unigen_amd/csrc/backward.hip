@@ -8,17 +8,11 @@
 //   ug_qk_rmsnorm_rope_bwd  RMSNorm(q|k) . weight, apply_rotary_emb  ->  d(q|k), and du (.) xhat for the weight gradient
 //   ug_row_lse, ug_attn_prob, ug_attn_dscore, ug_rowdot   softmax statistics and the elementwise steps of the attention backward
 // Every kernel is a template over the element type (bf16 product / fp32 verification twin); arithmetic in fp32, outputs rounded once.
-#include "ug_common.h"
-#include <algorithm>
+#include "pointwise.h"
 
 namespace {
 
-// gelu_tanh(x) = x / (1 + exp(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3); same formulation as the GEMM epilogue (gemm_epilogue.h)
-__device__ __forceinline__ float gelu_f(float x) {
-    constexpr float C0 = -2.3022081986f, C1 = C0 * 0.044715f;
-    const float u = x * fmaf(x * x, C1, C0);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u));
-}
+// derivative of gelu_tanh (ug_common.h: the forward here and the GEMM epilogue's GELU are that one function)
 __device__ __forceinline__ float gelu_grad_f(float x) {
     // y = x s, s = sigmoid(2u): dy/dx = s + x s (1 - s) 2 du/dx, 2 du/dx = 2 sqrt(2/pi) (1 + 3 * 0.044715 x^2)
     constexpr float K2 = 1.5957691216f;           // 2 sqrt(2/pi)
@@ -150,37 +144,18 @@ __global__ void gate_residual_kernel(const T* __restrict__ x, int64_t ldx, const
     }
 }
 
-// 8 elements per lane and access (16-byte loads / stores) when n and the bases allow (VEC); element-wise otherwise
-template <typename T, bool VEC>
-__global__ void gelu_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n) {
-    if constexpr (VEC) {
-        for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * blockDim.x * 8) {
-            float v[8];
-            ElemT<T>::load8(x + i, v);
+// y = gelu_tanh(x) and dx = dy gelu_tanh'(x): 8 elements per lane and access (16-byte loads / stores) when n and the bases allow, element-wise otherwise
+struct GeluTanh { static __device__ __forceinline__ float f(float x) { return gelu_tanh(x); } };
+template <typename T> struct GeluTanhBwd {
+    const T* x; const T* dy; T* dx; int64_t n;
+    template <int W> __device__ __forceinline__ void at(int64_t i) const {
+        float v[W], g[W];
+        pw_load<T, W>(x + i, v); pw_load<T, W>(dy + i, g);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = gelu_f(v[k]);
-            ElemT<T>::store8(y + i, v);
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-            ElemT<T>::st(y + i, gelu_f(ElemT<T>::ld(x + i)));
+        for (int k = 0; k < W; ++k) v[k] = g[k] * gelu_grad_f(v[k]);
+        pw_store<T, W>(dx + i, v);
     }
-}
-template <typename T, bool VEC>
-__global__ void gelu_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, int64_t n) {
-    if constexpr (VEC) {
-        for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * blockDim.x * 8) {
-            float v[8], g[8];
-            ElemT<T>::load8(x + i, v); ElemT<T>::load8(dy + i, g);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = g[k] * gelu_grad_f(v[k]);
-            ElemT<T>::store8(dx + i, v);
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-            ElemT<T>::st(dx + i, ElemT<T>::ld(dy + i) * gelu_grad_f(ElemT<T>::ld(x + i)));
-    }
-}
+};
 
 // y = xhat (1 + s) + sh, xhat = (x - mu) rstd:   g = dy (1 + s);  dx = rstd (g - mean(g) - xhat mean(g xhat));  d shift[sample] = sum_rows dy,
 // d scale[sample] = sum_rows dy xhat. Block (p, sample) takes the p-th chunk of the sample's rows; its W = ceil(D / 512) <= 8 waves share every row,
@@ -452,7 +427,7 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ a, in
     if (lane == 0) out[(int64_t)g * rows + r] = acc;
 }
 
-unsigned grid1d(int64_t n, int per) { return (unsigned)std::min<int64_t>((n + per - 1) / per, 65535 * 16); }
+constexpr int64_t GRID_CAP = 65535 * 16;        // of every grid-stride launch in this file
 
 template <typename T>
 int transpose_impl(const void* src, int64_t ld_src, int64_t src_bstride, void* dst, int64_t ld_dst, int64_t dst_bstride, int64_t batch, int64_t rows,
@@ -492,7 +467,7 @@ int colsum_impl(const void* a, int64_t lda, const void* b, int64_t ldb, void* ou
     dim3 grid((unsigned)((cols + 511) / 512), (unsigned)nchunks, (unsigned)groups);
     hipLaunchKernelGGL(colsum_partial_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (float*)workspace, rows_per_group,
                        (int)cols, nchunks);
-    hipLaunchKernelGGL(colsum_final_kernel<T>, dim3(grid1d(groups * cols, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, (T*)out, ldo, (int)cols,
+    hipLaunchKernelGGL(colsum_final_kernel<T>, dim3(ug_grid1d(groups * cols, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, (T*)out, ldo, (int)cols,
                        nchunks, (int)groups, alpha);
     UG_CHECK_LAUNCH("ug_colsum");
     return UG_OK;
@@ -591,16 +566,14 @@ int gelu_impl(const void* x, const void* dy, void* out, int64_t n, ug_stream_t s
     if (n == 0) return UG_OK;
     UG_REQUIRE(x && out && n > 0, UG_ERR_BAD_SHAPE, "ug_gelu_tanh: bad arguments");
     const bool vec = n % 8 == 0 && ug_aligned(x, 16) && ug_aligned(out, 16) && (!dy || ug_aligned(dy, 16));
-    const dim3 grid(grid1d(n, 256 * 8 * (vec ? 2 : 1)));
-    if (dy) {
-        if (vec) hipLaunchKernelGGL((gelu_bwd_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy, (T*)out, n);
-        else hipLaunchKernelGGL((gelu_bwd_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy, (T*)out, n);
-    } else {
-        if (vec) hipLaunchKernelGGL((gelu_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)out, n);
-        else hipLaunchKernelGGL((gelu_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)out, n);
-    }
-    UG_CHECK_LAUNCH("ug_gelu_tanh");
-    return UG_OK;
+    const unsigned grid = ug_grid1d(n, 256 * 8 * (vec ? 2 : 1), GRID_CAP);        // two chunks per thread where it moves chunks
+    using Fwd = PwMap<T, GeluTanh>;
+    using Bwd = GeluTanhBwd<T>;
+    const char* who = "ug_gelu_tanh";
+    const T *xp = (const T*)x, *gp = (const T*)dy;
+    T* op = (T*)out;
+    if (dy) return vec ? pointwise_launch<T, Bwd, PwLoop::Elems, 8>(who, grid, stream, xp, gp, op, n) : pointwise_launch<T, Bwd, PwLoop::Elems, 1>(who, grid, stream, xp, gp, op, n);
+    return vec ? pointwise_launch<T, Fwd, PwLoop::Elems, 8>(who, grid, stream, xp, op, n) : pointwise_launch<T, Fwd, PwLoop::Elems, 1>(who, grid, stream, xp, op, n);
 }
 template <typename T>
 int moe_gate_bwd_impl(const float* gates, const float* dgates, const void* x, const void* c, int64_t ld, const void* wg, int64_t S, int64_t D, int32_t E,
@@ -625,7 +598,7 @@ int gate_residual_impl(const void* x, int64_t ldx, const void* a, int64_t lda, c
                "ug_gate_residual: bad arguments");
     UG_REQUIRE(D % 8 == 0 && lda % 8 == 0 && ldy % 8 == 0 && gate_ld % 8 == 0 && (!x || ldx % 8 == 0) && ug_aligned(a, 16) && ug_aligned(gate, 16) &&
                ug_aligned(y, 16) && (!x || ug_aligned(x, 16)), UG_ERR_BAD_ALIGN, "ug_gate_residual: 16-byte alignment / multiples of 8 required");
-    hipLaunchKernelGGL(gate_residual_kernel<T>, dim3(grid1d(rows * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (const T*)a, lda,
+    hipLaunchKernelGGL(gate_residual_kernel<T>, dim3(ug_grid1d(rows * (D / 8), 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (const T*)a, lda,
                        (const T*)gate, gate_ld, rows_per_sample, (T*)y, ldy, rows, (int)(D / 8));
     UG_CHECK_LAUNCH("ug_gate_residual");
     return UG_OK;
@@ -694,7 +667,7 @@ int attn_prob_impl(const float* S, int64_t ld_s, const float* lse, void* P, int6
     if (rows == 0) return UG_OK;
     UG_REQUIRE(S && lse && P && rows > 0 && cols > 0 && valid_cols > 0 && valid_cols <= cols && ld_s >= cols && ld_p >= cols, UG_ERR_BAD_SHAPE,
                "ug_attn_prob: bad arguments");
-    hipLaunchKernelGGL(attn_prob_kernel<T>, dim3(grid1d(rows * cols, 256 * 8)), dim3(256), 0, (hipStream_t)stream, S, ld_s, lse, (T*)P, ld_p, rows, (int)cols,
+    hipLaunchKernelGGL(attn_prob_kernel<T>, dim3(ug_grid1d(rows * cols, 256 * 8, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, S, ld_s, lse, (T*)P, ld_p, rows, (int)cols,
                        (int)valid_cols, scale);
     UG_CHECK_LAUNCH("ug_attn_prob");
     return UG_OK;
@@ -704,7 +677,7 @@ int attn_dscore_impl(const void* P, int64_t ld_p, const float* dP, int64_t ld_dp
                      float scale, ug_stream_t stream) {
     if (rows == 0) return UG_OK;
     UG_REQUIRE(P && dP && delta && dS && rows > 0 && cols > 0 && ld_p >= cols && ld_dp >= cols && ld_ds >= cols, UG_ERR_BAD_SHAPE, "ug_attn_dscore: bad arguments");
-    hipLaunchKernelGGL(attn_dscore_kernel<T>, dim3(grid1d(rows * cols, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (const T*)P, ld_p, dP, ld_dp, delta, (T*)dS,
+    hipLaunchKernelGGL(attn_dscore_kernel<T>, dim3(ug_grid1d(rows * cols, 256 * 8, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, (const T*)P, ld_p, dP, ld_dp, delta, (T*)dS,
                        ld_ds, rows, (int)cols, scale);
     UG_CHECK_LAUNCH("ug_attn_dscore");
     return UG_OK;

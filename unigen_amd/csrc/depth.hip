@@ -10,25 +10,7 @@
 //   ug_minmax_to_u8          per-image (d - min) / (max - min) * 255 -> uint8, numpy's float32 order of operations
 // Activations are NHWC; all kernels are bandwidth-bound on small tensors: a lane moves 8 channels (16 bytes of bf16) when the bases and leading
 // dimensions allow it (`vec`, decided on the host) and single elements otherwise. -ffp-contract=off: every product and sum rounds on its own.
-#include "ug_common.h"
-
-static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline unsigned grid1d(int64_t n, int per_block) { return (unsigned)cdiv64(n, per_block); }
-
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float* f, bool vec) {
-    if (vec) ElemT<T>::load8(p, f);
-    else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = ElemT<T>::ld(p + j);
-    }
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, const float* f, bool vec) {
-    if (vec) ElemT<T>::store8(p, f);
-    else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ElemT<T>::st(p + j, f[j]);
-    }
-}
+#include "pointwise.h"
 
 // ---- uint8 NHWC -> patch rows [B * ph * pw][Kp]: column c P^2 + ky P + kx = ((float)(v * rescale) - mean[c]) / std[c] ------------------------------
 // One workgroup per patch row, a lane makes 8 consecutive columns. The image bytes of a patch are read once each (3 P^2 of them per row).
@@ -55,20 +37,22 @@ __global__ __launch_bounds__(128) void u8_to_patches_kernel(const uint8_t* __res
             }
             f[j] = v;
         }
-        st8<T>(out + row * ldo + c0, f, vec != 0);
+        ElemT<T>::store8(out + row * ldo + c0, f, vec != 0);
     }
 }
 
 // ---- ReLU over n contiguous elements, 8 per lane: x < 0 ? +0 : x, so NaN and -0 pass through as in torch.relu (fmaxf would launder a NaN into 0) ----
-template <typename T> __global__ __launch_bounds__(256) void relu_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8, int vec) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    float f[8];
-    ld8<T>(x + i * 8, f, vec != 0);
+template <typename T> struct Relu {
+    const T* x; T* y; int64_t n; int vec;
+    template <int W> __device__ __forceinline__ void at(int64_t i) const {
+        static_assert(W == 8, "ug_relu moves whole chunks; a base off 16 bytes takes the guarded accesses");
+        float f[8];
+        ElemT<T>::load8(x + i, f, vec != 0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = f[j] < 0.0f ? 0.0f : f[j];
-    st8<T>(y + i * 8, f, vec != 0);
-}
+        for (int j = 0; j < 8; ++j) f[j] = f[j] < 0.0f ? 0.0f : f[j];
+        ElemT<T>::store8(y + i, f, vec != 0);
+    }
+};
 
 // ---- ConvTranspose2d(k = s = f), second half: out[b][y f + ky][x f + kx][co] = rnd(prod[(b, y, x)][(ky f + kx) Cout + co] + bias[co]), pad = 0 ----
 // A lane makes 8 channels of one output pixel.
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(256) void deconv_scatter_kernel(const float* __rest
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = c0 + j < Cout ? p[j] + ElemT<T>::ld(bias + c0 + j) : 0.0f;
     }
-    st8<T>(out + pix * Cp + c0, v, vec != 0);
+    ElemT<T>::store8(out + pix * Cp + c0, v, vec != 0);
 }
 
 // ---- F.interpolate(mode="bilinear"): torch's area_pixel_compute_source_index in fp32, one rounding at the store ---------------------------------------
@@ -123,13 +107,13 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ x, 
     lin_src(ox, sw, align, W, x0, x1, wx0, wx1);
     const T* base = x + b * H * W * C + c0;
     float a[8], bq[8], c[8], d[8], r[8];
-    ld8<T>(base + ((int64_t)y0 * W + x0) * C, a, vec != 0);
-    ld8<T>(base + ((int64_t)y0 * W + x1) * C, bq, vec != 0);
-    ld8<T>(base + ((int64_t)y1 * W + x0) * C, c, vec != 0);
-    ld8<T>(base + ((int64_t)y1 * W + x1) * C, d, vec != 0);
+    ElemT<T>::load8(base + ((int64_t)y0 * W + x0) * C, a, vec != 0);
+    ElemT<T>::load8(base + ((int64_t)y0 * W + x1) * C, bq, vec != 0);
+    ElemT<T>::load8(base + ((int64_t)y1 * W + x0) * C, c, vec != 0);
+    ElemT<T>::load8(base + ((int64_t)y1 * W + x1) * C, d, vec != 0);
 #pragma unroll
     for (int j = 0; j < 8; ++j) r[j] = hy0 * (wx0 * a[j] + wx1 * bq[j]) + hy1 * (wx0 * c[j] + wx1 * d[j]);
-    st8<T>(out + pix * C + c0, r, vec != 0);
+    ElemT<T>::store8(out + pix * C + c0, r, vec != 0);
 }
 
 // ---- head: out[pix] = act(rnd(bias + sum_c w[c] relu(x[pix][c]))) * max_depth, fp32. Four lanes share a pixel, 8 channels per lane and step -------------
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(256) void depth_head_out_kernel(const T* __restrict
     if (pix < npix) {
         for (int c0 = sub * 8; c0 < C; c0 += 32) {
             float f[8], g[8];
-            if (c0 + 8 <= C) { ld8<T>(x + pix * Cp + c0, f, vec != 0); ld8<T>(w + c0, g, vec != 0); }
+            if (c0 + 8 <= C) { ElemT<T>::load8(x + pix * Cp + c0, f, vec != 0); ElemT<T>::load8(w + c0, g, vec != 0); }
             else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { const bool ok = c0 + j < C; f[j] = ok ? ElemT<T>::ld(x + pix * Cp + c0 + j) : 0.0f; g[j] = ok ? ElemT<T>::ld(w + c0 + j) : 0.0f; }
@@ -283,9 +267,7 @@ template <typename T> static int relu_impl(const void* x, void* y, int64_t n, ug
     UG_REQUIRE(x && y && n >= 0 && n % 8 == 0 && n / 8 < (1ll << 31) * 256, UG_ERR_BAD_SHAPE, "ug_relu: n=%lld must be a non-negative multiple of 8", (long long)n);
     if (n == 0) return UG_OK;
     const int vec = ug_aligned(x, 16) && ug_aligned(y, 16);
-    hipLaunchKernelGGL(relu_kernel<T>, dim3(grid1d(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n / 8, vec);
-    UG_CHECK_LAUNCH("ug_relu");
-    return UG_OK;
+    return pointwise_launch<T, Relu<T>, PwLoop::One>("ug_relu", ug_grid1d(n / 8, 256), stream, (const T*)x, (T*)y, n / 8, vec);
 }
 UG_TWINS(ug_relu, relu_impl, (const void* x, void* y, int64_t n, ug_stream_t stream), (x, y, n, stream))
 
@@ -297,9 +279,9 @@ static int deconv_scatter_impl(const float* prod, int64_t ld_prod, const void* b
                UG_ERR_BAD_SHAPE, "ug_deconv_scatter_nhwc: bad arguments (B=%lld h=%lld w=%lld f=%d Cout=%lld Cp=%lld ld_prod=%lld; Cp a multiple of 8, ld_prod >= f f Cout)",
                (long long)B, (long long)h, (long long)w, f, (long long)Cout, (long long)Cp, (long long)ld_prod);
     const int64_t npix = B * h * f * w * f, n = npix * (Cp / 8);
-    UG_REQUIRE(cdiv64(n, 256) < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_deconv_scatter_nhwc: too many elements");
+    UG_REQUIRE(ug_cdiv(n, 256) < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_deconv_scatter_nhwc: too many elements");
     const int vec = ug_aligned(prod, 16) && ld_prod % 4 == 0 && Cout % 8 == 0 && ug_aligned(bias, 16) && ug_aligned(out, 16);
-    hipLaunchKernelGGL(deconv_scatter_kernel<T>, dim3(grid1d(n, 256)), dim3(256), 0, (hipStream_t)stream, prod, ld_prod, (const T*)bias, (T*)out, npix, (int)h, (int)w,
+    hipLaunchKernelGGL(deconv_scatter_kernel<T>, dim3(ug_grid1d(n, 256)), dim3(256), 0, (hipStream_t)stream, prod, ld_prod, (const T*)bias, (T*)out, npix, (int)h, (int)w,
                        (int)f, (int)Cout, (int)Cp, vec);
     UG_CHECK_LAUNCH("ug_deconv_scatter_nhwc");
     return UG_OK;
@@ -320,9 +302,9 @@ static int bilinear_impl(const void* x, int64_t B, int64_t H, int64_t W, int64_t
                UG_ERR_BAD_SHAPE, "ug_bilinear_nhwc: bad arguments (B=%lld %lldx%lld -> %lldx%lld C=%lld; C a multiple of 8)", (long long)B, (long long)H, (long long)W,
                (long long)Ho, (long long)Wo, (long long)C);
     const int64_t npix = B * Ho * Wo, n = npix * (C / 8);
-    UG_REQUIRE(cdiv64(n, 256) < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_bilinear_nhwc: too many elements");
+    UG_REQUIRE(ug_cdiv(n, 256) < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_bilinear_nhwc: too many elements");
     const int vec = ug_aligned(x, 16) && ug_aligned(out, 16);
-    hipLaunchKernelGGL(bilinear_kernel<T>, dim3(grid1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (int)H, (int)W, (int)C, (T*)out, npix, (int)Ho, (int)Wo,
+    hipLaunchKernelGGL(bilinear_kernel<T>, dim3(ug_grid1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (int)H, (int)W, (int)C, (T*)out, npix, (int)Ho, (int)Wo,
                        lin_scale(H, Ho, align_corners), lin_scale(W, Wo, align_corners), align_corners ? 1 : 0, vec);
     UG_CHECK_LAUNCH("ug_bilinear_nhwc");
     return UG_OK;
@@ -337,7 +319,7 @@ static int depth_head_out_impl(const void* x, int64_t npix, int64_t C, int64_t C
     UG_REQUIRE(x && w && bias && out && npix >= 1 && C >= 1 && Cp >= C && C < (1 << 24) && Cp < (1 << 24) && npix < (1ll << 37), UG_ERR_BAD_SHAPE,
                "ug_depth_head_out: bad arguments (pixels=%lld C=%lld Cp=%lld)", (long long)npix, (long long)C, (long long)Cp);
     const int vec = ug_aligned(x, 16) && ug_aligned(w, 16) && (Cp * sizeof(T)) % 16 == 0;
-    hipLaunchKernelGGL(depth_head_out_kernel<T>, dim3(grid1d(npix * 4, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, npix, (int)C, (int)Cp, (const T*)w,
+    hipLaunchKernelGGL(depth_head_out_kernel<T>, dim3(ug_grid1d(npix * 4, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, npix, (int)C, (int)Cp, (const T*)w,
                        (const T*)bias, max_depth, metric ? 1 : 0, out, vec);
     UG_CHECK_LAUNCH("ug_depth_head_out");
     return UG_OK;
@@ -350,7 +332,7 @@ extern "C" int ug_bicubic_f32(const float* x, int64_t B, int64_t H, int64_t W, f
     UG_REQUIRE(x && out && B >= 1 && B < 65536 && H >= 1 && W >= 1 && Ho >= 1 && Ho < 65536 && Wo >= 1 && H < (1 << 24) && W < (1 << 24) && Wo < (1 << 24),
                UG_ERR_BAD_SHAPE, "ug_bicubic_f32: bad arguments (B=%lld %lldx%lld -> %lldx%lld; B, Ho < 65536)", (long long)B, (long long)H, (long long)W, (long long)Ho,
                (long long)Wo);
-    hipLaunchKernelGGL(bicubic_kernel, dim3(grid1d(Wo, 256), (unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, (int)H, (int)W, out, (int)Ho, (int)Wo,
+    hipLaunchKernelGGL(bicubic_kernel, dim3(ug_grid1d(Wo, 256), (unsigned)Ho, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, (int)H, (int)W, out, (int)Ho, (int)Wo,
                        lin_scale(H, Ho, 0), lin_scale(W, Wo, 0));
     UG_CHECK_LAUNCH("ug_bicubic_f32");
     return UG_OK;
@@ -363,7 +345,7 @@ extern "C" int ug_minmax_to_u8(const float* d, int64_t B, int64_t HW, uint8_t* o
                "ug_minmax_to_u8: bad arguments (B=%lld HW=%lld channels=%d; channels is 1 or 3)", (long long)B, (long long)HW, channels);
     UG_REQUIRE(workspace && ug_aligned(workspace, 8) && workspace_bytes >= ug_minmax_workspace_bytes(B, HW), UG_ERR_BAD_SHAPE,
                "ug_minmax_to_u8: the workspace is smaller than ug_minmax_workspace_bytes or not 8-byte aligned");
-    const int64_t nb = cdiv64(HW, 1024);
+    const int64_t nb = ug_cdiv(HW, 1024);
     UG_REQUIRE(nb < (1ll << 31), UG_ERR_UNSUPPORTED, "ug_minmax_to_u8: too many pixels");
     const int vec = HW % 4 == 0 && ug_aligned(d, 16) && ug_aligned(out, 4);
     hipLaunchKernelGGL(minmax_partial_kernel, dim3(MM_BLOCKS, (unsigned)B), dim3(256), 0, (hipStream_t)stream, d, HW, (float*)workspace, vec);

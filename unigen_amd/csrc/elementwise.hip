@@ -3,20 +3,12 @@
 // Rounding points mirror the reference's separate bf16 torch ops so results are comparable element-for-element.
 // Every kernel is a template over the element type (ElemT, ug_common.h): T = bf16_t is the product path, T = float the
 // fp32 VERIFICATION path (`ug_*_f32`: same code, fp32 storage, no intermediate rounding).
-#include "ug_common.h"
-#include <algorithm>
+#include "pointwise.h"
+#include <type_traits>
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
-    f[0] = bflo(v.x); f[1] = bfhi(v.x); f[2] = bflo(v.y); f[3] = bfhi(v.y);
-    f[4] = bflo(v.z); f[5] = bfhi(v.z); f[6] = bflo(v.w); f[7] = bfhi(v.w);
-}
-__device__ __forceinline__ u32x4 pack8(const float* f) {
-    u32x4 v;
-    v.x = pack2bf(f[0], f[1]); v.y = pack2bf(f[2], f[3]); v.z = pack2bf(f[4], f[5]); v.w = pack2bf(f[6], f[7]);
-    return v;
-}
+using B16 = ElemT<bf16_t>;      // the bf16-only kernels below work on packed registers: B16::unpack8 / pack8
 
 // ---------------------------------------------------------------------------------------------------------
 // AdaLayerNorm modulate: out = LN(x) * (1 + scale[b]) + shift[b].  One wave per row, row kept in registers.
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(256) void adaln_modulate_fast_kernel(
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < NCH; ++t) {
-        float f[8]; unpack8(xv[t], f);
+        float f[8]; B16::unpack8(xv[t], f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += f[e];
     }
@@ -135,7 +127,7 @@ __global__ __launch_bounds__(256) void adaln_modulate_fast_kernel(
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < NCH; ++t) {
-        float f[8]; unpack8(xv[t], f);
+        float f[8]; B16::unpack8(xv[t], f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; q += d * d; }
     }
@@ -146,14 +138,14 @@ __global__ __launch_bounds__(256) void adaln_modulate_fast_kernel(
 #pragma unroll
     for (int t = 0; t < NCH; ++t) {
         float f[8], fs[8], fc[8], o[8];
-        unpack8(xv[t], f); unpack8(shv[t], fs); unpack8(scv[t], fc);
+        B16::unpack8(xv[t], f); B16::unpack8(shv[t], fs); B16::unpack8(scv[t], fc);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float n = rbf((f[e] - mean) * rstd);     // LayerNorm output (bf16 tensor in the reference)
             const float s1 = rbf(1.0f + fc[e]);            // (1 + scale)
             o[e] = rbf(n * s1) + fs[e];                    // * then +, each a bf16 op in the reference (the + is rounded by the pack)
         }
-        *(u32x4*)(orow + t * 512) = pack8(o);
+        *(u32x4*)(orow + t * 512) = B16::pack8(o);
     }
 }
 
@@ -257,16 +249,16 @@ __global__ __launch_bounds__(256) void small_linear_kernel(
         const int m = i / nchunk, c = i - m * nchunk;
         float f[8];
         if (m < M) {
-            unpack8(*(const u32x4*)(x + (int64_t)m * ldx + c * 8), f);
+            B16::unpack8(*(const u32x4*)(x + (int64_t)m * ldx + c * 8), f);
             if (act_in == 1) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = f[e] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * f[e]));   // SiLU, rounded to bf16 below
+                for (int e = 0; e < 8; ++e) f[e] = silu<bf16_t>(f[e]);       // rounded to bf16 below
             }
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = 0.f;
         }
-        *(u32x4*)(xs + (int64_t)m * K + c * 8) = pack8(f);
+        *(u32x4*)(xs + (int64_t)m * K + c * 8) = B16::pack8(f);
     }
     __syncthreads();
     if (nbase >= N) return;
@@ -284,11 +276,11 @@ __global__ __launch_bounds__(256) void small_linear_kernel(
         }
         float xf[MT][8];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) unpack8(*(const u32x4*)(xs + (int64_t)m * K + c * 8), xf[m]);
+        for (int m = 0; m < MT; ++m) B16::unpack8(*(const u32x4*)(xs + (int64_t)m * K + c * 8), xf[m]);
 #pragma unroll
         for (int j = 0; j < SL_COLS_PER_WAVE; ++j) {
             float w[8];
-            unpack8(wq[j], w);
+            B16::unpack8(wq[j], w);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -359,18 +351,18 @@ __global__ void timestep_embed_kernel(const float* __restrict__ t, T* __restrict
 // step is a 0-dim fp32 tensor (an element difference of the scheduler's fp32 sigmas, on the model's device) and model_output a bf16 tensor - torch's type
 // promotion gives the PRODUCT the dimensioned operand's dtype and casts BOTH operands to it: the step is rounded to bf16, the product is rounded to bf16, then
 // the fp32 add, then the cast back. (With FLUX-schnell's four steps dt = -0.25 and everything is exact; SD3's 28 shifted steps round.)
-template <typename T>
-__global__ void euler_step_kernel(T* __restrict__ x, const T* __restrict__ v, float dt, int64_t nchunk) {
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * blockDim.x) {
-        float a[8], b[8];
+template <typename T> struct EulerStep {
+    T* x; const T* v; float dt; int64_t n;
+    template <int W> __device__ __forceinline__ void at(int64_t i) const {
+        float a[W], b[W];
         const float dtr = ElemT<T>::rnd(dt);
-        ElemT<T>::load8(x + c * 8, a);
-        ElemT<T>::load8(v + c * 8, b);
+        pw_load<T, W>(x + i, a);
+        pw_load<T, W>(v + i, b);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = a[e] + ElemT<T>::rnd(dtr * b[e]);
-        ElemT<T>::store8(x + c * 8, a);
+        for (int e = 0; e < W; ++e) a[e] = a[e] + ElemT<T>::rnd(dtr * b[e]);
+        pw_store<T, W>(x + i, a);
     }
-}
+};
 
 template <typename T>
 __global__ void add_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
@@ -387,18 +379,19 @@ __global__ void add_kernel(const T* __restrict__ a, int64_t lda, const T* __rest
     }
 }
 
-template <typename T>
-__global__ void cfg_combine_kernel(const T* __restrict__ u, const T* __restrict__ t, float gs, T* __restrict__ out, int64_t nchunk) {
-    using E = ElemT<T>;
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * blockDim.x) {
-        float a[8], b[8];
-        E::load8(u + c * 8, a);
-        E::load8(t + c * 8, b);
+// classifier-free guidance: out = uncond + rnd(gs * rnd(text - uncond)), torch's three bf16 ops
+template <typename T> struct CfgCombine {
+    const T* u; const T* t; float gs; T* out; int64_t n;
+    template <int W> __device__ __forceinline__ void at(int64_t i) const {
+        using E = ElemT<T>;
+        float a[W], b[W];
+        pw_load<T, W>(u + i, a);
+        pw_load<T, W>(t + i, b);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = a[e] + E::rnd(gs * E::rnd(b[e] - a[e]));
-        E::store8(out + c * 8, a);
+        for (int e = 0; e < W; ++e) a[e] = a[e] + E::rnd(gs * E::rnd(b[e] - a[e]));
+        pw_store<T, W>(out + i, a);
     }
-}
+};
 
 template <typename T>
 __global__ void add_rowbcast_f32_kernel(T* __restrict__ x, int64_t ldx, const float* __restrict__ t, int64_t ldt, int64_t rows,
@@ -469,12 +462,8 @@ int cfg_combine_impl(const void* uncond, const void* text, float guidance_scale,
     if (n == 0) return UG_OK;
     UG_REQUIRE(uncond && text && out && n > 0 && n % 8 == 0 && ug_aligned(uncond, 16) && ug_aligned(text, 16) && ug_aligned(out, 16),
                UG_ERR_BAD_ALIGN, "ug_cfg_combine: n must be a multiple of 8 and pointers 16-byte aligned");
-    const int64_t nchunk = n / 8;
-    const unsigned grid = (unsigned)std::min<int64_t>((nchunk + 255) / 256, 2048);
-    hipLaunchKernelGGL(cfg_combine_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)uncond, (const T*)text,
-                       guidance_scale, (T*)out, nchunk);
-    UG_CHECK_LAUNCH("ug_cfg_combine");
-    return UG_OK;
+    return pointwise_launch<T, CfgCombine<T>, PwLoop::Chunks>("ug_cfg_combine", ug_grid1d(n / 8, 256, 2048), stream, (const T*)uncond, (const T*)text, guidance_scale,
+                                                               (T*)out, n / 8);
 }
 
 template <typename T>
@@ -484,7 +473,7 @@ int add_rowbcast_impl(void* x, int64_t ldx, const float* table, int64_t ldt, int
     UG_REQUIRE(D % 8 == 0 && ldx % 8 == 0 && ldt % 4 == 0 && ug_aligned(x, 16) && ug_aligned(table, 16), UG_ERR_BAD_ALIGN,
                "ug_add_rowbcast_f32: 16-byte alignment required");
     const int64_t total = rows * (D / 8);
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 2048);
+    const unsigned grid = ug_grid1d(total, 256, 2048);
     hipLaunchKernelGGL(add_rowbcast_f32_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)x, ldx, table, ldt, rows, rows_per_batch, (int)(D / 8));
     UG_CHECK_LAUNCH("ug_add_rowbcast_f32");
     return UG_OK;
@@ -493,7 +482,7 @@ int add_rowbcast_impl(void* x, int64_t ldx, const float* table, int64_t ldt, int
 // ug_gather_rows (both element types: leading dimensions in multiples of 8, idx and the leading dimensions' size taken on trust, as ever) and
 // ug_gather_rows_scaled (16-byte rows per element type, idx 4-byte aligned, leading dimensions at least W)
 template <typename T, bool SCALED>
-int gather_rows_impl(const char* who, const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
+int gather_rows_impl(std::bool_constant<SCALED>, const char* who, const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
                      ug_stream_t stream) {
     if (n == 0 || W == 0) return UG_OK;
     UG_REQUIRE(src && idx && out && n > 0 && W > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
@@ -502,7 +491,7 @@ int gather_rows_impl(const char* who, const void* src, int64_t ld_src, const int
     UG_REQUIRE(W % 8 == 0 && ld_src % ldm == 0 && ld_out % ldm == 0 && ug_aligned(src, 16) && ug_aligned(out, 16) && (!SCALED || ug_aligned(idx, 4)),
                UG_ERR_BAD_ALIGN, "%s: W must be a multiple of 8 and rows 16-byte aligned", who);
     const int64_t total = n * (W / 8);
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    const unsigned grid = ug_grid1d(total, 256, 4096);
     hipLaunchKernelGGL((gather_rows_kernel<T, SCALED>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, ld_src, idx, (T*)out, ld_out, n,
                        (int)(W / 8), scale);
     UG_CHECK_LAUNCH(who);
@@ -585,11 +574,7 @@ int euler_step_impl(void* x, const void* v, float dt, int64_t n, ug_stream_t str
     if (n == 0) return UG_OK;
     UG_REQUIRE(x && v && n > 0 && n % 8 == 0 && ug_aligned(x, 16) && ug_aligned(v, 16), UG_ERR_BAD_ALIGN,
                "ug_euler_step: n must be a multiple of 8 and pointers 16-byte aligned");
-    const int64_t nchunk = n / 8;
-    const unsigned grid = (unsigned)std::min<int64_t>((nchunk + 255) / 256, 2048);
-    hipLaunchKernelGGL(euler_step_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)x, (const T*)v, dt, nchunk);
-    UG_CHECK_LAUNCH("ug_euler_step");
-    return UG_OK;
+    return pointwise_launch<T, EulerStep<T>, PwLoop::Chunks>("ug_euler_step", ug_grid1d(n / 8, 256, 2048), stream, (T*)x, (const T*)v, dt, n / 8);
 }
 
 template <typename T>
@@ -599,20 +584,20 @@ int add_impl(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, 
     UG_REQUIRE(D % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldo % 8 == 0 && ug_aligned(a, 16) && ug_aligned(b, 16) && ug_aligned(out, 16),
                UG_ERR_BAD_ALIGN, "ug_add: 16-byte alignment required");
     const int64_t total = rows * (D / 8);
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 2048);
+    const unsigned grid = ug_grid1d(total, 256, 2048);
     hipLaunchKernelGGL(add_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (T*)out, ldo, rows, (int)(D / 8));
     UG_CHECK_LAUNCH("ug_add");
     return UG_OK;
 }
 
 template <typename T, bool PACK>
-int pack_latents_impl(const void* src, void* dst, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t stream) {
+int pack_latents_impl(std::bool_constant<PACK>, const void* src, void* dst, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t stream) {
     if (B == 0) return UG_OK;
     UG_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, UG_ERR_BAD_SHAPE,
                "ug_pack_latents: need [B, C, H, W] with even H and W");
     UG_REQUIRE(B * C * H * W < (1ll << 40) && H < (1 << 20) && W < (1 << 20) && C < (1 << 20) && B < (1 << 20), UG_ERR_UNSUPPORTED, "ug_pack_latents: too large");
     const int64_t total = B * C * H * W;
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+    const unsigned grid = ug_grid1d(total, 256, 4096);
     hipLaunchKernelGGL((pack_latents_kernel<T, PACK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, (int)B, (int)C, (int)H, (int)W);
     UG_CHECK_LAUNCH("ug_pack_latents");
     return UG_OK;
@@ -620,56 +605,23 @@ int pack_latents_impl(const void* src, void* dst, int64_t B, int64_t C, int64_t 
 
 }  // namespace
 
-extern "C" int ug_cfg_combine(const void* u, const void* t, float gs, void* out, int64_t n, ug_stream_t s) { return cfg_combine_impl<bf16_t>(u, t, gs, out, n, s); }
-extern "C" int ug_cfg_combine_f32(const void* u, const void* t, float gs, void* out, int64_t n, ug_stream_t s) { return cfg_combine_impl<float>(u, t, gs, out, n, s); }
-
-extern "C" int ug_add_rowbcast_f32(void* x, int64_t ldx, const float* table, int64_t ldt, int64_t rows, int64_t rpb, int64_t D, ug_stream_t s) {
-    return add_rowbcast_impl<bf16_t>(x, ldx, table, ldt, rows, rpb, D, s);
-}
-extern "C" int ug_add_rowbcast_f32_f32(void* x, int64_t ldx, const float* table, int64_t ldt, int64_t rows, int64_t rpb, int64_t D, ug_stream_t s) {
-    return add_rowbcast_impl<float>(x, ldx, table, ldt, rows, rpb, D, s);
-}
-
-extern "C" int ug_gather_rows(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t s) {
-    return gather_rows_impl<bf16_t, false>("ug_gather_rows", src, ld_src, idx, out, ld_out, n, W, 1.0f, s);
-}
-extern "C" int ug_gather_rows_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t s) {
-    return gather_rows_impl<float, false>("ug_gather_rows", src, ld_src, idx, out, ld_out, n, W, 1.0f, s);       // the message names the family, as ever
-}
-extern "C" int ug_gather_rows_scaled(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
-                                     ug_stream_t s) {
-    return gather_rows_impl<bf16_t, true>(__func__, src, ld_src, idx, out, ld_out, n, W, scale, s);
-}
-extern "C" int ug_gather_rows_scaled_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
-                                         ug_stream_t s) {
-    return gather_rows_impl<float, true>(__func__, src, ld_src, idx, out, ld_out, n, W, scale, s);
-}
-
-extern "C" int ug_adaln_modulate(const void* x, int64_t ldx, int64_t x_rpb, int64_t x_bstride, const void* shift,
-                                 const void* scale, int64_t mod_ld, int64_t rows_per_sample, void* out, int64_t ldo,
-                                 int64_t rows, int64_t D, float eps, ug_stream_t stream) {
-    return adaln_modulate_impl<bf16_t>(x, ldx, x_rpb, x_bstride, shift, scale, mod_ld, rows_per_sample, out, ldo, rows, D, eps, stream);
-}
-extern "C" int ug_adaln_modulate_f32(const void* x, int64_t ldx, int64_t x_rpb, int64_t x_bstride, const void* shift,
-                                     const void* scale, int64_t mod_ld, int64_t rows_per_sample, void* out, int64_t ldo,
-                                     int64_t rows, int64_t D, float eps, ug_stream_t stream) {
-    return adaln_modulate_impl<float>(x, ldx, x_rpb, x_bstride, shift, scale, mod_ld, rows_per_sample, out, ldo, rows, D, eps, stream);
-}
-
-extern "C" int ug_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t batches, int64_t rows_per_batch, int64_t batch_stride_rows,
-                                  int64_t pos_offset, int64_t q_off, int64_t k_off, int32_t heads, int32_t dh, const void* wq_a, const void* wk_a,
-                                  const void* wq_b, const void* wk_b, int64_t split, const float* cos_tab,
-                                  const float* sin_tab, float eps, ug_stream_t stream) {
-    return qk_rmsnorm_rope_impl<bf16_t>(buf, ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh, wq_a, wk_a, wq_b, wk_b,
-                                        split, cos_tab, sin_tab, eps, stream);
-}
-extern "C" int ug_qk_rmsnorm_rope_f32(void* buf, int64_t ld, int64_t batches, int64_t rows_per_batch, int64_t batch_stride_rows,
-                                      int64_t pos_offset, int64_t q_off, int64_t k_off, int32_t heads, int32_t dh, const void* wq_a, const void* wk_a,
-                                      const void* wq_b, const void* wk_b, int64_t split, const float* cos_tab,
-                                      const float* sin_tab, float eps, ug_stream_t stream) {
-    return qk_rmsnorm_rope_impl<float>(buf, ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh, wq_a, wk_a, wq_b, wk_b,
-                                       split, cos_tab, sin_tab, eps, stream);
-}
+UG_TWINS(ug_cfg_combine, cfg_combine_impl, (const void* u, const void* t, float gs, void* out, int64_t n, ug_stream_t s), (u, t, gs, out, n, s))
+UG_TWINS(ug_add_rowbcast_f32, add_rowbcast_impl, (void* x, int64_t ldx, const float* table, int64_t ldt, int64_t rows, int64_t rpb, int64_t D, ug_stream_t s),
+         (x, ldx, table, ldt, rows, rpb, D, s))
+UG_TWINS(ug_gather_rows, gather_rows_impl, (const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, ug_stream_t s),
+         (std::false_type{}, "ug_gather_rows", src, ld_src, idx, out, ld_out, n, W, 1.0f, s))       // the message names the family, as ever
+UG_TWINS(ug_gather_rows_scaled, gather_rows_impl,
+         (const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale, ug_stream_t s),
+         (std::true_type{}, __func__, src, ld_src, idx, out, ld_out, n, W, scale, s))
+UG_TWINS(ug_adaln_modulate, adaln_modulate_impl,
+         (const void* x, int64_t ldx, int64_t x_rpb, int64_t x_bstride, const void* shift, const void* scale, int64_t mod_ld, int64_t rows_per_sample, void* out,
+          int64_t ldo, int64_t rows, int64_t D, float eps, ug_stream_t stream),
+         (x, ldx, x_rpb, x_bstride, shift, scale, mod_ld, rows_per_sample, out, ldo, rows, D, eps, stream))
+UG_TWINS(ug_qk_rmsnorm_rope, qk_rmsnorm_rope_impl,
+         (void* buf, int64_t ld, int64_t batches, int64_t rows_per_batch, int64_t batch_stride_rows, int64_t pos_offset, int64_t q_off, int64_t k_off, int32_t heads,
+          int32_t dh, const void* wq_a, const void* wk_a, const void* wq_b, const void* wk_b, int64_t split, const float* cos_tab, const float* sin_tab, float eps,
+          ug_stream_t stream),
+         (buf, ld, batches, rows_per_batch, batch_stride_rows, pos_offset, q_off, k_off, heads, dh, wq_a, wk_a, wq_b, wk_b, split, cos_tab, sin_tab, eps, stream))
 
 extern "C" int ug_small_linear_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, const void* bias,
                                     const void* R, int64_t ldr, void* out, int64_t ldo, int64_t M, int64_t N, int64_t K,
@@ -711,11 +663,8 @@ extern "C" int ug_small_linear_f32(const void* x, int64_t ldx, const void* W, in
     return UG_OK;
 }
 
-extern "C" int ug_timestep_embed(const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t s) { return timestep_embed_impl<bf16_t>(t, out, ldo, B, dim, s); }
-extern "C" int ug_timestep_embed_f32(const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t s) { return timestep_embed_impl<float>(t, out, ldo, B, dim, s); }
-
-extern "C" int ug_euler_step(void* x, const void* v, float dt, int64_t n, ug_stream_t s) { return euler_step_impl<bf16_t>(x, v, dt, n, s); }
-extern "C" int ug_euler_step_f32(void* x, const void* v, float dt, int64_t n, ug_stream_t s) { return euler_step_impl<float>(x, v, dt, n, s); }
+UG_TWINS(ug_timestep_embed, timestep_embed_impl, (const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t s), (t, out, ldo, B, dim, s))
+UG_TWINS(ug_euler_step, euler_step_impl, (void* x, const void* v, float dt, int64_t n, ug_stream_t s), (x, v, dt, n, s))
 
 extern "C" int ug_add_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows, int64_t D, ug_stream_t s) {
     return add_impl<bf16_t>(a, lda, b, ldb, out, ldo, rows, D, s);
@@ -724,15 +673,7 @@ extern "C" int ug_add_f32(const void* a, int64_t lda, const void* b, int64_t ldb
     return add_impl<float>(a, lda, b, ldb, out, ldo, rows, D, s);
 }
 
-extern "C" int ug_pack_latents(const void* latents, void* packed, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s) {
-    return pack_latents_impl<bf16_t, true>(latents, packed, B, C, H, W, s);
-}
-extern "C" int ug_unpack_latents(const void* packed, void* latents, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s) {
-    return pack_latents_impl<bf16_t, false>(packed, latents, B, C, H, W, s);
-}
-extern "C" int ug_pack_latents_f32(const void* latents, void* packed, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s) {
-    return pack_latents_impl<float, true>(latents, packed, B, C, H, W, s);
-}
-extern "C" int ug_unpack_latents_f32(const void* packed, void* latents, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s) {
-    return pack_latents_impl<float, false>(packed, latents, B, C, H, W, s);
-}
+UG_TWINS(ug_pack_latents, pack_latents_impl, (const void* latents, void* packed, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s),
+         (std::true_type{}, latents, packed, B, C, H, W, s))
+UG_TWINS(ug_unpack_latents, pack_latents_impl, (const void* packed, void* latents, int64_t B, int64_t C, int64_t H, int64_t W, ug_stream_t s),
+         (std::false_type{}, packed, latents, B, C, H, W, s))

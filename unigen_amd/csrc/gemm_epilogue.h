@@ -61,16 +61,6 @@ __device__ __forceinline__ TileCoord tile_of_block(int bid, int nM, int nN, int 
     return t;
 }
 
-__device__ __forceinline__ float gelu_tanh(float x) {
-    // 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3)  ==  x / (1 + exp(-2u)): 3 multiplies/FMAs, v_exp_f32, add, v_rcp_f32, multiply
-    // (the textbook form with an IEEE division is ~24 VALU instructions per element; the epilogue is VALU-bound). No cancellation
-    // for x << 0, exp -> inf gives rcp -> 0 -> -0.
-    constexpr float C0 = -2.3022081986f;            // -2 sqrt(2/pi) log2(e)
-    constexpr float C1 = C0 * 0.044715f;
-    const float u = x * fmaf(x * x, C1, C0);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u));
-}
-
 __device__ __forceinline__ void load_bias4(const bf16_t* bias, int64_t n, float* bv) {
     bv[0] = bv[1] = bv[2] = bv[3] = 0.f;
     if (bias) {

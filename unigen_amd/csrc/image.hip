@@ -16,7 +16,6 @@
 typedef __attribute__((ext_vector_type(4))) short i16x4;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ unsigned byte_of(const u32x4& v, int j) { return (v[j >> 2] >> (8 * (j & 3))) & 255u; }
 
@@ -554,7 +553,7 @@ extern "C" int ug_canny_grad(const uint8_t* img, int64_t bstride, int64_t rstrid
     UG_REQUIRE((C == 1 || C == 3) && img_args_ok(img, bstride, rstride, B, H, W, C) && dx && dy && mag, UG_ERR_BAD_SHAPE,
                "ug_canny_grad: bad arguments (B=%lld H=%lld W=%lld C=%d; C is 1 or 3, strides cover a row / a sample)", (long long)B, (long long)H,
                (long long)W, C);
-    const dim3 grid((unsigned)cdiv64(W, CT_W), (unsigned)cdiv64(H, CT_H), (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, CT_W), (unsigned)ug_cdiv(H, CT_H), (unsigned)B);
     const int vin = strided_aligned(img, bstride, rstride, 4), vout = W % 4 == 0 && ug_aligned(dx, 8) && ug_aligned(dy, 8) && ug_aligned(mag, 16);
     if (C == 1) hipLaunchKernelGGL(canny_grad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, img, bstride, rstride, (int)H, (int)W, dx, dy, mag, vin, vout);
     else hipLaunchKernelGGL(canny_grad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, img, bstride, rstride, (int)H, (int)W, dx, dy, mag, vin, vout);
@@ -567,7 +566,7 @@ extern "C" int ug_canny_nms(const int16_t* dx, const int16_t* dy, const int32_t*
     UG_REQUIRE(dx && dy && mag && map && B >= 1 && H >= 1 && W >= 1 && B < 65536 && H < 65536 && W < (1 << 24), UG_ERR_BAD_SHAPE,
                "ug_canny_nms: bad arguments (B=%lld H=%lld W=%lld)", (long long)B, (long long)H, (long long)W);
     if (low > high) { const int32_t t = low; low = high; high = t; }
-    const dim3 grid((unsigned)cdiv64(W, CT_W), (unsigned)cdiv64(H, CT_H), (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, CT_W), (unsigned)ug_cdiv(H, CT_H), (unsigned)B);
     const int vec = W % 4 == 0 && ug_aligned(dx, 8) && ug_aligned(dy, 8) && ug_aligned(map, 4);
     hipLaunchKernelGGL(canny_nms_kernel, grid, dim3(256), 0, (hipStream_t)stream, dx, dy, mag, (int)H, (int)W, low, high, map, vec);
     UG_CHECK_LAUNCH("ug_canny_nms");
@@ -581,7 +580,7 @@ extern "C" int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W
     UG_REQUIRE(map && flag && img_args_ok(out, out_bstride, out_rstride, B, H, W, 1), UG_ERR_BAD_SHAPE,
                "ug_canny_hysteresis: bad arguments (B=%lld H=%lld W=%lld)", (long long)B, (long long)H, (long long)W);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)cdiv64(W, HT_W), (unsigned)cdiv64(H, HT_H), (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, HT_W), (unsigned)ug_cdiv(H, HT_H), (unsigned)B);
     const int vec = W % 4 == 0 && ug_aligned(map, 4);
     const int64_t bound = ug_canny_max_sweeps(H, W);
     int64_t n = 0;
@@ -597,7 +596,7 @@ extern "C" int ug_canny_hysteresis(uint8_t* map, int64_t B, int64_t H, int64_t W
         ++n;
     }
     UG_REQUIRE(!raised, UG_ERR_HIP, "ug_canny_hysteresis: no fixed point after %lld sweeps", (long long)n);
-    const dim3 fgrid((unsigned)cdiv64(W, 256 * 16), (unsigned)H, (unsigned)B);
+    const dim3 fgrid((unsigned)ug_cdiv(W, 256 * 16), (unsigned)H, (unsigned)B);
     hipLaunchKernelGGL(canny_final_kernel, fgrid, dim3(256), 0, s, map, (int)H, (int)W, out, out_bstride, out_rstride, (int)(W % 16 == 0 && ug_aligned(map, 16)),
                        (int)strided_aligned(out, out_bstride, out_rstride, 16));
     UG_CHECK_LAUNCH("ug_canny_hysteresis");
@@ -656,7 +655,7 @@ extern "C" int ug_img_resize_u8(const uint8_t* src, int64_t src_bstride, int64_t
     if (horiz) {
         uint8_t* hd = vert ? tmp : dst;
         const int64_t hdb = vert ? Hin * Wout * C : dst_bstride, hdr = vert ? Wout * C : dst_rstride;
-        const dim3 grid((unsigned)cdiv64(Wout, 256), (unsigned)Hin, (unsigned)B);
+        const dim3 grid((unsigned)ug_cdiv(Wout, 256), (unsigned)Hin, (unsigned)B);
         const int vin = strided_aligned(src, src_bstride, src_rstride, 4), vout = strided_aligned(hd, hdb, hdr, 4);
         if (C == 1) hipLaunchKernelGGL(resize_h_kernel<1>, grid, dim3(256), 0, s, src, src_bstride, src_rstride, (int)Win, hd, hdb, hdr, (int)Wout, xbounds, xcoef, (int)xk, vin, vout);
         else hipLaunchKernelGGL(resize_h_kernel<3>, grid, dim3(256), 0, s, src, src_bstride, src_rstride, (int)Win, hd, hdb, hdr, (int)Wout, xbounds, xcoef, (int)xk, vin, vout);
@@ -665,7 +664,7 @@ extern "C" int ug_img_resize_u8(const uint8_t* src, int64_t src_bstride, int64_t
     }
     if (vert) {
         const int64_t row_bytes = Wout * C;
-        const dim3 grid((unsigned)cdiv64(row_bytes, 256 * 16), (unsigned)Hout, (unsigned)B);
+        const dim3 grid((unsigned)ug_cdiv(row_bytes, 256 * 16), (unsigned)Hout, (unsigned)B);
         hipLaunchKernelGGL(resize_v_kernel, grid, dim3(256), 0, s, vsrc, vsb, vsr, (int)Hin, row_bytes, dst, dst_bstride, dst_rstride, ybounds, ycoef, (int)yk,
                            (int)strided_aligned(vsrc, vsb, vsr, 16), (int)strided_aligned(dst, dst_bstride, dst_rstride, 16));
         UG_CHECK_LAUNCH("ug_img_resize_u8");
@@ -677,7 +676,7 @@ extern "C" int ug_img_rgb_to_l(const uint8_t* src, int64_t src_bstride, int64_t 
                                int64_t dst_rstride, ug_stream_t stream) {
     UG_REQUIRE(img_args_ok(src, src_bstride, src_rstride, B, H, W, 3) && img_args_ok(dst, dst_bstride, dst_rstride, B, H, W, 1), UG_ERR_BAD_SHAPE,
                "ug_img_rgb_to_l: bad arguments (B=%lld H=%lld W=%lld)", (long long)B, (long long)H, (long long)W);
-    const dim3 grid((unsigned)cdiv64(W, 256 * 16), (unsigned)H, (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, 256 * 16), (unsigned)H, (unsigned)B);
     hipLaunchKernelGGL(rgb_to_l_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, src_bstride, src_rstride, (int)W, dst, dst_bstride, dst_rstride,
                        (int)strided_aligned(src, src_bstride, src_rstride, 16), (int)strided_aligned(dst, dst_bstride, dst_rstride, 16));
     UG_CHECK_LAUNCH("ug_img_rgb_to_l");
@@ -686,7 +685,7 @@ extern "C" int ug_img_rgb_to_l(const uint8_t* src, int64_t src_bstride, int64_t 
 
 template <typename T>
 static int u8_to_chw_launch(const uint8_t* src, int64_t sb, int64_t sr, int64_t B, int64_t H, int64_t W, int C, void* dst, int Cout, int normalize, hipStream_t s) {
-    const dim3 grid((unsigned)cdiv64(W, 256 * 4), (unsigned)H, (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, 256 * 4), (unsigned)H, (unsigned)B);
     const int vin = strided_aligned(src, sb, sr, 4), vout = W % 4 == 0 && ug_aligned(dst, 16);
     if (C == 1) hipLaunchKernelGGL((u8_to_chw_kernel<T, 1>), grid, dim3(256), 0, s, src, sb, sr, (int)H, (int)W, (T*)dst, Cout, normalize, vin, vout);
     else hipLaunchKernelGGL((u8_to_chw_kernel<T, 3>), grid, dim3(256), 0, s, src, sb, sr, (int)H, (int)W, (T*)dst, Cout, normalize, vin, vout);
@@ -707,7 +706,7 @@ extern "C" int ug_img_chw_to_u8(const void* src, int32_t src_dtype, int64_t B, i
     UG_REQUIRE(src && C >= 1 && C <= 4 && img_args_ok(dst, dst_bstride, dst_rstride, B, H, W, C) && (src_dtype == UG_DT_BF16 || src_dtype == UG_DT_F32),
                UG_ERR_BAD_SHAPE, "ug_img_chw_to_u8: bad arguments (B=%lld C=%d H=%lld W=%lld, dtype %d; 1 to 4 channels)", (long long)B, C, (long long)H,
                (long long)W, src_dtype);
-    const dim3 grid((unsigned)cdiv64(W, CU_SEG), (unsigned)H, (unsigned)B);
+    const dim3 grid((unsigned)ug_cdiv(W, CU_SEG), (unsigned)H, (unsigned)B);
     const int vout = strided_aligned(dst, dst_bstride, dst_rstride, 16);
     if (src_dtype == UG_DT_F32)
         hipLaunchKernelGGL(chw_to_u8_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, C, (int)H, (int)W, dst, dst_bstride, dst_rstride,
@@ -779,17 +778,17 @@ extern "C" int ug_img_box_blur_u8(const uint8_t* src, int64_t src_bstride, int64
             const int vin = strided_aligned(in, ib, ir, 4), vout = strided_aligned(out, ob, orow, 4);
             const int halo = a.per * (a.r + 1);
             if (!a.tile) {
-                const dim3 grid((unsigned)cdiv64(W * C, 256), (unsigned)H, (unsigned)B);
+                const dim3 grid((unsigned)ug_cdiv(W * C, 256), (unsigned)H, (unsigned)B);
                 hipLaunchKernelGGL(blur_direct_kernel, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, (int)C, out, ob, orow, a.vertical, a.r, (unsigned)a.ww,
                                    (unsigned)a.fw);
             } else if (a.vertical) {
                 const int th = BV_ROWS - 2 * halo < BV_TH_MAX ? BV_ROWS - 2 * halo : BV_TH_MAX;
-                const dim3 grid((unsigned)cdiv64(W * C, BV_WB), (unsigned)cdiv64(H, th), (unsigned)B);
+                const dim3 grid((unsigned)ug_cdiv(W * C, BV_WB), (unsigned)ug_cdiv(H, th), (unsigned)B);
                 hipLaunchKernelGGL(blur_v_kernel, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)(W * C), out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, th,
                                    vin, vout);
             } else {
                 const int nds = ((BH_TW + 2 * halo) * C + 12) / 4;
-                const dim3 grid((unsigned)cdiv64(W, BH_TW), (unsigned)cdiv64(H, BH_ROWS), (unsigned)B);
+                const dim3 grid((unsigned)ug_cdiv(W, BH_TW), (unsigned)ug_cdiv(H, BH_ROWS), (unsigned)B);
                 if (C == 1) hipLaunchKernelGGL(blur_h_kernel<1>, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, nds, vin, vout);
                 else hipLaunchKernelGGL(blur_h_kernel<3>, grid, dim3(256), 0, s, in, ib, ir, (int)H, (int)W, out, ob, orow, a.r, (unsigned)a.ww, (unsigned)a.fw, a.per, nds, vin, vout);
             }

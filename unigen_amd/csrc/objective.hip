@@ -281,30 +281,17 @@ int flow_loss_bwd_impl(const char* who, const void* pred, const void* target, co
 
 }  // namespace
 
-extern "C" int ug_flow_noise(const void* x, const void* noise, const float* u, const float* sigma_table, int64_t T, int32_t scheme, int32_t pack, int64_t B,
-                             int64_t C, int64_t H, int64_t W, void* noisy, void* target, float* sigma, float* timestep, float* weight, ug_stream_t s) {
-    return flow_noise_impl<bf16_t>("ug_flow_noise", x, noise, u, sigma_table, T, scheme, pack, B, C, H, W, noisy, target, sigma, timestep, weight, s);
-}
-extern "C" int ug_flow_noise_f32(const void* x, const void* noise, const float* u, const float* sigma_table, int64_t T, int32_t scheme, int32_t pack, int64_t B,
-                                 int64_t C, int64_t H, int64_t W, void* noisy, void* target, float* sigma, float* timestep, float* weight, ug_stream_t s) {
-    return flow_noise_impl<float>("ug_flow_noise_f32", x, noise, u, sigma_table, T, scheme, pack, B, C, H, W, noisy, target, sigma, timestep, weight, s);
-}
+UG_TWINS(ug_flow_noise, flow_noise_impl,
+         (const void* x, const void* noise, const float* u, const float* sigma_table, int64_t T, int32_t scheme, int32_t pack, int64_t B, int64_t C, int64_t H, int64_t W,
+          void* noisy, void* target, float* sigma, float* timestep, float* weight, ug_stream_t s),
+         (__func__, x, noise, u, sigma_table, T, scheme, pack, B, C, H, W, noisy, target, sigma, timestep, weight, s))
 
 extern "C" int64_t ug_flow_loss_workspace_bytes(int64_t B, int64_t n) { return (B > 0 ? B : 1) * (int64_t)loss_blocks(n > 0 ? n : 1) * (int64_t)sizeof(float); }
 
-extern "C" int ug_flow_loss(const void* pred, const void* target, const float* weight, int64_t B, int64_t n, float* loss_per_sample, float* loss,
-                            void* workspace, int64_t workspace_bytes, ug_stream_t s) {
-    return flow_loss_impl<bf16_t>("ug_flow_loss", pred, target, weight, B, n, loss_per_sample, loss, workspace, workspace_bytes, s);
-}
-extern "C" int ug_flow_loss_f32(const void* pred, const void* target, const float* weight, int64_t B, int64_t n, float* loss_per_sample, float* loss,
-                                void* workspace, int64_t workspace_bytes, ug_stream_t s) {
-    return flow_loss_impl<float>("ug_flow_loss_f32", pred, target, weight, B, n, loss_per_sample, loss, workspace, workspace_bytes, s);
-}
-
-extern "C" int ug_flow_loss_bwd(const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad, ug_stream_t s) {
-    return flow_loss_bwd_impl<bf16_t>("ug_flow_loss_bwd", pred, target, weight, gout, B, n, grad, s);
-}
-extern "C" int ug_flow_loss_bwd_f32(const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad,
-                                    ug_stream_t s) {
-    return flow_loss_bwd_impl<float>("ug_flow_loss_bwd_f32", pred, target, weight, gout, B, n, grad, s);
-}
+UG_TWINS(ug_flow_loss, flow_loss_impl,
+         (const void* pred, const void* target, const float* weight, int64_t B, int64_t n, float* loss_per_sample, float* loss, void* workspace, int64_t workspace_bytes,
+          ug_stream_t s),
+         (__func__, pred, target, weight, B, n, loss_per_sample, loss, workspace, workspace_bytes, s))
+UG_TWINS(ug_flow_loss_bwd, flow_loss_bwd_impl,
+         (const void* pred, const void* target, const float* weight, const float* gout, int64_t B, int64_t n, void* grad, ug_stream_t s),
+         (__func__, pred, target, weight, gout, B, n, grad, s))

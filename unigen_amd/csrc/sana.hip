@@ -226,11 +226,6 @@ constexpr int GT_W = 32;                         // image columns per workgroup
 constexpr int GT_ROWS = 16;                      // image rows per workgroup
 constexpr int GT_PX = GT_W + 2;                  // a ring row: the columns and one halo pixel either side
 
-template <typename T> __device__ __forceinline__ float silu_t(float x) {
-    if constexpr (ElemT<T>::kF32) return x / (1.0f + expf(-x));
-    else return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
-}
-
 template <typename T, int OCT>
 __global__ __launch_bounds__(GT_W * OCT) void glu_dwconv3x3_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ w9, const T* __restrict__ bias,
                                                                  T* __restrict__ out, int64_t ldo, int H, int W, int C, int xtiles) {
@@ -286,7 +281,7 @@ __global__ __launch_bounds__(GT_W * OCT) void glu_dwconv3x3_kernel(const T* __re
             if (it < ITEMS) {
                 float a[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) a[i] = silu_t<T>(stage[p][i]);
+                for (int i = 0; i < 8; ++i) a[i] = silu<T>(stage[p][i]);
                 E::store8(&ring[slot][it][0], a);
             }
         }
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(GT_W * OCT) void glu_dwconv3x3_kernel(const T* __re
             }
             float r[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) r[i] = E::rnd(av[i]) * E::rnd(silu_t<T>(E::rnd(ag[i])));
+            for (int i = 0; i < 8; ++i) r[i] = E::rnd(av[i]) * E::rnd(silu<T>(E::rnd(ag[i])));
             E::store8(orow, r);
         } else if (pad) {
             E::zero8(orow);
@@ -360,24 +355,12 @@ extern "C" int64_t ug_linear_attn_workspace_bytes(int64_t batches, int64_t heads
     return batches * heads * (la_chunks(N) + 1) * LA_STATE * (int64_t)sizeof(float);
 }
 
-#define UG_LA_PARAMS (const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride,          \
-                      const void* v, int64_t v_row_stride, int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride, int64_t batches, \
-                      int32_t heads, int64_t N, int32_t dh, void* workspace, ug_stream_t stream)
-extern "C" int ug_linear_attn UG_LA_PARAMS {
-    return linear_attn_impl<bf16_t>("ug_linear_attn", q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o,
-                                    o_row_stride, o_batch_stride, batches, heads, N, dh, workspace, stream);
-}
-extern "C" int ug_linear_attn_f32 UG_LA_PARAMS {
-    return linear_attn_impl<float>("ug_linear_attn_f32", q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o,
-                                   o_row_stride, o_batch_stride, batches, heads, N, dh, workspace, stream);
-}
-#undef UG_LA_PARAMS
-
-extern "C" int ug_glu_dwconv3x3(const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
-                                int64_t C, ug_stream_t stream) {
-    return glu_dwconv3x3_impl<bf16_t>("ug_glu_dwconv3x3", x, ldx, w9, bias, out, ldo, B, H, W, C, stream);
-}
-extern "C" int ug_glu_dwconv3x3_f32(const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
-                                    int64_t C, ug_stream_t stream) {
-    return glu_dwconv3x3_impl<float>("ug_glu_dwconv3x3_f32", x, ldx, w9, bias, out, ldo, B, H, W, C, stream);
-}
+UG_TWINS(ug_linear_attn, linear_attn_impl,
+         (const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride, int64_t k_batch_stride, const void* v, int64_t v_row_stride,
+          int64_t v_batch_stride, void* o, int64_t o_row_stride, int64_t o_batch_stride, int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace,
+          ug_stream_t stream),
+         (__func__, q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, v, v_row_stride, v_batch_stride, o, o_row_stride, o_batch_stride, batches, heads,
+          N, dh, workspace, stream))
+UG_TWINS(ug_glu_dwconv3x3, glu_dwconv3x3_impl,
+         (const void* x, int64_t ldx, const void* w9, const void* bias, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t C, ug_stream_t stream),
+         (__func__, x, ldx, w9, bias, out, ldo, B, H, W, C, stream))

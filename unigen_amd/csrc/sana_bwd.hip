@@ -306,17 +306,9 @@ int linear_attn_bwd_impl(const char* who, ug_view q, ug_view k, ug_view v, ug_vi
 // ---- GLU depthwise 3x3 ----
 constexpr int GB_SLAB = 256;                     // pixels per partial sum of dw9 / dbias
 
-template <typename T> __device__ __forceinline__ float sigmoid_b(float x) {
-    if constexpr (ElemT<T>::kF32) return 1.0f / (1.0f + expf(-x));
-    else return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
-}
-// the forward's silu_t, expression for expression: a, y and s must be the forward's bits
-template <typename T> __device__ __forceinline__ float silu_b(float x) {
-    if constexpr (ElemT<T>::kF32) return x / (1.0f + expf(-x));
-    else return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
-}
+// a, y and s must be the forward's bits: silu<T> (ug_common.h) is the function the forward calls
 template <typename T> __device__ __forceinline__ float dsilu_b(float x) {
-    const float s = sigmoid_b<T>(x);
+    const float s = sigmoid<T>(x);
     return s * (1.0f + x * (1.0f - s));
 }
 
@@ -348,7 +340,7 @@ __global__ __launch_bounds__(256) void glu_bwd_dy_kernel(const T* __restrict__ x
                 E::load8(xp, a);
                 E::load8(xp + C, g);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) { a[i] = E::rnd(silu_b<T>(a[i])); g[i] = E::rnd(silu_b<T>(g[i])); }
+                for (int i = 0; i < 8; ++i) { a[i] = E::rnd(silu<T>(a[i])); g[i] = E::rnd(silu<T>(g[i])); }
             } else {                                       // the convolution's zero padding acts on the activation
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { a[i] = 0.f; g[i] = 0.f; }
@@ -367,7 +359,7 @@ __global__ __launch_bounds__(256) void glu_bwd_dy_kernel(const T* __restrict__ x
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float yv = E::rnd(av[i]), yg = E::rnd(ag[i]);
-        const float s = E::rnd(silu_b<T>(yg));
+        const float s = E::rnd(silu<T>(yg));
         rv[i] = gd[i] * s;
         rg[i] = gd[i] * yv * dsilu_b<T>(yg);
     }
@@ -430,7 +422,7 @@ __global__ __launch_bounds__(64) void glu_bwd_dw_kernel(const T* __restrict__ x,
         float a[8], gc[8];
         E::load8(x + q * ldx + c, a);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = E::rnd(silu_b<T>(a[i]));
+        for (int i = 0; i < 8; ++i) a[i] = E::rnd(silu<T>(a[i]));
         E::load8(dy + q * 2 * C + c, gc);
 #pragma unroll
         for (int i = 0; i < 8; ++i) bacc[i] += gc[i];
@@ -527,12 +519,10 @@ extern "C" int64_t ug_linear_attn_bwd_workspace_bytes(int64_t batches, int64_t h
                        const float* state, void* dq, int64_t dq_row_stride, int64_t dq_batch_stride, void* dk, int64_t dk_row_stride, int64_t dk_batch_stride, \
                        void* dv, int64_t dv_row_stride, int64_t dv_batch_stride, int64_t batches, int32_t heads, int64_t N, int32_t dh, void* workspace,       \
                        int64_t workspace_bytes, ug_stream_t stream)
-#define UG_LAB_ARGS(who) (who, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), {dout, do_row_stride, do_batch_stride}, state, UG_VIEW(dq), UG_VIEW(dk), UG_VIEW(dv),      \
-                          batches, heads, N, dh, workspace, workspace_bytes, stream)
-extern "C" int ug_linear_attn_bwd UG_LAB_PARAMS { return linear_attn_bwd_impl<bf16_t> UG_LAB_ARGS("ug_linear_attn_bwd"); }
-extern "C" int ug_linear_attn_bwd_f32 UG_LAB_PARAMS { return linear_attn_bwd_impl<float> UG_LAB_ARGS("ug_linear_attn_bwd_f32"); }
+UG_TWINS(ug_linear_attn_bwd, linear_attn_bwd_impl, UG_LAB_PARAMS,
+         (__func__, UG_VIEW(q), UG_VIEW(k), UG_VIEW(v), {dout, do_row_stride, do_batch_stride}, state, UG_VIEW(dq), UG_VIEW(dk), UG_VIEW(dv), batches, heads, N, dh,
+          workspace, workspace_bytes, stream))
 #undef UG_LAB_PARAMS
-#undef UG_LAB_ARGS
 
 extern "C" int64_t ug_glu_dwconv3x3_bwd_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int32_t elem_bytes) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (elem_bytes != 2 && elem_bytes != 4)) return 0;

@@ -29,7 +29,7 @@
 // wholly above its own 32 rows' diagonal or behind its window. A row none of whose keys is live (every row of a sample whose kv_len is 0, and
 // with a window the padded rows from kv_len + window - 1 on) is written as zeros. K and V rows in [kv_len, L) are still read and enter the
 // products with a probability of zero: they must be finite.
-#include "ug_common.h"
+#include "pointwise.h"
 #include <math.h>
 #include <type_traits>
 
@@ -341,11 +341,6 @@ __global__ __launch_bounds__(256) void rope_half_kernel(T* __restrict__ buf, int
     E::store8(p, ylo); E::store8(p + HALF, yhi);
 }
 
-__device__ __forceinline__ float gelu_new_f(float x) {          // 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))
-    const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-    return 0.5f * x * (1.0f + tanhf(u));
-}
-
 // out[m][n] = rnd(rnd(gelu_new(ab[m][n])) * ab[m][F + n]): T5DenseGatedActDense between its GEMMs. One thread per 8 columns.
 template <typename T>
 __global__ __launch_bounds__(256) void gated_gelu_kernel(const T* __restrict__ ab, int64_t ld, T* __restrict__ out, int64_t ldo, int64_t M, int64_t F8) {
@@ -357,11 +352,11 @@ __global__ __launch_bounds__(256) void gated_gelu_kernel(const T* __restrict__ a
     E::load8(ab + mrow * ld + 8 * ch, a);
     E::load8(ab + mrow * ld + 8 * (F8 + ch), bb);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = E::rnd(gelu_new_f(a[e])) * bb[e];
+    for (int e = 0; e < 8; ++e) y[e] = E::rnd(gelu_tanh_exact(a[e])) * bb[e];
     E::store8(out + mrow * ldo + 8 * ch, y);
 }
 
-// Contiguous activations between CLIP's fc1 and fc2, n a multiple of 8, one thread per 16-byte (bf16) / 2 x 16-byte (fp32) chunk; y may alias x.
+// Contiguous activations between CLIP's fc1 and fc2 (PwMap, pointwise.h), n a multiple of 8, one thread per 16-byte (bf16) / 2 x 16-byte (fp32) chunk; y may alias x.
 struct QuickGelu {             // y = x sigmoid(1.702 x): CLIP-L's "quick_gelu"
     static __device__ __forceinline__ float f(float a) { return a / (1.0f + expf(-1.702f * a)); }
 };
@@ -375,18 +370,6 @@ struct GeluErf {
         return a < 0.0f ? 0.5f * a * erfcf(-u) : 0.5f * a * (1.0f + erff(u));
     }
 };
-
-template <typename T, typename Act>
-__global__ __launch_bounds__(256) void act8_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8) {
-    using E = ElemT<T>;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    float a[8], r[8];
-    E::load8(x + 8 * i, a);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = Act::f(a[e]);
-    E::store8(y + 8 * i, r);
-}
 
 constexpr int REL_LEN_MAX = 4096;             // (2 x 4096 - 1) floats = 32 KiB of table beside the 18 KiB of tiles
 
@@ -496,11 +479,8 @@ static int act8_launch(const char* who, Act, const void* x, void* y, int64_t n, 
     UG_REQUIRE(x && y && n > 0, UG_ERR_BAD_SHAPE, "%s: bad arguments", who);
     UG_REQUIRE(n % 8 == 0, UG_ERR_UNSUPPORTED, "%s: n = %lld must be a multiple of 8", who, (long long)n);
     UG_REQUIRE(ug_aligned(x, 16) && ug_aligned(y, 16), UG_ERR_BAD_ALIGN, "%s: tensors must be 16-byte aligned", who);
-    const int64_t nblk = (n / 8 + 255) / 256;
-    UG_REQUIRE(nblk < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: too many elements", who);
-    hipLaunchKernelGGL((act8_kernel<T, Act>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n / 8);
-    UG_CHECK_LAUNCH(who);
-    return UG_OK;
+    UG_REQUIRE(ug_cdiv(n / 8, 256) < (1ll << 31), UG_ERR_UNSUPPORTED, "%s: too many elements", who);
+    return pointwise_launch<T, PwMap<T, Act>, PwLoop::One>(who, ug_grid1d(n / 8, 256), stream, (const T*)x, (T*)y, n / 8);
 }
 
 template <typename T>

@@ -43,6 +43,11 @@ int ug_env_int(const char* name, int dflt);
     extern "C" int NAME##_f32 PARAMS { return IMPL<float> ARGS; }
 
 static inline bool ug_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+static inline int64_t ug_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of a 1-D launch over n items, `per` to a block, at most `cap` of them: the cap is each caller's own (it decides how many trips a
+// grid-stride loop makes); a kernel that makes one trip passes none and checks the count itself
+constexpr int64_t UG_GRID_NOCAP = INT64_MAX;
+static inline unsigned ug_grid1d(int64_t n, int64_t per, int64_t cap = UG_GRID_NOCAP) { const int64_t g = ug_cdiv(n, per); return (unsigned)(g < cap ? g : cap); }
 
 // ---- strided attention views (host; unigen_hip.h "Strided attention views") -----------------------------------------------------------
 // An attention operand as the entry points take it: base pointer, row stride and batch stride in elements. A plain buffer (workspace, state)
@@ -87,24 +92,37 @@ __device__ __forceinline__ float bfhi(unsigned u) { return __uint_as_float(u & 0
 // ---- element traits: one kernel source for the product path (bf16 storage, the reference's bf16 rounding points) and the
 // fp32 VERIFICATION path (`*_f32` entry points: fp32 storage, no intermediate rounding). 8 elements per access in both. ------
 template <typename T> struct ElemT;
+// guarded forms of load8 / store8, in both specialisations: one 16-byte (bf16) / 2 x 16-byte (fp32) access where the caller found the address
+// aligned (`vec`), eight element accesses otherwise
+#define UG_ELEM_GUARDED8(T)                                                                                               \
+    static __device__ __forceinline__ void load8(const T* p, float* f, bool vec) {                                        \
+        if (vec) load8(p, f);                                                                                             \
+        else { _Pragma("unroll") for (int j = 0; j < 8; ++j) f[j] = ld(p + j); }                                         \
+    }                                                                                                                     \
+    static __device__ __forceinline__ void store8(T* p, const float* f, bool vec) {                                       \
+        if (vec) store8(p, f);                                                                                            \
+        else { _Pragma("unroll") for (int j = 0; j < 8; ++j) st(p + j, f[j]); }                                          \
+    }
 template <> struct ElemT<bf16_t> {
     static constexpr bool kF32 = false;
-    static __device__ __forceinline__ void load8(const bf16_t* p, float* f) {
-        const u32x4 v = *(const u32x4*)p;
+    static __device__ __forceinline__ void unpack8(const u32x4 v, float* f) {         // the register forms: 8 bf16 in 4 registers <-> 8 floats
         f[0] = bflo(v.x); f[1] = bfhi(v.x); f[2] = bflo(v.y); f[3] = bfhi(v.y);
         f[4] = bflo(v.z); f[5] = bfhi(v.z); f[6] = bflo(v.w); f[7] = bfhi(v.w);
     }
-    static __device__ __forceinline__ void store8(bf16_t* p, const float* f) {
+    static __device__ __forceinline__ u32x4 pack8(const float* f) {
         u32x4 v;
         v.x = pack2bf(f[0], f[1]); v.y = pack2bf(f[2], f[3]); v.z = pack2bf(f[4], f[5]); v.w = pack2bf(f[6], f[7]);
-        *(u32x4*)p = v;
+        return v;
     }
+    static __device__ __forceinline__ void load8(const bf16_t* p, float* f) { unpack8(*(const u32x4*)p, f); }
+    static __device__ __forceinline__ void store8(bf16_t* p, const float* f) { *(u32x4*)p = pack8(f); }
     static __device__ __forceinline__ void zero8(bf16_t* p) { *(u32x4*)p = (u32x4){0u, 0u, 0u, 0u}; }
     static __device__ __forceinline__ void load2(const bf16_t* p, float* f) { const unsigned v = *(const unsigned*)p; f[0] = bflo(v); f[1] = bfhi(v); }
     static __device__ __forceinline__ void store2(bf16_t* p, const float* f) { *(unsigned*)p = pack2bf(f[0], f[1]); }
     static __device__ __forceinline__ float rnd(float x) { return rbf(x); }          // a bf16 tensor op's output
     static __device__ __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); }
     static __device__ __forceinline__ void st(bf16_t* p, float x) { *p = f2bf(x); }
+    UG_ELEM_GUARDED8(bf16_t)
 };
 template <> struct ElemT<float> {
     static constexpr bool kF32 = true;
@@ -122,7 +140,34 @@ template <> struct ElemT<float> {
     static __device__ __forceinline__ float rnd(float x) { return x; }
     static __device__ __forceinline__ float ld(const float* p) { return *p; }
     static __device__ __forceinline__ void st(float* p, float x) { *p = x; }
+    UG_ELEM_GUARDED8(float)
 };
+#undef UG_ELEM_GUARDED8
+
+// ---- activations (device): one copy each, so that a forward, its backward and the GEMM epilogue that share a formula share its bits ----------
+// tanh GELU, fast form: 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3)  ==  x / (1 + exp(-2u)): 3 multiplies/FMAs, v_exp_f32, add,
+// v_rcp_f32, multiply (the textbook form with an IEEE division is ~24 VALU instructions per element; the GEMM epilogue is VALU-bound). No
+// cancellation for x << 0, exp -> inf gives rcp -> 0 -> -0. The GEMM epilogues (gemm_epilogue.h) and ug_gelu_tanh (backward.hip).
+__device__ __forceinline__ float gelu_tanh(float x) {
+    constexpr float C0 = -2.3022081986f;            // -2 sqrt(2/pi) log2(e)
+    constexpr float C1 = C0 * 0.044715f;
+    const float u = x * fmaf(x * x, C1, C0);
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u));
+}
+// tanh GELU, exact form with tanhf: T5's gelu_new (text.hip) and the fp32 GEMM's epilogue (verify_f32.hip)
+__device__ __forceinline__ float gelu_tanh_exact(float x) {
+    const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+    return 0.5f * x * (1.0f + tanhf(u));
+}
+// sigmoid and SiLU: rcp / exp2 on the bf16 path, IEEE division and expf on the fp32 verification path
+template <typename T> __device__ __forceinline__ float sigmoid(float x) {
+    if constexpr (ElemT<T>::kF32) return 1.0f / (1.0f + expf(-x));
+    else return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
+}
+template <typename T> __device__ __forceinline__ float silu(float x) {
+    if constexpr (ElemT<T>::kF32) return x / (1.0f + expf(-x));
+    else return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
+}
 
 // logical row -> physical row of a concatenated buffer (see unigen_hip.h "row map")
 __device__ __forceinline__ int64_t ug_rowmap(int64_t m, int64_t rpb, int64_t bstride) {

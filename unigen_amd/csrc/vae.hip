@@ -644,7 +644,7 @@ int to_nhwc_impl(const void* in, void* out, int64_t B, int64_t C, int64_t HW, in
     if (B == 0) return UG_OK;
     UG_REQUIRE(in && out && B > 0 && C > 0 && HW > 0 && Cp >= C && B * HW * Cp < (1ll << 40) && HW < (1ll << 31), UG_ERR_BAD_SHAPE, "ug_nchw_to_nhwc: bad arguments");
     const int64_t total = B * HW * Cp;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (int)B, (int)C,
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(ug_grid1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (int)B, (int)C,
                        (int)HW, (int)Cp, div, add);
     UG_CHECK_LAUNCH("ug_nchw_to_nhwc");
     return UG_OK;
@@ -654,7 +654,7 @@ int to_nchw_impl(const void* in, void* out, int64_t B, int64_t C, int64_t HW, in
     if (B == 0) return UG_OK;
     UG_REQUIRE(in && out && B > 0 && C > 0 && HW > 0 && Cp >= C && B * HW * Cp < (1ll << 40) && HW < (1ll << 31), UG_ERR_BAD_SHAPE, "ug_nhwc_to_nchw: bad arguments");
     const int64_t total = B * C * HW;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (int)B, (int)C,
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(ug_grid1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)in, (T*)out, (int)B, (int)C,
                        (int)HW, (int)Cp);
     UG_CHECK_LAUNCH("ug_nhwc_to_nchw");
     return UG_OK;
@@ -664,7 +664,7 @@ int sample_impl(const void* mom, int64_t Cp, const void* noise, void* z, int64_t
     if (B == 0) return UG_OK;
     UG_REQUIRE(mom && noise && z && B > 0 && L > 0 && HW > 0 && Cp >= 2 * L && HW < (1ll << 31), UG_ERR_BAD_SHAPE, "ug_vae_sample: bad arguments");
     const int64_t total = B * L * HW;
-    hipLaunchKernelGGL(vae_sample_kernel<T>, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)mom, (int)Cp, (const T*)noise,
+    hipLaunchKernelGGL(vae_sample_kernel<T>, dim3(ug_grid1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)mom, (int)Cp, (const T*)noise,
                        (T*)z, (int)B, (int)L, (int)HW, shift, scale);
     UG_CHECK_LAUNCH("ug_vae_sample");
     return UG_OK;
@@ -700,7 +700,7 @@ int tile_blend_impl(const ug_vae_blend_desc* dp, ug_stream_t stream) {
     const int mode = !cvec ? 0 : (d.oc == 1 && ug_aligned(d.out, 16) && d.ob % 8 == 0 && d.oy % 8 == 0 && d.ox % 8 == 0) ? 1 : d.ox == 1 ? 2 : 0;
     const int64_t ng = (d.C + 7) / 8;
     const int64_t total = mode == 0 ? d.B * d.C * d.h * d.w : mode == 1 ? d.B * d.h * d.w * ng : d.B * ng * d.h * ((d.w + 7) / 8 + 1);
-    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 8192));
+    const dim3 grid(ug_grid1d(total, 256, 8192));
     const hipStream_t s = (hipStream_t)stream;
     if (mode == 0) hipLaunchKernelGGL((vae_tile_blend_kernel<T, 0>), grid, dim3(256), 0, s, p);
     else if (mode == 1) hipLaunchKernelGGL((vae_tile_blend_kernel<T, 1>), grid, dim3(256), 0, s, p);
@@ -793,34 +793,20 @@ extern "C" int ug_conv2d_nhwc_f32(const ug_conv_desc* dp, ug_stream_t stream) {
     p.B = (int)d.B; p.H = (int)d.H; p.W = (int)d.W; p.Cin = (int)d.Cin; p.Ho = (int)d.Ho; p.Wo = (int)d.Wo; p.Cout = (int)d.Cout;
     p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad_t = d.pad_t; p.pad_l = d.pad_l; p.up = d.up;
     const int64_t total = d.B * d.Ho * d.Wo * d.Cout;
-    hipLaunchKernelGGL(conv2d_nhwc_f32_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 16384)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(conv2d_nhwc_f32_kernel, dim3(ug_grid1d(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, p);
     UG_CHECK_LAUNCH("ug_conv2d_nhwc_f32");
     return UG_OK;
 }
 
-extern "C" int ug_groupnorm_nhwc(const void* x, const void* gamma, const void* beta, void* out, void* ws, int64_t wsb, int64_t B, int64_t HW, int64_t C, int32_t G, float eps,
-                                 int32_t silu, ug_stream_t s) { return groupnorm_impl<bf16_t>(x, gamma, beta, out, ws, wsb, B, HW, C, G, eps, silu, s); }
-extern "C" int ug_groupnorm_nhwc_f32(const void* x, const void* gamma, const void* beta, void* out, void* ws, int64_t wsb, int64_t B, int64_t HW, int64_t C, int32_t G, float eps,
-                                     int32_t silu, ug_stream_t s) { return groupnorm_impl<float>(x, gamma, beta, out, ws, wsb, B, HW, C, G, eps, silu, s); }
-extern "C" int ug_softmax_rows(const float* S, int64_t ld_s, void* P, int64_t ld_p, int64_t rows, int64_t cols, float scale, ug_stream_t s) {
-    return softmax_impl<bf16_t>(S, ld_s, P, ld_p, rows, cols, scale, s);
-}
-extern "C" int ug_softmax_rows_f32(const float* S, int64_t ld_s, void* P, int64_t ld_p, int64_t rows, int64_t cols, float scale, ug_stream_t s) {
-    return softmax_impl<float>(S, ld_s, P, ld_p, rows, cols, scale, s);
-}
-extern "C" int ug_nchw_to_nhwc(const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, float div, float add, ug_stream_t s) {
-    return to_nhwc_impl<bf16_t>(in, out, B, C, HW, Cp, div, add, s);
-}
-extern "C" int ug_nchw_to_nhwc_f32(const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, float div, float add, ug_stream_t s) {
-    return to_nhwc_impl<float>(in, out, B, C, HW, Cp, div, add, s);
-}
-extern "C" int ug_nhwc_to_nchw(const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, ug_stream_t s) { return to_nchw_impl<bf16_t>(in, out, B, C, HW, Cp, s); }
-extern "C" int ug_nhwc_to_nchw_f32(const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, ug_stream_t s) { return to_nchw_impl<float>(in, out, B, C, HW, Cp, s); }
-extern "C" int ug_vae_sample(const void* mom, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale, ug_stream_t s) {
-    return sample_impl<bf16_t>(mom, Cp, noise, z, B, L, HW, shift, scale, s);
-}
-extern "C" int ug_vae_sample_f32(const void* mom, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale, ug_stream_t s) {
-    return sample_impl<float>(mom, Cp, noise, z, B, L, HW, shift, scale, s);
-}
-extern "C" int ug_vae_tile_blend(const ug_vae_blend_desc* d, ug_stream_t s) { return tile_blend_impl<bf16_t>(d, s); }
-extern "C" int ug_vae_tile_blend_f32(const ug_vae_blend_desc* d, ug_stream_t s) { return tile_blend_impl<float>(d, s); }
+UG_TWINS(ug_groupnorm_nhwc, groupnorm_impl,
+         (const void* x, const void* gamma, const void* beta, void* out, void* ws, int64_t wsb, int64_t B, int64_t HW, int64_t C, int32_t G, float eps, int32_t silu,
+          ug_stream_t s),
+         (x, gamma, beta, out, ws, wsb, B, HW, C, G, eps, silu, s))
+UG_TWINS(ug_softmax_rows, softmax_impl, (const float* S, int64_t ld_s, void* P, int64_t ld_p, int64_t rows, int64_t cols, float scale, ug_stream_t s),
+         (S, ld_s, P, ld_p, rows, cols, scale, s))
+UG_TWINS(ug_nchw_to_nhwc, to_nhwc_impl, (const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, float div, float add, ug_stream_t s),
+         (in, out, B, C, HW, Cp, div, add, s))
+UG_TWINS(ug_nhwc_to_nchw, to_nchw_impl, (const void* in, void* out, int64_t B, int64_t C, int64_t HW, int64_t Cp, ug_stream_t s), (in, out, B, C, HW, Cp, s))
+UG_TWINS(ug_vae_sample, sample_impl, (const void* mom, int64_t Cp, const void* noise, void* z, int64_t B, int64_t L, int64_t HW, float shift, float scale, ug_stream_t s),
+         (mom, Cp, noise, z, B, L, HW, shift, scale, s))
+UG_TWINS(ug_vae_tile_blend, tile_blend_impl, (const ug_vae_blend_desc* d, ug_stream_t s), (d, s))

@@ -86,8 +86,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const ug_gemm_desc p) {
             if (n >= p.N) continue;
             float v = acc[i][j] + (bias ? bias[n] : 0.f);
             if (gelu_tile) {
-                const float u = 0.7978845608028654f * (v + 0.044715f * v * v * v);      // F.gelu(approximate="tanh")
-                v = 0.5f * v * (1.0f + tanhf(u));
+                v = gelu_tanh_exact(v);                                                 // F.gelu(approximate="tanh")
             } else if (p.epilogue == UG_EPI_RES_GATE) {
                 v = rrow[n] + grow[n] * v;
             } else if (p.epilogue == UG_EPI_RES_SCALE) {
