@@ -987,6 +987,55 @@ int ug_gather_rows_scaled(const void* src, int64_t ld_src, const int32_t* idx, v
 int ug_gather_rows_scaled_f32(const void* src, int64_t ld_src, const int32_t* idx, void* out, int64_t ld_out, int64_t n, int64_t W, float scale,
                               ug_stream_t stream);
 
+/* ---- DC-AE (csrc/dcae.hip; unigen_amd/dcae.py: diffusers' AutoencoderDC, the 32x autoencoder of Sana). Its convolutions are ug_conv2d_nhwc, its 1x1
+ * convolutions and linears ug_gemm_bf16, its attention ug_linear_attn, the middle of its GLUMBConv ug_glu_dwconv3x3. Below are the remaining passes over
+ * NHWC activations: rows with an explicit row stride in elements. Every bf16 entry has an `_f32` twin (fp32 storage, no intermediate rounding)
+ * declared beside it. No workspace, no atomics, no state: two calls give the same bits and each call can be captured in a graph. Zero-sized calls
+ * return UG_OK without a launch. ---- */
+/* diffusers' RMSNorm(C, eps, elementwise_affine = True, bias = True) over the channel row, fused with what follows it in DC-AE:
+ *   y = rnd((x * rsqrt(mean(x^2) + eps)) * w + b)      fp32 statistics and arithmetic, ONE rounding
+ *   out = residual ? rnd(y + residual) : act == 1 ? relu(y) : y
+ * (the residual of ResBlock, GLUMBConv and the attention; the decoder's norm_out + ReLU). residual: rows at ldr, or NULL (ldr ignored); a residual
+ * together with act = 1 is UG_ERR_UNSUPPORTED. x, residual and out may be one another. C a multiple of 8, at most 4608 (UG_ERR_UNSUPPORTED): the row
+ * is read once, with 16-byte accesses, and kept in registers. ldx, ldo, ldr multiples of 8 (twin: 4) elements, every base 16-byte aligned. */
+int ug_rmsnorm_bias_rows(const void* x, int64_t ldx, const void* w, const void* bias, const void* residual, int64_t ldr, void* out, int64_t ldo, int64_t rows,
+                         int64_t C, float eps, int32_t act, ug_stream_t stream);
+int ug_rmsnorm_bias_rows_f32(const void* x, int64_t ldx, const void* w, const void* bias, const void* residual, int64_t ldr, void* out, int64_t ldo,
+                             int64_t rows, int64_t C, float eps, int32_t act, ug_stream_t stream);
+/* SanaMultiscaleAttentionProjection, one scale: a depthwise k x k convolution (zero padding k / 2, no bias), then a grouped 1x1 convolution with G
+ * groups of 32 channels in and 32 out (no bias). x NHWC [B][H][W] rows of G * 32 channels with row stride ldx; w_dw: proj_in.weight [G*32][1][k][k]
+ * repacked as [k*k][G*32] (tap ky k + kx major); w_pw: proj_out.weight [G*32][32][1][1], that is [G][32 out][32 in] as stored.
+ *   a = rnd(dwconv(x))  (fp32 accumulate)      out[..][g*32 + o] = rnd(sum_i a[..][g*32 + i] * w_pw[g][o][i])  (fp32 accumulate, on the matrix cores)
+ * out rows have row stride ldo; columns from G * 32 on are not written. `a` never goes to memory. k = 5 (every published configuration) and k = 3
+ * are built, any other k is UG_ERR_UNSUPPORTED. ldx, ldo multiples of 8 elements and every base 16-byte aligned (UG_ERR_BAD_ALIGN). */
+int ug_msconv_proj(const void* x, int64_t ldx, const void* w_dw, const void* w_pw, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t G,
+                   int32_t k, ug_stream_t stream);
+int ug_msconv_proj_f32(const void* x, int64_t ldx, const void* w_dw, const void* w_pw, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t G,
+                       int32_t k, ug_stream_t stream);
+/* The non-parametric shortcuts of DCDownBlock2d / DCUpBlock2d, of the encoder's out_shortcut and the decoder's in_shortcut, with the add. h NHWC
+ * [B][H][W] rows of Cin channels (row stride ldh); factor f is 1 or 2 (UG_ERR_UNSUPPORTED otherwise).
+ * down: out [B][H / f][W / f] rows of Cout.  u = pixel_unshuffle(h, f): u[c f^2 + dy f + dx] at (y, x) is h[c] at (f y + dy, f x + dx);
+ *       y[n] = rnd(mean_{j < g} u[n g + j]), g = Cin f^2 / Cout, the sum in fp32 in ascending j.
+ * up:   out [B][H f][W f] rows of Cout.      rep[m] = h[m / r], r = Cout f^2 / Cin;  y = pixel_shuffle(rep, f): y[c] at (f y + dy, f x + dx) is
+ *       rep[c f^2 + dy f + dx] at (y, x).
+ * out = x ? rnd(x + y) : y. x (row stride ldx), when x_shuffle = 0, has the layout of out and may be out itself. x_shuffle = 1: x is itself still to
+ * be pixel-(un)shuffled - it has h's pixel grid [B][H][W] and Cout / f^2 (down) resp. Cout f^2 (up) channels (the "pixel_unshuffle" / "pixel_shuffle"
+ * block types, whose convolution runs before the rearrangement). Without x and with g = 1 (down) resp. always (up) the call is a pure copy, bit for bit.
+ * UG_ERR_BAD_SHAPE unless g resp. r is a positive integer and (down) H, W are multiples of f. Cin, Cout multiples of 8 (UG_ERR_UNSUPPORTED); ldh, ldx,
+ * ldo multiples of 8 (twin: 4) elements, every base 16-byte aligned. */
+int ug_dc_shortcut_down(const void* h, int64_t ldh, const void* x, int64_t ldx, int32_t x_shuffle, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
+                        int64_t Cin, int64_t Cout, int32_t factor, ug_stream_t stream);
+int ug_dc_shortcut_down_f32(const void* h, int64_t ldh, const void* x, int64_t ldx, int32_t x_shuffle, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
+                            int64_t Cin, int64_t Cout, int32_t factor, ug_stream_t stream);
+int ug_dc_shortcut_up(const void* h, int64_t ldh, const void* x, int64_t ldx, int32_t x_shuffle, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
+                      int64_t Cin, int64_t Cout, int32_t factor, ug_stream_t stream);
+int ug_dc_shortcut_up_f32(const void* h, int64_t ldh, const void* x, int64_t ldx, int32_t x_shuffle, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W,
+                          int64_t Cin, int64_t Cout, int32_t factor, ug_stream_t stream);
+/* y = rnd(silu(x)) over n contiguous elements (the activation between a ResBlock's two convolutions); y may be x. n a multiple of 8
+ * (UG_ERR_UNSUPPORTED), both 16-byte aligned. The bf16 entry evaluates the sigmoid through exp2 and a reciprocal, the twin with expf and a division. */
+int ug_silu(const void* x, void* y, int64_t n, ug_stream_t stream);
+int ug_silu_f32(const void* x, void* y, int64_t n, ug_stream_t stream);
+
 int ug_version(void);
 const char* ug_last_error(void);
 

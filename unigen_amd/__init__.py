@@ -9,7 +9,7 @@ _LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training
          "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text", "CLIPTextModelWithProjection": "text",
          "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text",
          "SanaTransformerBlock": "sana", "SanaTransformer2DModel": "sana",
-         "Gemma2Model": "gemma", "encode_prompt_sana": "gemma"}
+         "Gemma2Model": "gemma", "encode_prompt_sana": "gemma", "AutoencoderDC": "dcae"}
 __all__ = sorted(_LAZY)
 
 

@@ -1350,3 +1350,61 @@ def gather_rows_scaled(src: torch.Tensor, idx: torch.Tensor, scale: float, out: 
     assert idx.numel() == n and src.shape[1] == W and idx.is_contiguous()
     _call("ug_gather_rows_scaled", dt, src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0), n, W, scale, _stream())
     return out
+
+
+# ---- DC-AE (csrc/dcae.hip; unigen_amd/dcae.py): NHWC activations as 2-D tensors [B * H * W, C] ----
+def rmsnorm_bias_rows(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, eps: float, *, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                      out: Optional[torch.Tensor] = None, C_: Optional[int] = None) -> torch.Tensor:
+    """RMSNorm with weight and bias over the first C_ (default: all) columns of x [rows, ld], one rounding; then + residual, or ReLU. out may be x
+    or the residual."""
+    dt = _act(x, "x")
+    _chk(w, "w", dt); _chk(bias, "bias", dt)
+    rows, Cc = x.shape[0], (x.shape[1] if C_ is None else C_)
+    out = torch.empty(rows, Cc, dtype=dt, device=x.device) if out is None else out
+    _chk(out, "out", dt)
+    assert w.numel() == Cc and bias.numel() == Cc and out.shape[0] == rows
+    if residual is not None:
+        _chk(residual, "residual", dt)
+        assert residual.shape[0] == rows
+    _call("ug_rmsnorm_bias_rows", dt, x.data_ptr(), x.stride(0), w.data_ptr(), bias.data_ptr(), _p(residual), residual.stride(0) if residual is not None else 0,
+          out.data_ptr(), out.stride(0), rows, Cc, eps, 1 if relu else 0, _stream())
+    return out
+
+
+def msconv_proj(x: torch.Tensor, w_dw: torch.Tensor, w_pw: torch.Tensor, out: torch.Tensor, *, B: int, H: int, W: int, G: int, k: int = 5) -> torch.Tensor:
+    """One scale of SanaMultiscaleAttentionProjection: depthwise k x k (w_dw [k*k, G*32], tap-major) then the grouped 1x1 (w_pw [G, 32, 32]) over the
+    first G * 32 columns of x [B*H*W, ld] into those of out [B*H*W, ld']."""
+    dt = _act(x, "x")
+    _chk(w_dw, "w_dw", dt); _chk(w_pw, "w_pw", dt); _chk(out, "out", dt)
+    assert w_dw.is_contiguous() and tuple(w_dw.shape) == (k * k, G * 32) and w_pw.is_contiguous() and w_pw.numel() == G * 32 * 32, (w_dw.shape, w_pw.shape, G, k)
+    assert x.shape[0] == B * H * W and out.shape[0] == B * H * W
+    ev = _timer.begin("msconv") if _timer is not None else None
+    _call("ug_msconv_proj", dt, x.data_ptr(), x.stride(0), w_dw.data_ptr(), w_pw.data_ptr(), out.data_ptr(), out.stride(0), B, H, W, G, k, _stream())
+    if ev is not None:
+        _timer.end("msconv", 2.0 * (k * k + 32) * G * 32 * B * H * W, ev, tag=(B, H, W, G, k))
+    return out
+
+
+def dc_shortcut(h: torch.Tensor, out: torch.Tensor, *, up: bool, B: int, H: int, W: int, Cin: int, Cout: int, factor: int, x: Optional[torch.Tensor] = None,
+                x_shuffle: bool = False) -> torch.Tensor:
+    """The non-parametric DC-AE shortcut of h [B*H*W, ld] (pixel-unshuffle + group mean, or channel repeat + pixel-shuffle), plus x where given;
+    x_shuffle: x has h's pixel grid and is rearranged as h is. H, W are h's."""
+    dt = _act(h, "h")
+    _chk(out, "out", dt)
+    if x is not None:
+        _chk(x, "x", dt)
+    assert h.shape[0] == B * H * W and out.shape[0] == (B * H * W * factor * factor if up else B * (H // factor) * (W // factor)), (h.shape, out.shape)
+    assert x is None or x.shape[0] == (h.shape[0] if x_shuffle else out.shape[0])
+    _call("ug_dc_shortcut_up" if up else "ug_dc_shortcut_down", dt, h.data_ptr(), h.stride(0), _p(x), x.stride(0) if x is not None else 0, 1 if x_shuffle else 0,
+          out.data_ptr(), out.stride(0), B, H, W, Cin, Cout, factor, _stream())
+    return out
+
+
+def silu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """silu(x) on a contiguous tensor, numel a multiple of 8; out may be x itself."""
+    dt = _act(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "out", dt)
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
+    _call("ug_silu", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
+    return out
