@@ -25,6 +25,7 @@ EPS_ATTN = 1e-15
 EPS_NORM = 1e-5
 MARGIN = 1.5                 # the project's standing margin for a kernel that follows its variant's rounding points
 MS_TILE_W = 32               # image columns per workgroup of msconv_proj_kernel (MS_W)
+MS_TILE_H = 16               # image rows per workgroup (MS_ROWS)
 
 
 def bounds(O, O_v):
@@ -40,12 +41,31 @@ def _silu(t):
 # ---------------------------------------------------------------- RMSNorm with weight and bias ------------------------------------------------------
 # (rows, C, mode, ld pad); mode: plain | residual | alias (the residual is the output buffer) | relu
 NORM_SHAPES = [(1, 8), (5, 40), (33, 128), (7, 1024), (3, 4096)]
+# the lane groups of rmsnorm_bias_rows_kernel (lpr lanes per row, C / 8 chunks): lpr 2 with a row in a second workgroup; lpr 4 with 3 live chunks;
+# lpr 32, the last width below a whole wave; 33 chunks, the first whole-wave width; one chunk in the second pass; all nine passes full
+NORM_LANE_SHAPES = [(129, 16), (65, 24), (9, 256), (5, 264), (5, 520), (2, 4608)]
 NORM_MODES = ("plain", "residual", "alias", "relu")
-NORM_SLIPS = ("no_bias", "residual_before_norm")
+NORM_SLIPS = ("no_bias", "residual_before_norm", "no_eps", "eps_after_sqrt")
+NORM_EPS_SLIPS = NORM_SLIPS[2:]
+NORM_SMALL_SCALES = (2.0 ** -10, 2.0 ** -6)      # rows whose mean square (2^-20, 2^-12) lies below and near eps = 1e-5
+
+
+def norm_old_case_ids():
+    """the cases the kernel shipped with: every x ~ N(0, 4), where eps does not matter"""
+    return ["norm-%dx%d-%s" % (r, c, m) for (r, c) in NORM_SHAPES for m in NORM_MODES] + ["norm-5x40-plain-ld56", "norm-6x128-zero_row"]
+
+
+def norm_lane_case_ids():
+    return ["norm-%dx%d-%s" % (r, c, m) for (r, c) in NORM_LANE_SHAPES for m in NORM_MODES]
+
+
+def norm_small_case_ids():
+    return ["norm-6x128-plain-small", "norm-6x128-residual-small"]
 
 
 def norm_case_ids():
-    return ["norm-%dx%d-%s" % (r, c, m) for (r, c) in NORM_SHAPES for m in NORM_MODES] + ["norm-5x40-plain-ld56", "norm-6x128-zero_row"]
+    """ids and seeds go by position: new cases are appended"""
+    return norm_old_case_ids() + norm_lane_case_ids() + norm_small_case_ids()
 
 
 _CACHE = {}
@@ -66,6 +86,8 @@ def norm_case(case_id):
         pad = 16 if case_id.endswith("ld56") else 0
         g = torch.Generator().manual_seed(8100 + norm_case_ids().index(case_id))
         x = (2.0 * torch.randn(rows, C, generator=g)).to(BF)
+        if case_id.endswith("small"):               # rows 0, 2, 4 at the first scale, 1, 3, 5 at the second
+            x = (x.float() * torch.tensor(NORM_SMALL_SCALES).repeat(rows // 2)[:, None]).to(BF)
         zero_row = None
         if case_id.endswith("zero_row"):
             zero_row = 3
@@ -88,12 +110,15 @@ def rmsnorm_bias(x, w, b, r=None, act=0, eps=EPS_NORM):
 
 
 def rmsnorm_bias_variant(x, w, b, r=None, act=0, slip=None, eps=EPS_NORM):
-    """y rounded once, then the sum with the residual rounded once. slips - no_bias: the bias is dropped; residual_before_norm: x + r is normalised"""
+    """y rounded once, then the sum with the residual rounded once. slips - no_bias: the bias is dropped; residual_before_norm: x + r is normalised;
+    no_eps: rsqrt(mean) without eps; eps_after_sqrt: 1 / (sqrt(mean) + eps)"""
     assert slip is None or slip in NORM_SLIPS
     x = x.to(F64)
     if slip == "residual_before_norm" and r is not None:
         x = x + r.to(F64)
-    y = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * w.to(F64)
+    ms = (x * x).mean(-1, keepdim=True)
+    rs = torch.rsqrt(ms) if slip == "no_eps" else 1 / (torch.sqrt(ms) + eps) if slip == "eps_after_sqrt" else torch.rsqrt(ms + eps)
+    y = x * rs * w.to(F64)
     if slip != "no_bias":
         y = y + b.to(F64)
     y = BR.bf16(y)
@@ -104,8 +129,19 @@ def rmsnorm_bias_variant(x, w, b, r=None, act=0, slip=None, eps=EPS_NORM):
 
 # ---------------------------------------------------------------- multiscale projection ------------------------------------------------------------
 # (B, H, W, G); the last is two pixels wider than the kernel's tile: a halo from the neighbouring tile and a ragged last tile
-MS_SHAPES = [(1, 1, 1, 3), (1, 2, 9, 3), (2, 5, 7, 6), (1, 16, 16, 24), (1, 3, MS_TILE_W + 2, 3)]
-MS_SLIPS = ("clamp_padding", "matrix_transposed", "missing_halo_row")
+# Then the seams of the 16-row x 32-column tile: one row in a second row tile (its lower halo wholly outside the image); second tiles both ways,
+# each narrower than halo + tile; three tiles each way (an interior tile with real halo on all four sides, B = 2, and G = 5: a partial group block
+# at NG = 4 and at NG = 2); whole tiles only
+MS_SHAPES = [(1, 1, 1, 3), (1, 2, 9, 3), (2, 5, 7, 6), (1, 16, 16, 24), (1, 3, MS_TILE_W + 2, 3),
+             (1, 17, 5, 3), (1, 20, 33, 4), (2, 35, 70, 5), (1, 48, 96, 8)]
+MS_OLD = 5                   # MS_SHAPES[:MS_OLD] at k = 5 and [1:3] at k = 3 are the cases the kernel shipped with: none has H > MS_TILE_H
+MS_SLIPS = ("clamp_padding", "matrix_transposed", "missing_halo_row", "seam_rows_zero", "seam_cols_zero")
+MS_SEAM_IDS = ["ms%d-%s" % (k, s) for k in (5, 3) for s in ("1x17x5x3", "1x20x33x4", "2x35x70x5", "1x48x96x8")]
+MS_MODEL_LAYOUT_ID = "ms5-2x35x70x5"             # run once more with x and out as column windows of one buffer, as AutoencoderDC calls it
+
+
+def ms_old_case_ids():
+    return ms_case_ids(5)[:MS_OLD] + ms_case_ids(3)[1:3]
 
 
 def ms_case_ids(k=5):
@@ -126,9 +162,16 @@ def ms_case(case_id):
     return _once(case_id, make)
 
 
-def _dw(x, w_dw, clamp=False, drop_row=None):
+def _same_tile(n, shift, tile):
+    """float64 [n]: 1 where position i + shift lies in the tile of i, else 0"""
+    i = torch.arange(n)
+    return (torch.div(i + shift, tile, rounding_mode="floor") == torch.div(i, tile, rounding_mode="floor")).to(F64)
+
+
+def _dw(x, w_dw, clamp=False, drop_row=None, seam=None):
     """x [B, H, W, C] float64, w_dw [C, 1, k, k]: depthwise k x k with zero padding k / 2 (clamp: replicated borders), as shifted sums.
-    drop_row: the taps of that kernel row are left out (a ring one row short)"""
+    drop_row: the taps of that kernel row are left out (a ring one row short); seam = "rows" / "cols": a tap outside the output pixel's own
+    MS_TILE_H-row / MS_TILE_W-column tile reads zero (the neighbouring tile's halo is missing)"""
     B, H, W, C = x.shape
     k = w_dw.shape[-1]
     r = k // 2
@@ -138,7 +181,12 @@ def _dw(x, w_dw, clamp=False, drop_row=None):
         if ky == drop_row:
             continue
         for kx in range(k):
-            y = y + xp[:, ky:ky + H, kx:kx + W, :] * w_dw[:, 0, ky, kx].to(F64)
+            t = xp[:, ky:ky + H, kx:kx + W, :] * w_dw[:, 0, ky, kx].to(F64)
+            if seam == "rows":
+                t = t * _same_tile(H, ky - r, MS_TILE_H)[None, :, None, None]
+            elif seam == "cols":
+                t = t * _same_tile(W, kx - r, MS_TILE_W)[None, None, :, None]
+            y = y + t
     return y
 
 
@@ -157,19 +205,29 @@ def msconv(x, w_dw, w_pw):
 
 def msconv_variant(x, w_dw, w_pw, slip=None):
     """a = bf16(dwconv), out = bf16(grouped 1x1). slips - clamp_padding: replicated borders; matrix_transposed: w[g][i][o] read as w[g][o][i];
-    missing_halo_row: the last kernel row never enters the sum"""
+    missing_halo_row: the last kernel row never enters the sum; seam_rows_zero / seam_cols_zero: rows / columns of the neighbouring tile read as zeros"""
     assert slip is None or slip in MS_SLIPS
-    a = BR.bf16(_dw(x.to(F64), w_dw, clamp=slip == "clamp_padding", drop_row=w_dw.shape[-1] - 1 if slip == "missing_halo_row" else None))
+    a = BR.bf16(_dw(x.to(F64), w_dw, clamp=slip == "clamp_padding", drop_row=w_dw.shape[-1] - 1 if slip == "missing_halo_row" else None,
+                    seam={"seam_rows_zero": "rows", "seam_cols_zero": "cols"}.get(slip)))
     return BR.bf16(_pw(a, w_pw, transposed=slip == "matrix_transposed"))
 
 
 # ---------------------------------------------------------------- shortcuts -------------------------------------------------------------------------
 # (B, H, W, Cin, Cout, f): H, W are the input's
-DOWN_SHAPES = [(1, 2, 2, 8, 16, 2), (2, 4, 6, 16, 16, 2), (1, 2, 2, 64, 256, 2), (2, 3, 5, 64, 8, 1)]
-UP_SHAPES = [(1, 1, 1, 16, 8, 2), (2, 3, 5, 32, 8, 2), (1, 2, 2, 8, 8, 2), (2, 3, 5, 8, 64, 1)]
+# Then the published stage pairs (512 <-> 1024, 512 <-> 512) and the two latent shortcuts (1024 -> 32: a group of 32; 32 -> 1024: 32 repeats), each
+# over several workgroups of dc_shortcut_kernel
+DOWN_SHAPES = [(1, 2, 2, 8, 16, 2), (2, 4, 6, 16, 16, 2), (1, 2, 2, 64, 256, 2), (2, 3, 5, 64, 8, 1),
+               (2, 6, 10, 512, 1024, 2), (1, 4, 6, 512, 512, 2), (2, 9, 11, 1024, 32, 1)]
+UP_SHAPES = [(1, 1, 1, 16, 8, 2), (2, 3, 5, 32, 8, 2), (1, 2, 2, 8, 8, 2), (2, 3, 5, 8, 64, 1),
+             (2, 3, 5, 1024, 512, 2), (1, 2, 3, 512, 512, 2), (1, 3, 5, 32, 1024, 1)]
+SC_OLD = 4                   # the first SC_OLD shapes of each list shipped with the kernel: fewer than 256 threads of work each
 SC_MODES = ("nox", "x", "xshuffle")
 DOWN_SLIPS = ("channel_order_dydxc", "sum_not_mean")
 UP_SLIPS = ("repeat_not_interleave",)
+
+
+def sc_published_case_ids(up):
+    return sc_case_ids(up)[SC_OLD * len(SC_MODES):]
 
 
 def sc_case_ids(up):
@@ -517,22 +575,30 @@ _TYPES = ("ResBlock", "EfficientViTBlock", "EfficientViTBlock")
 TINY = {
     "a": _cfg((64, 128, 128), 1, _TYPES, ((), (5,), ()), "Conv", "interpolate"),
     "b": _cfg((64, 128, 256), 2, _TYPES, ((), (5,), (5,)), "pixel_unshuffle", "pixel_shuffle"),
+    # the published widths of the attention stages: 16 and 32 heads, G = 48 and 96, GLU at 2048 and 4096 channels, 32 latent channels. 66 M values
+    "w": _cfg((512, 1024), 1, ("EfficientViTBlock",) * 2, ((5,), (5,)), "pixel_unshuffle", "pixel_shuffle", latent=32),
 }
 # (config, image H, W); B = 2 everywhere. "a": 64 and 256 tokens at the attention stages of the 32 x 32 image; "b" at 16 x 16: 16 tokens at the last
 # stage, where diffusers takes its quadratic branch
-TINY_RUNS = [("a", 32, 32), ("a", 24, 40), ("b", 16, 16), ("b", 32, 24)]
+# "w" at 24 x 40: two row and two column tiles of the multiscale projection and N = 960 (four chunks of the linear attention) at width 512, then
+# 12 x 20 at width 1024; down 512 -> 1024 (a group of 2), up 1024 -> 512, and the latent shortcuts with a group and a repeat of 32
+TINY_RUNS = [("a", 32, 32), ("a", 24, 40), ("b", 16, 16), ("b", 32, 24), ("w", 24, 40)]
+RUN_W = 4
 
 
 def tiny_quantised(name):
-    """seeded weights of a tiny model on an 8-bit grid: {key: (int8 tensor, exponent e)}, value = q * 2^e, exact in bf16 (tests/sana_ref.py)"""
-    g = torch.Generator().manual_seed(2000 + sum(map(ord, name)))
-    out = {}
-    for k, t in DCAERef(**TINY[name]).state_dict().items():
-        small = k.endswith("bias") or ".norm" in k
-        std = 0.2 if small else 1.0 / math.sqrt(t[0].numel())
-        e = int(round(math.log2(std * math.sqrt(3.0) / 127.0)))
-        out[k] = (torch.randint(-127, 128, t.shape, generator=g, dtype=torch.int8), e)
-    return out
+    """seeded weights of a tiny model on an 8-bit grid: {key: (int8 tensor, exponent e)}, value = q * 2^e, exact in bf16 (tests/sana_ref.py);
+    computed once per process, read-only"""
+    def make():
+        g = torch.Generator().manual_seed(2000 + sum(map(ord, name)))
+        out = {}
+        for k, t in DCAERef(**TINY[name]).state_dict().items():
+            small = k.endswith("bias") or ".norm" in k
+            std = 0.2 if small else 1.0 / math.sqrt(t[0].numel())
+            e = int(round(math.log2(std * math.sqrt(3.0) / 127.0)))
+            out[k] = (torch.randint(-127, 128, t.shape, generator=g, dtype=torch.int8), e)
+        return out
+    return _once("grid-" + name, make)
 
 
 def dequantise(k, q, e):
@@ -545,7 +611,8 @@ def dequantise(k, q, e):
 
 
 def tiny_state_dict(name):
-    return {k: dequantise(k, q, e) for k, (q, e) in tiny_quantised(name).items()}
+    """computed once per process, read-only"""
+    return _once("state-" + name, lambda: {k: dequantise(k, q, e) for k, (q, e) in tiny_quantised(name).items()})
 
 
 def fingerprint(name):
@@ -554,7 +621,7 @@ def fingerprint(name):
 
 
 def tiny_inputs(run):
-    """-> dict(x [2, 3, H, W], z [2, 8, H / 4, W / 4]) bf16: the image for encode, latents of their own for decode"""
+    """-> dict(x [2, 3, H, W], z [2, latent channels, H / f, W / f]) bf16: the image for encode, latents of their own for decode"""
     name, H, W = TINY_RUNS[run]
     g = torch.Generator().manual_seed(8500 + run)
     f = 2 ** (len(TINY[name]["encoder_block_out_channels"]) - 1)

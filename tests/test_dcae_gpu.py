@@ -4,8 +4,14 @@ rel-L2 of the float64 truth; the bf16 path no further from that truth than 1.25 
 Configuration "a" (tests/golden/dcae_tiny.safetensors holds its inputs and float64 outputs): "Conv" / "interpolate", one layer per stage, a 5 x 5 scale at
 the middle stage; 32 x 32 (64 and 256 tokens at the attention stages) and 24 x 40 images. Configuration "b": "pixel_unshuffle" / "pixel_shuffle", two
 layers per stage, widths (64, 128, 256), the reference evaluated here; its 16 x 16 image has 16 tokens at the last stage, where diffusers takes its
-quadratic branch and this package the same linear kernel."""
+quadratic branch and this package the same linear kernel. Configuration "w": two EfficientViTBlock stages at the published attention widths 512 and
+1024 (16 and 32 heads, G = 48 and 96 in the multiscale projection, GLU at 2048 and 4096 channels), 32 latent channels, on a 24 x 40 image: two row and
+two column tiles of ug_msconv_proj written in place behind its input, N = 960 and 240 tokens, the shortcuts 512 <-> 1024 and the latent ones with a
+group and a repeat of 32. Its 66 M weights come from the seeded grid; the fixture holds its float64 outputs too (their evaluation takes longer than
+all the rest of its test), tests/test_dcae_ref_cpu.py checks them against a fresh evaluation, and the reference's bf16 evaluation is made here, once
+per process."""
 import os
+import time
 
 import pytest
 import torch
@@ -26,12 +32,15 @@ _TRUTH = {}
 
 
 def truth(run):
-    """(float64 latent, float64 image, bf16-evaluated latent, bf16-evaluated image) of a run; "a" reads the float64 pair from the fixture"""
+    """(float64 latent, float64 image, bf16-evaluated latent, bf16-evaluated image) of a run; "a" and "w" read the float64 pair from the fixture"""
     if run not in _TRUTH:
-        if R.TINY_RUNS[run][0] == "a":
+        name = R.TINY_RUNS[run][0]
+        if name in ("a", "w"):
             from safetensors.torch import load_file
             fx = load_file(GOLDEN)
-            assert torch.equal(fx["fingerprint"], R.fingerprint("a")), "the seeded weight generator no longer gives the fixture's weights"
+            assert torch.equal(fx["fingerprint" if name == "a" else "fingerprint.w"], R.fingerprint(name)), \
+                "the seeded weight generator no longer gives the fixture's weights"
+            assert torch.equal(fx[f"run{run}.x"], R.tiny_inputs(run)["x"]) and torch.equal(fx[f"run{run}.z"], R.tiny_inputs(run)["z"])
             lat, img = fx[f"run{run}.latent"], fx[f"run{run}.sample"]
         else:
             lat, img = R.evaluate(run)
@@ -57,7 +66,9 @@ def model(name, dtype, gpu):
 def test_encode_decode_against_fp64(gpu, run):
     name = R.TINY_RUNS[run][0]
     i = R.tiny_inputs(run)
+    t0 = time.perf_counter()
     lat, img, lat16, img16 = truth(run)
+    t1 = time.perf_counter()
     m32, m16 = model(name, F32, gpu), model(name, BF, gpu)
     z32, y32 = m32.encode(i["x"].float()).latent, m32.decode(i["z"].float()).sample
     assert z32.shape == lat.shape and y32.shape == img.shape and z32.dtype == F32
@@ -66,7 +77,7 @@ def test_encode_decode_against_fp64(gpu, run):
     assert z16.dtype == BF and bool(torch.isfinite(z16).all()) and bool(torch.isfinite(y16).all())
     e_z, e_y, r_z, r_y = rel(z16, lat), rel(y16, img), rel(lat16, lat), rel(img16, img)
     print(f"run {run} {R.TINY_RUNS[run]}: fp32 path encode {e_z32:.3e} decode {e_y32:.3e} (bound 1e-3); bf16 encode {e_z:.3e} (reference's bf16 {r_z:.3e}) "
-          f"decode {e_y:.3e} ({r_y:.3e})")
+          f"decode {e_y:.3e} ({r_y:.3e}); the reference took {t1 - t0:.1f} s of {time.perf_counter() - t0:.1f} s")
     assert e_z32 <= 1e-3 and e_y32 <= 1e-3, (e_z32, e_y32)
     assert e_z <= 1.25 * r_z and e_y <= 1.25 * r_y, (e_z, r_z, e_y, r_y)
 

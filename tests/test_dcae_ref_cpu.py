@@ -25,7 +25,7 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1)
 
 
-@pytest.mark.parametrize("case_id", R.ms_case_ids(5) + R.ms_case_ids(3)[:3])
+@pytest.mark.parametrize("case_id", R.ms_case_ids(5)[:R.MS_OLD] + R.ms_case_ids(3)[:3] + R.MS_SEAM_IDS)
 def test_msconv_against_conv2d(case_id):
     d = R.ms_case(case_id)
     C, k = d["G"] * R.DH, d["k"]
@@ -116,23 +116,92 @@ def test_heads_are_96_channel_chunks_and_the_permutation_commutes():
 
 # ---------------------------------------------------------------- the slips against the GPU bounds -------------------------------------------------
 def _caught(O, O_v, bad):
+    """what tests/test_dcae_kernels_gpu.py's _judge would refuse: an output that is not finite, or one above either bound"""
     b_total, b_row = R.bounds(O, O_v)
     total, worst, _ = BR.err(bad, O)
-    return total > b_total or worst > b_row
+    return not bool(torch.isfinite(bad).all()) or total > b_total or worst > b_row
 
 
-@pytest.mark.parametrize("slip", R.NORM_SLIPS)
+def test_the_new_case_ids_are_the_appended_ones():
+    """ids and seeds go by position: the cases that shipped with the kernels keep theirs"""
+    assert R.ms_case_ids(5)[R.MS_OLD:] + R.ms_case_ids(3)[R.MS_OLD:] == R.MS_SEAM_IDS and R.MS_MODEL_LAYOUT_ID in R.MS_SEAM_IDS
+    assert R.norm_case_ids()[:22] == R.norm_old_case_ids() and R.norm_case_ids()[21] == "norm-6x128-zero_row"
+    assert R.norm_lane_case_ids()[0] == "norm-129x16-plain" and R.norm_lane_case_ids()[-1] == "norm-2x4608-relu" and len(R.norm_case_ids()) == 48
+    assert R.sc_case_ids(False)[:12][-1] == "down-2x3x5x64to8xf1-xshuffle" and R.sc_case_ids(True)[:12][-1] == "up-2x3x5x8to64xf1-xshuffle"
+    assert R.sc_published_case_ids(False)[0] == "down-2x6x10x512to1024xf2-nox" and R.sc_published_case_ids(True)[-1] == "up-1x3x5x32to1024xf1-xshuffle"
+    assert R.TINY_RUNS[R.RUN_W] == ("w", 24, 40) and len(R.TINY_RUNS) == 5
+
+
+def test_lane_cases_reach_the_lane_groups_they_name():
+    """lpr as rmsnorm_bias_rows_impl picks it, and the chunk passes (ceil of C / 8 over 64 lanes) of the whole-wave widths"""
+    def lpr(C):
+        n = 1
+        while n < 64 and n < C // 8:
+            n *= 2
+        return n
+    assert [(lpr(C), -(-(C // 8) // 64)) for _, C in R.NORM_LANE_SHAPES] == [(2, 1), (4, 1), (32, 1), (64, 1), (64, 2), (64, 9)]
+    assert {lpr(C) for _, C in R.NORM_SHAPES} == {1, 8, 16, 64}                     # what the first cases ran
+    rows, C = R.NORM_LANE_SHAPES[0]
+    assert rows == 256 // lpr(C) + 1                                                # one row in a second workgroup
+
+
+def _norm_slipped(cid, slip):
+    d = R.norm_case(cid)
+    return _caught(d["O"], d["O_v"], R.rmsnorm_bias_variant(d["x"], d["w"], d["b"], d["r"], d["act"], slip=slip))
+
+
+def _ms_slipped(cid, slip):
+    d = R.ms_case(cid)
+    return _caught(d["O"], d["O_v"], R.msconv_variant(d["x"], d["w_dw"], d["w_pw"], slip=slip))
+
+
+@pytest.mark.parametrize("slip", R.NORM_SLIPS[:2])
 def test_norm_slips_exceed_the_bound(slip):
-    for cid in ("norm-5x40-residual", "norm-33x128-residual", "norm-7x1024-alias"):
-        d = R.norm_case(cid)
-        assert _caught(d["O"], d["O_v"], R.rmsnorm_bias_variant(d["x"], d["w"], d["b"], d["r"], d["act"], slip=slip)), (slip, cid)
+    for cid in ["norm-5x40-residual", "norm-33x128-residual", "norm-7x1024-alias"] + [c for c in R.norm_lane_case_ids() + R.norm_small_case_ids()
+                                                                                       if "residual" in c or "alias" in c]:
+        assert _norm_slipped(cid, slip), (slip, cid)
+    if slip == "no_bias":
+        for cid in R.norm_lane_case_ids() + R.norm_small_case_ids():
+            assert _norm_slipped(cid, slip), (slip, cid)
 
 
-@pytest.mark.parametrize("slip", R.MS_SLIPS)
+@pytest.mark.parametrize("slip", R.NORM_EPS_SLIPS)
+def test_eps_slips_pass_the_first_cases_and_exceed_the_bound_on_small_rows(slip):
+    """THE GAP: at x ~ N(0, 4) the mean square is 4e5 x eps, and an eps that is missing or added after the square root stays inside every bound -
+    on all the cases the kernel shipped with and on the lane-group cases alike. The one exception is no_eps on the row of zeros, where rsqrt(0)
+    gives a NaN that the finite check refuses: the only place the first suite saw eps at all, and eps_after_sqrt passes it too."""
+    for cid in R.norm_old_case_ids() + R.norm_lane_case_ids():
+        assert _norm_slipped(cid, slip) == (slip == "no_eps" and cid == "norm-6x128-zero_row"), (slip, cid)
+    for cid in R.norm_small_case_ids():
+        assert _norm_slipped(cid, slip), (slip, cid)
+
+
+def test_small_rows_are_below_and_near_eps():
+    for cid in R.norm_small_case_ids():
+        ms = R.norm_case(cid)["x"].double().pow(2).mean(-1)
+        assert bool((ms[0::2] < R.EPS_NORM / 2).all()) and bool((ms[1::2] > 4 * R.EPS_NORM).all()) and bool((ms[1::2] < 400 * R.EPS_NORM).all()), ms
+
+
+@pytest.mark.parametrize("slip", R.MS_SLIPS[:3])
 def test_msconv_slips_exceed_the_bound(slip):
-    for cid in ("ms5-2x5x7x6", "ms5-1x16x16x24", "ms5-1x3x34x3"):
-        d = R.ms_case(cid)
-        assert _caught(d["O"], d["O_v"], R.msconv_variant(d["x"], d["w_dw"], d["w_pw"], slip=slip)), (slip, cid)
+    for cid in ["ms5-2x5x7x6", "ms5-1x16x16x24", "ms5-1x3x34x3"] + R.MS_SEAM_IDS:
+        assert _ms_slipped(cid, slip), (slip, cid)
+
+
+def test_seam_rows_slip_passes_the_first_cases_and_exceeds_the_bound_past_16_rows():
+    """THE GAP: no case the kernel shipped with has more than MS_TILE_H rows, so a second row tile whose halo is missing changes nothing there"""
+    for cid in R.ms_old_case_ids() + R.ms_case_ids(3)[:R.MS_OLD]:
+        assert R.ms_case(cid)["H"] <= R.MS_TILE_H and not _ms_slipped(cid, "seam_rows_zero"), cid
+    for cid in R.MS_SEAM_IDS:
+        assert _ms_slipped(cid, "seam_rows_zero"), cid
+
+
+def test_seam_cols_slip_passes_single_column_tiles_and_exceeds_the_bound_past_32_columns():
+    """the first cases caught it at W = 34 and k = 5 only (two pixels in the second tile); every new case wider than the tile catches it at both k"""
+    for cid in R.ms_case_ids(5) + R.ms_case_ids(3):
+        assert _ms_slipped(cid, "seam_cols_zero") == (R.ms_case(cid)["W"] > R.MS_TILE_W), cid
+    assert [c for c in R.ms_old_case_ids() if R.ms_case(c)["W"] > R.MS_TILE_W] == ["ms5-1x3x34x3"]
+    assert sum(R.ms_case(c)["W"] > 2 * R.MS_TILE_W for c in R.MS_SEAM_IDS) == 4          # an interior column tile, at k = 5 and k = 3
 
 
 @pytest.mark.parametrize("slip", R.DOWN_SLIPS)
@@ -149,7 +218,7 @@ def test_down_slips_exceed_the_bound(slip):
         else:
             assert _caught(d["O"], d["O_v"], bad), (slip, cid)
         hit += 1
-    assert hit >= 6
+    assert hit >= 6 + (6 if slip == "channel_order_dydxc" else 9)
 
 
 def test_up_slip_exceeds_the_bound():
@@ -164,7 +233,7 @@ def test_up_slip_exceeds_the_bound():
         else:
             assert _caught(d["O"], d["O_v"], bad), cid
         hit += 1
-    assert hit >= 9
+    assert hit >= 9 + 9
 
 
 @pytest.fixture(scope="module")
@@ -177,6 +246,24 @@ def test_head_slip_exceeds_the_model_bound(run0):
     lat, img = run0
     lat_s, img_s = R.evaluate(0, head_slip=True)
     assert float((lat_s - lat).norm() / lat.norm()) > 1e-2 and float((img_s - img).norm() / img.norm()) > 1e-2
+
+
+def test_head_slip_exceeds_the_model_bound_at_published_widths():
+    """the same at 16 and 32 heads (configuration "w", widths 512 and 1024)"""
+    assert R.TINY["w"]["encoder_block_out_channels"] == (512, 1024) and R.TINY["w"]["latent_channels"] == 32
+    lat, img = R.evaluate(R.RUN_W)
+    assert lat.shape == (2, 32, 12, 20) and img.shape == (2, 3, 24, 40)
+    from safetensors.torch import load_file
+    fx = load_file(GOLDEN)                                                    # the fixture's pair of this run is this evaluation
+    assert torch.equal(fx["fingerprint.w"], R.fingerprint("w"))
+    i = R.tiny_inputs(R.RUN_W)
+    assert torch.equal(fx[f"run{R.RUN_W}.x"], i["x"]) and torch.equal(fx[f"run{R.RUN_W}.z"], i["z"])
+    assert float((fx[f"run{R.RUN_W}.latent"] - lat).abs().max()) <= 1e-12 * float(lat.abs().max())
+    assert float((fx[f"run{R.RUN_W}.sample"] - img).abs().max()) <= 1e-12 * float(img.abs().max())
+    lat_s, img_s = R.evaluate(R.RUN_W, head_slip=True)
+    e = float((lat_s - lat).norm() / lat.norm()), float((img_s - img).norm() / img.norm())
+    print("head slip at published widths: encode %.3g decode %.3g" % e)
+    assert min(e) > 1e-2
 
 
 def test_fixture_matches_the_generator(run0):
@@ -201,3 +288,23 @@ def test_tiny_weights_are_exact_in_bf16_and_ordinary():
     for k, v in sd.items():
         assert v.dtype == R.BF and bool(torch.isfinite(v).all()), k
     assert abs(float(sd["encoder.down_blocks.0.0.norm.weight"].float().mean()) - 1) < 0.1
+
+
+def test_fuzz_draws_are_inside_what_the_entry_points_accept():
+    """tests/test_fuzz_dcae_gpu.py redraws on the host what an entry point must refuse: every draw it sends obeys the documented rules, the norm's
+    forced draws are the lane-group edges, and the draws reach second tiles, several workgroups and both directions"""
+    from tests import test_fuzz_dcae_gpu as Z
+    ms = [Z.draw_ms(s) for s in range(Z.SEEDS)]
+    for c in ms:
+        assert c["k"] in (3, 5) and 1 <= c["B"] <= 2 and 1 <= c["H"] <= 40 and 1 <= c["W"] <= 80 and 1 <= c["G"] <= 9 and {c["pad_x"], c["pad_o"]} <= {0, 8, 24}
+    assert {c["k"] for c in ms} == {3, 5} and any(c["H"] > R.MS_TILE_H for c in ms) and any(c["W"] > 2 * R.MS_TILE_W for c in ms)
+    no = [Z.draw_norm(s) for s in range(Z.SEEDS)]
+    for s, c in enumerate(no):
+        assert 1 <= c["rows"] <= 300 and c["C"] % 8 == 0 and 8 <= c["C"] <= 4608 and c["mode"] in R.NORM_MODES
+        assert s % 2 or c["C"] // 8 in Z.NORM_EDGES
+    sc = [Z.draw_sc(s) for s in range(Z.SEEDS)]
+    for c in sc:
+        assert c["Cin"] % 8 == 0 and c["Cout"] % 8 == 0 and max(c["Cin"], c["Cout"]) <= 1024 and c["f"] in (1, 2) and c["mode"] in R.SC_MODES
+        num, den = (c["Cout"] * c["f"] ** 2, c["Cin"]) if c["up"] else (c["Cin"] * c["f"] ** 2, c["Cout"])
+        assert num % den == 0 and (c["up"] or (c["H"] % c["f"] == 0 and c["W"] % c["f"] == 0)) and 1 <= c["H"] <= 12 and 1 <= c["W"] <= 12
+    assert {c["up"] for c in sc} == {False, True} and {c["f"] for c in sc} == {1, 2}
