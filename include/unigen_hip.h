@@ -222,6 +222,24 @@ int ug_euler_step(void* x, const void* v, float dt, int64_t n, ug_stream_t strea
  * UniGenSD3Pipeline (src/UniGenPipeline.py:404-407). n elements, contiguous. */
 int ug_cfg_combine(const void* uncond, const void* text, float guidance_scale, void* out, int64_t n, ug_stream_t stream);
 
+/* One step of DPMSolverMultistepScheduler as Sana configures it (dpmsolver++, midpoint, solver_order <= 2, flow prediction, flow sigmas) over n
+ * contiguous elements, in one launch: classifier-free guidance, the flow-to-x0 conversion, the first- or second-order update, the history and the
+ * next forward's input. pred_uncond, pred_text (NULL: no guidance) and model_in (NULL allowed with copies = 0) are bf16, fp32 in the _f32 twin;
+ * sample and x0_prev are fp32 in both. Per element, every line ONE IEEE fp32 operation (no FMA), as torch's tensor ops on fp32 latents round:
+ *     p  = pred_text ? u + gs * (t - u) : u            u, t widened to fp32
+ *     x0 = x - sigma * p
+ *     o  = a * x - b * x0                              order 1 ends here
+ *     o  = o - (0.5f * b) * (rinv * (x0 - m1))         order 2; m1 = x0_prev[i] as the previous step left it
+ *     x0_prev[i] = x0;  sample[i] = o;  model_in[k * n + i] = o rounded to the predictions' type, for k < copies
+ * sigma = sigma_s0; a = sigma_t / sigma_s0, b = alpha_t * (exp(-h) - 1), rinv = 1 / ((lambda_s0 - lambda_s1) / h), formed by the host in fp32
+ * (unigen_amd/sana_pipeline.py). The last step has a = 0, b = -1: the result is x0. model_in stands for `torch.cat([latents] * copies).to(dtype)`.
+ * A thread reads its 8 elements of every operand before it writes any: sample and x0_prev are updated in place, and model_in may be the very buffer
+ * that holds the predictions (model_in + k n = pred_uncond / pred_text) once the transformer has finished reading it; any other overlap of model_in with
+ * the predictions, or of sample / x0_prev with anything else, is undefined. n % 8 == 0 and 16-byte aligned pointers, or UG_ERR_BAD_ALIGN; order outside
+ * {1, 2}: UG_ERR_UNSUPPORTED; a NULL pred_uncond, sample or x0_prev, copies < 0, or copies > 0 without model_in: UG_ERR_BAD_SHAPE. n == 0: UG_OK. */
+int ug_dpm_step(const void* pred_uncond, const void* pred_text, float guidance_scale, float* sample, float* x0_prev, void* model_in, int32_t copies,
+                int32_t order, float sigma, float a, float b, float rinv, int64_t n, ug_stream_t stream);
+
 /* out = bf16(a + b) elementwise (bf16), rows x D with leading dims. */
 int ug_add_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,
                 int64_t rows, int64_t D, ug_stream_t stream);
@@ -433,6 +451,8 @@ int ug_flash_attn_fwd_wide_f32(const void* q, int64_t q_row_stride, int64_t q_ba
 int ug_timestep_embed_f32(const float* t, void* out, int64_t ldo, int64_t B, int32_t dim, ug_stream_t stream);
 int ug_euler_step_f32(void* x, const void* v, float dt, int64_t n, ug_stream_t stream);
 int ug_cfg_combine_f32(const void* uncond, const void* text, float guidance_scale, void* out, int64_t n, ug_stream_t stream);
+int ug_dpm_step_f32(const void* pred_uncond, const void* pred_text, float guidance_scale, float* sample, float* x0_prev, void* model_in, int32_t copies,
+                    int32_t order, float sigma, float a, float b, float rinv, int64_t n, ug_stream_t stream);
 int ug_add_f32(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,
                int64_t rows, int64_t D, ug_stream_t stream);
 int ug_add_rowbcast_f32_f32(void* x, int64_t ldx, const float* table, int64_t ldt, int64_t rows, int64_t rows_per_batch, int64_t D,

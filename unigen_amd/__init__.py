@@ -9,7 +9,9 @@ _LAZY = {"FlowMatchObjective": "objective", "train_step": "objective", "training
          "T5EncoderModel": "text", "CLIPTextModel": "text", "encode_prompt": "text", "CLIPTextModelWithProjection": "text",
          "encode_prompt_sd3": "text", "encode_condition_prompt_sd3": "text",
          "SanaTransformerBlock": "sana", "SanaTransformer2DModel": "sana",
-         "Gemma2Model": "gemma", "encode_prompt_sana": "gemma", "AutoencoderDC": "dcae"}
+         "Gemma2Model": "gemma", "encode_prompt_sana": "gemma", "AutoencoderDC": "dcae",
+         "SanaPipeline": "sana_pipeline", "SanaPipelineOutput": "sana_pipeline", "DPMSolverMultistepScheduler": "sana_pipeline",
+         "sana_denoise_loop": "sana_pipeline"}
 __all__ = sorted(_LAZY)
 
 

@@ -23,7 +23,7 @@ HEADER = os.path.join(ROOT, "include", "unigen_hip.h")      # the C ABI; unigen_
 LIB = os.path.join(HERE, "libunigen_hip.so")
 PROBE_DIR = os.path.join(ROOT, "tools", "probe")
 PROBE_LIB = os.path.join(PROBE_DIR, "libunigen_hip_probe.so")
-SOURCES = ["core.hip", "gemm.hip", "attention.hip", "attn_wide.hip", "elementwise.hip", "moe.hip", "verify_f32.hip", "probe.hip", "vae.hip", "backward.hip", "optim.hip", "lora_bwd.hip", "objective.hip", "text.hip", "image.hip", "depth.hip", "sana.hip", "sana_bwd.hip", "dcae.hip"]
+SOURCES = ["core.hip", "gemm.hip", "attention.hip", "attn_wide.hip", "elementwise.hip", "moe.hip", "verify_f32.hip", "probe.hip", "vae.hip", "backward.hip", "optim.hip", "lora_bwd.hip", "objective.hip", "text.hip", "image.hip", "depth.hip", "sana.hip", "sana_bwd.hip", "dcae.hip", "sched.hip"]
 PROBE_ONLY_SOURCES = ["gemm_pwg.hip", "gemm_tn.hip", "lora_down.hip", "attn_fwd_variants.hip", "attn_bwd_variants.hip"]      # tools/probe/csrc/: kernels that lost their A/B, not in the product library
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # attention: scores are finite or -inf, never NaN; without IEEE mode hipcc drops the NaN-quieting v_max x,x it adds per fmaxf operand

@@ -2,8 +2,8 @@
 // traversal; an op is a struct whose fields are its operands, in the order of its entry point, and which applies itself at an element offset:
 //     int64_t n;                                                    the op's length, its last field but for Relu's vec (see PwLoop for the unit)
 //     template <int W> __device__ void at(int64_t i) const;         elements [i, i + W), W = 8 (one 16-byte access of bf16) or 1
-// Ops: EulerStep, CfgCombine (elementwise.hip), GeluTanhBwd (backward.hip), Relu (depth.hip) and, as PwMap over an activation, GeluTanh
-// (backward.hip), QuickGelu and GeluErf (text.hip). Each keeps the loop that its own kernel had, as a compile-time parameter.
+// Ops: EulerStep, CfgCombine (elementwise.hip), DpmStep1 / DpmStep2 (sched.hip), GeluTanhBwd (backward.hip), Relu (depth.hip) and, as PwMap over an
+// activation, GeluTanh (backward.hip), QuickGelu and GeluErf (text.hip), Silu (dcae.hip). Each keeps the loop that its own kernel had, as a compile-time parameter.
 // Every entry point keeps its own argument checks: they differ in code and message.
 #pragma once
 #include "ug_common.h"

@@ -317,6 +317,27 @@ def cfg_combine(uncond: torch.Tensor, text: torch.Tensor, guidance_scale: float,
     return out
 
 
+def dpm_step(pred_uncond: torch.Tensor, pred_text: Optional[torch.Tensor], guidance_scale: float, sample: torch.Tensor, x0_prev: torch.Tensor,
+             model_in: Optional[torch.Tensor], *, order: int, sigma: float, a: float, b: float, rinv: float = 0.0) -> torch.Tensor:
+    """ug_dpm_step: guidance, x0 = sample - sigma p, the DPM-Solver++ update of `order` and the history, on fp32 `sample` / `x0_prev` in place;
+    `model_in` ([copies x sample.numel()] elements of the predictions' dtype, or None) receives the new sample once per copy."""
+    dt = _act(pred_uncond, "pred_uncond")
+    _chk(sample, "sample", f32); _chk(x0_prev, "x0_prev", f32)
+    n = sample.numel()
+    assert pred_uncond.is_cuda and pred_uncond.is_contiguous() and sample.is_contiguous() and x0_prev.is_contiguous() and pred_uncond.numel() == x0_prev.numel() == n
+    if pred_text is not None:
+        _chk(pred_text, "pred_text", dt)
+        assert pred_text.is_contiguous() and pred_text.numel() == n
+    copies = 0
+    if model_in is not None:
+        _chk(model_in, "model_in", dt)
+        assert model_in.is_contiguous() and n > 0 and model_in.numel() % n == 0
+        copies = model_in.numel() // n
+    _call("ug_dpm_step", dt, pred_uncond.data_ptr(), _p(pred_text), guidance_scale, sample.data_ptr(), x0_prev.data_ptr(), _p(model_in), copies, order,
+          sigma, a, b, rinv, n, _stream())
+    return sample
+
+
 def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     dt = _act(a, "a")
     _chk(b, "b", dt); _chk(out, "out", dt)
